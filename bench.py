@@ -13,18 +13,22 @@ delta=1, reg_dim=(1..5).  One step = zero_grad -> loss_and_acc_for_batch -> back
 on synthetic dSprites-shaped inputs resident in HBM before the timed region; the reparameterisation noise is drawn on
 the device each step.  `--workload mnist|measure` times BASELINE.json configs[2] / configs[4] the same way.
 
-Timing: W warm-up steps, then regions of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize() on both
-sides and timed by the host clock (max over ranks) and by HIP events on the launch stream.  Regions repeat until
->= 1 s has been timed (>= 3 regions); `ms_per_step` / `value` are the MEDIAN region, the spread is under `timing`.
+Timing: W warm-up steps, then ONE region of exactly K steps, bracketed by barrier + torch.cuda.synchronize() on both
+sides and timed by the host clock (max over ranks) and by HIP events on the launch stream; `ms_per_step` / `value` come
+from it.  With --full, regions of K steps repeat until >= --min-seconds (default 1 s) has been timed (>= 3 regions);
+`ms_per_step` / `value` are then the MEDIAN region, the spread is under `timing`.
 
-Prints ONE JSON line (rank 0).  Extra objects in the line:
+--dump-outputs DIR writes what the last timed step computed (bench_outputs) as DIR/<name>.npy; the inputs, the weights
+and the noise are seeded, so the same arguments give the same inputs from run to run.
+
+Prints ONE JSON line (rank 0).  A plain run measures only the headline figure; --full adds (and --breakdown implies it):
   roofline      the dominant kernel of the step, timed live with HIP events on the launch stream in a separate
                 instrumented pass (arvae_profile_begin/_end): algorithmic bytes (or executed MFMA FLOP) per launch /
                 average launch duration against the HBM (or MFMA) peak; `rocprof_names` = the kernel names a
                 rocprofv3 --kernel-trace of this command shows for that label
   cpu_baseline  the CPU oracle (oracle/step.py, a port: the reference's Python cannot travel) timed on this box's host
                 cores on a bounded sample of the same workload (rank 0, N = 1 only), all cores and 8 threads
-  secondary     (default run, N = 1) the Morpho-MNIST B=1024 and MeasureVAE B=256 steps, same timing rules; N > 1: the MeasureVAE
+  secondary     (N = 1) the Morpho-MNIST B=1024 and MeasureVAE B=256 steps, same timing rules; N > 1: the MeasureVAE
                 step, 256 measures per rank (BASELINE.json configs[4], weak scaling)
   dp            (N > 1 or --force-dp) HIP-event cost of the step's gradient all-reduce and grouped all-gather in isolation,
                 and (N > 1) ms per step with the collectives on the launch stream vs the overlap schedule
@@ -345,19 +349,20 @@ class Fence:
         return float(t)
 
 
-def timed_regions(step, steps, warmup, fence, min_total_s=1.0, min_regions=3, max_regions=400):
-    """-> (median region seconds, timing dict, last loss).  Every region is exactly `steps` steps between two fences."""
+def timed_regions(step, steps, warmup, fence, min_total_s=0.0, min_regions=1, max_regions=400):
+    """-> (median region seconds, timing dict, what the last step returned).  Every region is exactly `steps` steps between
+    two fences; the defaults time one region."""
     for i in range(warmup):
         step(i)
     host, dev = [], []
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    loss = None
+    last = None
     while True:
         fence()
         e0.record()                                   # torch's current stream = the stream every library launch goes to
         t0 = time.perf_counter()
         for i in range(steps):
-            loss = step(i)
+            last = step(i)
         e1.record()
         fence()
         host.append(fence.max_over_ranks(time.perf_counter() - t0))
@@ -372,9 +377,9 @@ def timed_regions(step, steps, warmup, fence, min_total_s=1.0, min_regions=3, ma
               'hip_event_ms_per_step_median': float(np.median(dev)) * k, 'timed_seconds_total': sum(host),
               # the regions in order, thinned to <= 32 entries: a box's first second runs slower than its steady state
               'ms_per_step_regions': [round(h * k, 4) for h in host[::max(1, (len(host) + 31) // 32)]],
-              'rule': 'regions of exactly K steps, barrier + synchronize on both sides, repeated until >= 1 s is timed; '
-                      'value and ms_per_step are the median region (host clock, max over ranks)'}
-    return med, timing, loss
+              'rule': f'regions of exactly K steps, barrier + synchronize on both sides, repeated until >= {min_total_s:g} s is '
+                      f'timed (>= {min_regions} regions); value and ms_per_step are the median region (host clock, max over ranks)'}
+    return med, timing, last
 
 
 def kernel_profile(step, n_steps):
@@ -393,6 +398,29 @@ def kernel_profile(step, n_steps):
         prof[name] = {'calls': int(calls), 'ms': float(ms)}
     prof.pop('(gap)', None)          # launch gaps the library marks separately so that kernel times exclude them
     return prof
+
+
+def bench_outputs(trainer, loss, acc):
+    """what a caller of the timed step receives from its last run: the loss and accuracy loss_and_acc_for_batch returned,
+    the loss terms it left in `last_terms`, the model's state after the Adam update and the optimizer's moments (the
+    gradient arena itself is cleared by the update).  name -> float32 numpy array."""
+    out = {'loss': loss, 'accuracy': acc}
+    for k, v in trainer.last_terms.items():
+        if v is not None:
+            out[f'term.{k}'] = v
+    for k, v in trainer.model.state_dict().items():
+        out[f'state.{k}'] = v
+    for k in ('exp_avg', 'exp_avg_sq'):
+        v = getattr(trainer.optimizer, k, None)
+        if v is not None:
+            out[f'adam.{k}'] = v
+    return {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(dirname, trainer, loss, acc):
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in bench_outputs(trainer, loss, acc).items():
+        np.save(os.path.join(dirname, name + '.npy'), arr)
 
 
 # ---- workloads ----------------------------------------------------------------------------------------------------------
@@ -418,7 +446,7 @@ def build_trainer(device, use_dp):
 
 
 def build_side_workload(kind, device, batch, rank=0, use_dp=False, graphs=False):
-    """-> (timed step, eager step for the instrumented pass, unit) for BASELINE.json configs[2] / configs[4]."""
+    """-> (timed step, eager step for the instrumented pass, unit, trainer) for BASELINE.json configs[2] / configs[4]."""
     from arvae_amd import synthetic as syn
     if kind == 'mnist':
         from arvae_amd.image_vae import MnistVAE
@@ -450,10 +478,10 @@ def build_side_workload(kind, device, batch, rank=0, use_dp=False, graphs=False)
 
     def eager(i):
         trainer.zero_grad()
-        loss, _ = trainer.loss_and_acc_for_batch(data, 0, i, True)
+        loss, acc = trainer.loss_and_acc_for_batch(data, 0, i, True)
         trainer.backward(loss)
         trainer.step()
-        return loss
+        return loss, acc
 
     unit = 'images/s' if kind == 'mnist' else 'measures/s'
     if kind == 'measure' and graphs:                             # forward + backward replayed from HIP graphs (graphed.py)
@@ -461,11 +489,11 @@ def build_side_workload(kind, device, batch, rank=0, use_dp=False, graphs=False)
         graphed = GraphedStep(trainer, data)
 
         def gstep(i):
-            loss, _ = graphed(data)
+            loss, acc = graphed(data)
             trainer.step()
-            return loss
-        return gstep, eager, unit
-    return eager, eager, unit
+            return loss, acc
+        return gstep, eager, unit, trainer
+    return eager, eager, unit, trainer
 
 
 def side_roofline(kind, prof, prof_steps, batch):
@@ -525,11 +553,13 @@ def run_side(kind, device, args, fence, rank, world, use_dp, with_cpu):
     # MeasureVAE: a step is two library calls (the whole-model executor; three and one grouped all-gather under data parallelism):
     # eager.  --graphs replays it from a HIP graph, collectives recorded with the kernels
     graphs = kind == 'measure' and not args.no_graphs and args.graphs
-    step, eager, unit = build_side_workload(kind, device, bsz, rank, use_dp, graphs)
+    step, eager, unit, trainer = build_side_workload(kind, device, bsz, rank, use_dp, graphs)
     steps = args.steps if args.workload == kind else max(10, min(args.steps, 50))
-    med, timing, loss = timed_regions(step, steps, args.warmup, fence, args.min_seconds)
+    med, timing, (loss, acc) = timed_regions(step, steps, args.warmup, fence, args.min_seconds, args.min_regions)
+    if args.dump_outputs and args.workload == kind and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss, acc)
     prof_steps = 4
-    prof = kernel_profile(eager, prof_steps)
+    prof = kernel_profile(eager, prof_steps) if args.full else None
     fence()
     rate = world * bsz * steps / med
     flop, byts = SIDE_WORK[kind]
@@ -556,7 +586,7 @@ def run_side(kind, device, args, fence, rank, world, use_dp, with_cpu):
                              'flop_frac_mfma16_3products': per_gpu * flop / (PEAK_BF16_MFMA_TFLOPS / F16X2_PRODUCTS * 1e12),
                              'roof_tflops_fp32_equivalent': PEAK_BF16_MFMA_TFLOPS / F16X2_PRODUCTS,
                              'hbm_frac': per_gpu * byts / (PEAK_HBM_GBS * 1e9)},
-           'roofline': side_roofline(kind, prof, prof_steps, bsz)}
+           'roofline': side_roofline(kind, prof, prof_steps, bsz)}          # (None without --full: no instrumented pass)
     if with_cpu:
         res['cpu_baseline'] = side_cpu_baseline(kind, bsz)
     return res
@@ -685,54 +715,9 @@ def dp_overlap_trial(step, fence, steps=60, warm=10):
     return res
 
 
-# ---- the headline workload ---------------------------------------------------------------------------------------------
-def run_dsprites(device, args, fence, rank, world, use_dp):
-    from arvae_amd import synthetic as syn
-    trainer, state = build_trainer(device, use_dp)
-    if use_dp:
-        trainer.data_parallel.broadcast_parameters(trainer.model)
-    b = args.batch
-    x_np, lab_np = syn.dsprites_batch(b, seed=1234 + rank)
-    x = torch.from_numpy(x_np).to(device)
-    lab = torch.from_numpy(lab_np).to(device)
-
-    def step(i):
-        trainer.zero_grad()
-        loss, _ = trainer.loss_and_acc_for_batch((x, lab), 0, i, True)
-        trainer.backward(loss)                        # = loss.backward() with a cached seed gradient (Trainer.backward)
-        trainer.step()
-        return loss
-
-    med, timing, loss = timed_regions(step, args.steps, args.warmup, fence, args.min_seconds)
-    final_loss = float(loss.detach())
-    if not np.isfinite(final_loss):
-        raise SystemExit(f'non-finite loss {final_loss}')
-
-    # ---- instrumented pass: per-kernel device time from HIP events recorded by the library on the launch stream after
-    # every kernel (arvae_profile_begin/_end); a separate pass so the timed regions are untouched
-    prof_steps = 10
-    prof = kernel_profile(step, prof_steps)
-    for name, v in prof.items():
-        macs, nbytes, fixed = (KERNEL_WORK.get(name, (0, 0)) + (0,))[:3]
-        v['flop'] = 2.0 * macs * b * v['calls']
-        v['bytes'] = (float(nbytes) * b + fixed) * v['calls']
-    fence()
-    dp_info = None
-    if use_dp and hasattr(COMM, 'wait_idle') and b == 512:
-        # (every rank runs these: they are collectives)  The trial comes LAST and under a short deadline: the overlap schedule has
-        # never met a second rank on hardware available to this build, and a failure there must not cost the headline line
-        dp_info = {'world': world, 'collectives_on': 'launch stream (ARVAE_DP_OVERLAP unset)' if os.environ.get('ARVAE_DP_OVERLAP', '0') != '1' else 'side stream (ARVAE_DP_OVERLAP=1)'}
-        try:
-            dp_info.update(dp_collective_costs(trainer, b, device))
-            dp_info['share_of_step'] = (dp_info['all_reduce_us'] + dp_info['all_gather_us']) / (1e6 * med / args.steps)
-        except Exception as e:
-            dp_info['collective_costs_error'] = f'{type(e).__name__}: {e}'
-    run_dsprites.trial = (lambda: dp_overlap_trial(step, fence)) if dp_info is not None and world > 1 else None
-    if rank != 0:
-        return None
-
-    ms_per_step = 1e3 * med / args.steps
-    value = world * b * args.steps / med
+def dsprites_roofline(prof, prof_steps, b, step_s):
+    """the `roofline` object of the headline line (--full): the dominant kernel of the instrumented pass against its roof, the
+    whole step (step_s seconds) against the same roofs, and every launch site of the step"""
     # the dominant kernel = the label with the most device time among ALL labels whose algorithmic work is known
     # (every kernel of the step above 2 % of its device time has a KERNEL_WORK entry; `unaccounted_labels` lists the rest)
     dom_name, dom = max(((k, v) for k, v in prof.items() if v['bytes'] > 0), key=lambda kv: kv[1]['ms'])
@@ -780,7 +765,6 @@ def run_dsprites(device, args, fence, rank, world, use_dp):
     roof['step_algorithmic_bytes'] = BYTES_PER_IMAGE * b + PARAM_BYTES_PER_STEP
     # the whole step against the same roofs (the figure that is comparable from round to round: it does not depend on which
     # kernel is the longest): algorithmic bytes / FLOP of one step over the timed step
-    step_s = med / args.steps
     roof['step'] = {'ms_per_step': 1e3 * step_s,
                     'hbm_frac': (BYTES_PER_IMAGE * b + PARAM_BYTES_PER_STEP) / step_s / (PEAK_HBM_GBS * 1e9),
                     'flop_frac_fp32_equivalent': FLOP_PER_IMAGE * b / step_s / (ARITH_PEAK_TFLOPS['f16x2'] * 1e12),
@@ -813,6 +797,60 @@ def run_dsprites(device, args, fence, rank, world, use_dp):
                  'algorithmic_bytes_per_launch': dom['bytes'] / dom['calls'],
                  'share_of_device_time': dom['ms'] / sum(v['ms'] for v in prof.values()),
                  'unaccounted_labels': sorted(k for k, v in prof.items() if v['bytes'] <= 0)})
+    return roof
+
+
+# ---- the headline workload ---------------------------------------------------------------------------------------------
+def run_dsprites(device, args, fence, rank, world, use_dp):
+    from arvae_amd import synthetic as syn
+    trainer, state = build_trainer(device, use_dp)
+    if use_dp:
+        trainer.data_parallel.broadcast_parameters(trainer.model)
+    b = args.batch
+    x_np, lab_np = syn.dsprites_batch(b, seed=1234 + rank)
+    x = torch.from_numpy(x_np).to(device)
+    lab = torch.from_numpy(lab_np).to(device)
+
+    def step(i):
+        trainer.zero_grad()
+        loss, acc = trainer.loss_and_acc_for_batch((x, lab), 0, i, True)
+        trainer.backward(loss)                        # = loss.backward() with a cached seed gradient (Trainer.backward)
+        trainer.step()
+        return loss, acc
+
+    med, timing, (loss, acc) = timed_regions(step, args.steps, args.warmup, fence, args.min_seconds, args.min_regions)
+    final_loss = float(loss.detach())
+    if not np.isfinite(final_loss):
+        raise SystemExit(f'non-finite loss {final_loss}')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss, acc)
+
+    # ---- instrumented pass (--full): per-kernel device time from HIP events recorded by the library on the launch stream
+    # after every kernel (arvae_profile_begin/_end); a separate pass so the timed regions are untouched
+    prof_steps = 10
+    prof = kernel_profile(step, prof_steps) if args.full else {}
+    for name, v in prof.items():
+        macs, nbytes, fixed = (KERNEL_WORK.get(name, (0, 0)) + (0,))[:3]
+        v['flop'] = 2.0 * macs * b * v['calls']
+        v['bytes'] = (float(nbytes) * b + fixed) * v['calls']
+    fence()
+    dp_info = None
+    if args.full and use_dp and hasattr(COMM, 'wait_idle') and b == 512:
+        # (every rank runs these: they are collectives)  The trial comes LAST and under a short deadline: the overlap schedule has
+        # never met a second rank on hardware available to this build, and a failure there must not cost the headline line
+        dp_info = {'world': world, 'collectives_on': 'launch stream (ARVAE_DP_OVERLAP unset)' if os.environ.get('ARVAE_DP_OVERLAP', '0') != '1' else 'side stream (ARVAE_DP_OVERLAP=1)'}
+        try:
+            dp_info.update(dp_collective_costs(trainer, b, device))
+            dp_info['share_of_step'] = (dp_info['all_reduce_us'] + dp_info['all_gather_us']) / (1e6 * med / args.steps)
+        except Exception as e:
+            dp_info['collective_costs_error'] = f'{type(e).__name__}: {e}'
+    run_dsprites.trial = (lambda: dp_overlap_trial(step, fence)) if dp_info is not None and world > 1 else None
+    if rank != 0:
+        return None
+
+    ms_per_step = 1e3 * med / args.steps
+    value = world * b * args.steps / med
+    roof = dsprites_roofline(prof, prof_steps, b, med / args.steps) if args.full else None
     per_gpu = value / world
     line = {
         'metric': 'training images/sec (dSprites beta-VAE+AR, per-GPU batch 512)', 'value': value,
@@ -846,7 +884,7 @@ def run_dsprites(device, args, fence, rank, world, use_dp):
                   f"{v['bytes'] / max(v['ms'], 1e-9) / 1e6:8.1f} GB/s", file=sys.stderr)
         print(f'  device-time sum {tot / prof_steps * 1e3:.1f} us/step vs wall {ms_per_step * 1e3:.1f} us/step',
               file=sys.stderr)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline(b, state)
     return line
 
@@ -857,11 +895,17 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=30)
     ap.add_argument('--batch', type=int, default=512, help='per-GPU batch')
-    ap.add_argument('--min-seconds', type=float, default=1.0,
-                    help='keep timing K-step regions until this much time is covered (at least 3 regions)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the Morpho-MNIST / MeasureVAE timings of the default run')
-    ap.add_argument('--breakdown', action='store_true', help='print the per-kernel-family table to stderr')
+    ap.add_argument('--min-seconds', type=float, default=None,
+                    help='keep timing K-step regions until this much time is covered (default: 0, one region; with --full: '
+                         '1 s, at least 3 regions)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure: repeated timing regions, the instrumented per-kernel pass and its '
+                         'rooflines, the CPU oracle baseline, the secondary workloads and the data-parallel extras')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU oracle baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='(--full) skip the Morpho-MNIST / MeasureVAE timings')
+    ap.add_argument('--breakdown', action='store_true', help='print the per-kernel-family table to stderr (implies --full)')
     ap.add_argument('--force-dp', action='store_true',
                     help='run the data-parallel code path (RCCL all-gather + all-reduce) even with one rank')
     ap.add_argument('--no-graphs', action='store_true', help='(accepted for older scripts: the measure workload runs eagerly by default)')
@@ -869,6 +913,10 @@ def main():
     ap.add_argument('--workload', default='dsprites', choices=['dsprites', 'mnist', 'measure'],
                     help='dsprites = the headline metric (default); mnist / measure = BASELINE.json configs[2] / configs[4]')
     args = ap.parse_args()
+    args.full = args.full or args.breakdown          # the table comes from the instrumented pass
+    if args.min_seconds is None:
+        args.min_seconds = 1.0 if args.full else 0.0
+    args.min_regions = 3 if args.full else 1
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # before anything touches the GPU: dmabuf IPC only on this pool
                                                                  # (RCCL under `torch.distributed.run bench.py` needs it too)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:             # no launcher: start the ranks (nothing has touched the GPU)
@@ -906,10 +954,11 @@ def main():
     fence = Fence(device, COMM)
 
     if args.workload != 'dsprites':
-        line = run_side(args.workload, device, args, fence, rank, world, use_dp, with_cpu=world == 1 and not args.no_cpu_baseline)
+        line = run_side(args.workload, device, args, fence, rank, world, use_dp,
+                        with_cpu=args.full and world == 1 and not args.no_cpu_baseline)
     else:
         line = run_dsprites(device, args, fence, rank, world, use_dp)
-        if line is not None and world == 1 and not args.force_dp and not args.no_secondary and args.batch == 512:
+        if line is not None and args.full and world == 1 and not args.force_dp and not args.no_secondary and args.batch == 512:
             sec = {}
             for kind in ('mnist', 'measure'):
                 try:
@@ -924,7 +973,7 @@ def main():
             head['secondary_ms_per_step'] = {k: v.get('ms_per_step') for k, v in sec.items()}
             line = {**head, **{k: v for k, v in line.items() if k not in head}}
     comm_ok = True
-    if args.workload == 'dsprites' and use_dp and world > 1 and not args.no_secondary and args.batch == 512:
+    if args.full and args.workload == 'dsprites' and use_dp and world > 1 and not args.no_secondary and args.batch == 512:
         # BASELINE.json configs[4] ("MeasureVAE batch = 256, 1 -> 8 MI355X DP"): weak scaling, 256 measures per rank, the executor's
         # data-parallel path (forward to z, grouped all-gather, arvae_measure_vae_finish, backward, all-reduce, Adam) -- every
         # rank runs it, rank 0 reports it beside the headline

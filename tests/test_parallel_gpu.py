@@ -231,7 +231,7 @@ def test_bench_under_the_drivers_launcher_with_two_ranks():
         env['ARVAE_DP_TRANSPORT'] = 'staged'
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--min-seconds', '0', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, env=env)
+                        '--min-seconds', '0', '--no-cpu-baseline', '--full'], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -254,8 +254,8 @@ def test_bench_refuses_more_ranks_than_gpus():
 
 
 def test_bench_line_has_the_contract_fields():
-    """default-shaped run (short): roofline, timing, secondary workloads with their own rooflines"""
-    line = _bench('--steps', '5', '--warmup', '2', '--min-seconds', '0', '--no-cpu-baseline')
+    """--full run (short): roofline, timing, secondary workloads with their own rooflines"""
+    line = _bench('--steps', '5', '--warmup', '2', '--min-seconds', '0', '--no-cpu-baseline', '--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'timing', 'secondary'):
         assert k in line, k
@@ -279,3 +279,25 @@ def test_bench_line_has_the_contract_fields():
         # (the fraction is of the fp32-MFMA roof; the Morpho-MNIST step multiplies on the fp16 MFMA -- three products per MAC on a pipe
         # 16x as fast -- and sits at 0.95-1.0 of the fp32 roof since round 4: not bounded by 1)
         assert sec['value'] > 0 and sec['roofline']['kernel'] and 0 < sec['step_roofline']['flop_frac_mfma16_3products'] < 1
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_same_outputs(tmp_path):
+    """a plain run times exactly --steps steps, measures nothing beside the headline figure, and --dump-outputs writes what the
+    last timed step computed: the same arrays from two runs with the same arguments"""
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        line = _bench('--steps', '7', '--warmup', '2', '--batch', '64', '--dump-outputs', str(out))
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in line, k
+        assert line['timing']['regions'] == 1 and line['timing']['steps_per_region'] == 7
+        assert abs(line['value'] - 64 * 1e3 / line['ms_per_step']) <= 1e-6 * line['value']
+        assert line['roofline'] is None and line['dp'] is None and 'secondary' not in line and 'cpu_baseline' not in line
+        dumps.append({f.name: np.load(f) for f in sorted(out.iterdir())})
+    a, b = dumps
+    assert {'loss.npy', 'accuracy.npy', 'state.enc_conv.0.weight.npy', 'adam.exp_avg.npy'} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert abs(b['loss.npy'].reshape(-1)[0] - line['config']['final_loss']) <= 1e-6 * abs(line['config']['final_loss'])
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-7, err_msg=k)

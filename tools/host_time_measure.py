@@ -6,7 +6,7 @@ import torch
 import bench
 kind = sys.argv[1] if len(sys.argv) > 1 else 'measure'
 dev = torch.device('cuda:0')
-step, _, unit = bench.build_side_workload(kind, dev, bench.SIDE_BATCH[kind])
+step, _, unit, _ = bench.build_side_workload(kind, dev, bench.SIDE_BATCH[kind])
 for i in range(20):
     step(i)
 torch.cuda.synchronize()

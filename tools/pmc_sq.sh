@@ -4,8 +4,8 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 wl=${1:-mnist}; pat=${2:-conv_wgrad_pairs}
 rm -rf /tmp/pmc_sq
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA --output-format csv -d /tmp/pmc_sq -o p -- python3 bench.py --workload $wl --steps 2 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2>&1
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM --output-format csv -d /tmp/pmc_sq2 -o p -- python3 bench.py --workload $wl --steps 2 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA --output-format csv -d /tmp/pmc_sq -o p -- python3 bench.py --full --workload $wl --steps 2 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM --output-format csv -d /tmp/pmc_sq2 -o p -- python3 bench.py --full --workload $wl --steps 2 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2>&1
 PAT="$pat" python3 - <<'P' > gpurun_out/pmc_sq_$wl.txt
 import csv, glob, os, collections
 pat = os.environ['PAT']

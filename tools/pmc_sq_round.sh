@@ -10,7 +10,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 for wl in dsprites mnist measure; do
   rm -rf /tmp/sq_$wl
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d /tmp/sq_$wl -o p -- python3 bench.py --workload $wl --steps 4 --warmup 2 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2> /tmp/sq_$wl.err
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d /tmp/sq_$wl -o p -- python3 bench.py --full --workload $wl --steps 4 --warmup 2 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2> /tmp/sq_$wl.err
 done
 python3 - $out <<'P'
 import collections, csv, glob, json, sys

@@ -3,7 +3,7 @@ import sys, json, subprocess, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 which = sys.argv[1]
 import torch
-sys.argv = ['bench.py', '--no-cpu-baseline', '--no-secondary']
+sys.argv = ['bench.py', '--full', '--no-cpu-baseline', '--no-secondary']
 import bench
 from arvae_amd import ops
 if which == 'skip':

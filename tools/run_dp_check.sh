@@ -11,12 +11,12 @@ mkdir -p gpurun_out
 : > $out
 ms() { python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('%.4f ms/step  %s' % (d['ms_per_step'], d['config'].get('collectives')))" $1; }
 for i in 1 2 3; do
-    python3 bench.py --no-cpu-baseline --no-secondary > /tmp/dpc_plain.json 2> /dev/null
-    python3 bench.py --no-cpu-baseline --no-secondary --force-dp > /tmp/dpc_dp.json 2> /dev/null
+    python3 bench.py --full --no-cpu-baseline --no-secondary > /tmp/dpc_plain.json 2> /dev/null
+    python3 bench.py --full --no-cpu-baseline --no-secondary --force-dp > /tmp/dpc_dp.json 2> /dev/null
     echo "run $i: plain $(ms /tmp/dpc_plain.json) | forced DP (one rank) $(ms /tmp/dpc_dp.json)" >> $out
 done
-python3 bench.py --workload measure --no-cpu-baseline > /tmp/dpc_m.json 2> /dev/null
-python3 bench.py --workload measure --no-cpu-baseline --force-dp > /tmp/dpc_mdp.json 2> /dev/null
+python3 bench.py --full --workload measure --no-cpu-baseline > /tmp/dpc_m.json 2> /dev/null
+python3 bench.py --full --workload measure --no-cpu-baseline --force-dp > /tmp/dpc_mdp.json 2> /dev/null
 echo "MeasureVAE (whole-model executor, eager): plain $(ms /tmp/dpc_m.json) | forced DP (one rank) $(ms /tmp/dpc_mdp.json)" >> $out
 python3 - >> $out <<'P'
 import json

@@ -11,7 +11,7 @@ var=ARVAE_PAIR_SPLIT$which
 for sp in ${2:-44 46 48 50 54 58}; do
   export $var=$sp
   rm -rf /tmp/sw_k
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sw_k -o p -- python3 bench.py --steps 50 --warmup 10 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sw_k -o p -- python3 bench.py --full --steps 50 --warmup 10 --min-seconds 0 --no-cpu-baseline --no-secondary --no-graphs > /dev/null 2>&1
   echo "$var=$sp"
   python3 tools/kstats.py $(find /tmp/sw_k -name '*kernel_stats.csv' | head -1) 50 30 | grep -i "pair_\|kernels,"
 done

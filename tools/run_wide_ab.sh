@@ -6,8 +6,8 @@ python -m pytest tests/test_hip_parity.py tests/test_inference_gpu.py -x -q -m g
 export ARVAE_LIB=$PWD/ar-vae_amd/libarvae_hip_diag.so
 q() { python -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d["value"]), round(d["ms_per_step"],4))'; }
 for rep in 1 2; do
-  echo "A (tile GEMMs)  $(python bench.py --no-cpu-baseline --workload mnist --steps 30 2>/dev/null | q)"
-  echo "B (row kernels) $(ARVAE_MID_NO_WIDE=1 python bench.py --no-cpu-baseline --workload mnist --steps 30 2>/dev/null | q)"
+  echo "A (tile GEMMs)  $(python bench.py --full --no-cpu-baseline --workload mnist --steps 30 2>/dev/null | q)"
+  echo "B (row kernels) $(ARVAE_MID_NO_WIDE=1 python bench.py --full --no-cpu-baseline --workload mnist --steps 30 2>/dev/null | q)"
 done > gpurun_out/wide_ab.txt 2>&1
 unset ARVAE_LIB
 WORKLOAD=mnist bash tools/trace_kernels.sh all > gpurun_out/wide_trace.txt 2>&1

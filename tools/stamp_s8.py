@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 dev = torch.device('cuda:0')
-step, eager, unit = bench.build_side_workload('mnist', dev, 1024, 0, False, False)
+step, eager, unit, _ = bench.build_side_workload('mnist', dev, 1024, 0, False, False)
 for i in range(3):
     eager(i)
 torch.cuda.synchronize()

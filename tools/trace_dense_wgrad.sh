@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 export ARVAE_DENSE_BATCH_SPLIT=1
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_dw -o p -- python3 bench.py --steps 30 --warmup 5 --min-seconds 0 --no-cpu-baseline --no-secondary > /dev/null 2> /tmp/tr_dw.err
+rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_dw -o p -- python3 bench.py --full --steps 30 --warmup 5 --min-seconds 0 --no-cpu-baseline --no-secondary > /dev/null 2> /tmp/tr_dw.err
 python3 - <<'P'
 import csv, glob, collections
 f = glob.glob('/tmp/tr_dw/**/*kernel_trace.csv', recursive=True)[0]
