@@ -10,7 +10,7 @@ import threading
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libarvae_hip.so')
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_i32, c_i64, c_f32, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
@@ -173,6 +173,8 @@ SIGNATURES = {
     'arvae_comm_broadcast': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     'arvae_comm_group_begin': (c_i32, []),
     'arvae_comm_group_end': (c_i32, []),
+    'arvae_ksg_ws_bytes': (c_i64, [c_i64, c_i32]),
+    'arvae_ksg_mi': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lock = threading.Lock()

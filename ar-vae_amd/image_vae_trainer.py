@@ -165,7 +165,7 @@ class ImageVAETrainer(Trainer):
         return loss, accuracy
 
     # -- evaluation-only inference (image_vae_trainer.py:264-288,381-403): encoder / decoder passes on the forward
-    #    kernels; the metrics fed from here (utils/evaluation.py) stay host-side and are out of scope ---------------------
+    #    kernels; the metrics fed from here (utils/evaluation.py) are arvae_amd.evaluation's ---------------------------
     def _extract_relevant_attributes(self, attributes):
         attr_list = [a for a in self.attr_dict if a not in ('digit_identity', 'color')]
         return attributes[:, [self.attr_dict[a] for a in attr_list]], attr_list
@@ -205,9 +205,9 @@ class ImageVAETrainer(Trainer):
 
     def save_representations(self, path, data_loader=None, batch_size=128):
         """Write the record the reference's compute_eval_metrics consumes (image_vae_trainer.py:289-317): latent codes,
-        attribute columns and attribute names as JSON, from the encoder-only pass.  The disentanglement metrics themselves
-        (utils/evaluation.py: sklearn / scipy on the host) are out of scope: they run unchanged on
-        this file's arrays."""
+        attribute columns and attribute names as JSON, from the encoder-only pass.  compute_eval_metrics computes the
+        disentanglement metrics from the same arrays (arvae_amd.evaluation); the reference's utils/evaluation.py also runs
+        unchanged on this file's arrays."""
         import json
         if data_loader is None:
             _, _, data_loader = self.dataset.data_loaders(batch_size=batch_size)
@@ -216,10 +216,13 @@ class ImageVAETrainer(Trainer):
             json.dump({'latent_codes': codes.tolist(), 'attributes': np.asarray(attrs).tolist(), 'attr_list': list(names)}, f)
         return codes, attrs, names
 
-    def compute_eval_metrics(self, batch_size=128):
+    def compute_eval_metrics(self, batch_size=128, random_state=None):
         """results_dict.json next to the checkpoint, as in the reference (image_vae_trainer.py:289-317): loaded when it exists,
-        otherwise created with what this path computes on the device -- the test loss / accuracy -- and the file the host-side
-        metric suite reads (representations.json)."""
+        otherwise created on the device: the disentanglement metrics of the reference (interpretability, Corr_score,
+        modularity_score, mig, SAP_score: arvae_amd.evaluation, its KSG estimator in HIP), the test loss / accuracy, and
+        representations.json (the codes and attributes they were computed from).  Non-finite metric values are written as JSON
+        null; an evaluation split of at most n_neighbors points leaves the metric keys out with a warning.  random_state: the
+        KSG noise draws (None: fresh, as in the reference; an int s: the c-th KSG call uses RandomState(s + c))."""
         import json
         import os
         folder = os.path.dirname(self.model.filepath)
@@ -230,8 +233,10 @@ class ImageVAETrainer(Trainer):
             return self.metrics
         os.makedirs(folder, exist_ok=True)
         rep_fp = os.path.join(folder, 'representations.json')
-        self.save_representations(rep_fp, batch_size=batch_size)
+        from .evaluation import eval_metrics_or_warn
+        codes, attrs, names = self.save_representations(rep_fp, batch_size=batch_size)
         self.metrics = {'representations': rep_fp}
+        self.metrics.update(eval_metrics_or_warn(codes, attrs, names, random_state=random_state))
         self.metrics.update(self.test_model(batch_size=batch_size))
         with open(results_fp, 'w') as f:
             json.dump(self.metrics, f, indent=2)

@@ -148,3 +148,38 @@ def sample_indices(name, numel, k=16):
     """k deterministic flat indices into a tensor called `name` (golden spot checks)."""
     rs = np.random.RandomState(zlib.crc32(('idx:' + name).encode()) & 0x7fffffff)
     return rs.randint(0, numel, k)
+
+
+# ----------------------------------------------------------------------------
+# disentanglement-metric inputs (arvae_amd.evaluation, tests/golden/make_eval_goldens.py)
+# ----------------------------------------------------------------------------
+# kind -> (N, latent dims, attribute kinds): an int is a grid with that many levels, 'zero' a continuous attribute that
+# sits exactly at 0 on a third of the points (float32 noise survives only there), 'cont' a continuous one
+EVAL_SHAPES = {
+    'small': (600, 4, (3, 'zero', 'cont')),
+    'dsprites': (201 * 128, 10, (3, 6, 40, 32, 32)),
+    'mnist': (201 * 128, 16, ('cont',) * 6),
+    'measure': (201 * 256, 32, (8, 'cont', 'zero', 12)),
+}
+
+
+def eval_metric_inputs(kind, seed=0):
+    """(latent codes (N, z) float32, attributes (N, A) float32, attribute names) shaped like what
+    compute_representations returns for `kind`; attribute a drives latent dimension a (plus noise), the other dimensions
+    are noise, so the metrics land away from their trivial values."""
+    n, z, attrs = EVAL_SHAPES[kind]
+    rs = np.random.RandomState((zlib.crc32(('eval:' + kind).encode()) ^ (seed * 2654435761)) & 0x7fffffff)
+    lab = np.empty((n, len(attrs)), np.float32)
+    for a, what in enumerate(attrs):
+        if what == 'cont':
+            lab[:, a] = rs.standard_normal(n) * (1.0 + a)
+        elif what == 'zero':
+            lab[:, a] = np.maximum(rs.standard_normal(n) + 0.43, 0.0)
+        else:
+            lab[:, a] = rs.randint(0, what, n) / float(what - 1)
+    codes = rs.standard_normal((n, z))
+    for a in range(min(z, len(attrs))):
+        col = lab[:, a].astype(np.float64)
+        col = (col - col.mean()) / col.std()
+        codes[:, a] = (0.9 - 0.15 * a) * col + 0.5 * codes[:, a]
+    return codes.astype(np.float32), lab, [f'attr{a}' for a in range(len(attrs))]

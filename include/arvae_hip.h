@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 11  /* 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 12  /* 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -668,6 +668,22 @@ int arvae_comm_broadcast(arvae_comm_t comm, void *buf, int64_t count, int32_t dt
  * the z and the label all-gather of a step */
 int arvae_comm_group_begin(void);
 int arvae_comm_group_end(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * KSG (Kraskov-Stoegbauer-Grassberger) mutual information of the disentanglement metrics, in fp64.
+ * Replaces: sklearn.feature_selection.mutual_info_regression as called by utils/evaluation.py (interpretability, modularity,
+ * MIG and its entropies); the caller does sklearn's scaling and tie-breaking noise on the host (arvae_amd.evaluation) and
+ * this call reproduces its _compute_mi_cc for each column, bit for bit in the radii and counts:
+ *   r_i  = nextafter(k-th smallest max(|x_j - x_i|, |y_j - y_i|) over j != i, 0)
+ *   nx_i = #{j : |x_j - x_i| <= r_i} - 1,  ny_i likewise with y
+ *   mi   = max(0, psi(n) + psi(k) - mean psi(nx + 1) - mean psi(ny + 1))
+ * x: p columns of n values, column c at x + c * ldx (ldx >= n); y: n values shared by the p columns; 1 <= k <= 8, k < n.
+ * ws: arvae_ksg_ws_bytes(n, p) bytes.  mi_out[p].  radius_out / nx_out / ny_out: optional [p][n] (NULL = not written).
+ * Deterministic: per-workgroup partial sums, then a fixed-order reduction (no float atomics).
+ * ------------------------------------------------------------------------------------------------ */
+int64_t arvae_ksg_ws_bytes(int64_t n, int32_t p);
+int arvae_ksg_mi(const double *x, int64_t ldx, int32_t p, const double *y, int64_t n, int32_t k, void *ws, double *mi_out,
+                 double *radius_out, int32_t *nx_out, int32_t *ny_out, arvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,9 +4,10 @@ defaults, same `models/<repr>/<repr>.pt` and `runs/` side effects, same reg_type
 
 Differences a user can observe: the dataset lives in HBM (arvae_amd.data), a single `-r <name>` works (the
 reference indexes its attribute table with the whole tuple there and raises KeyError), `--no_log` survives the
-second epoch, and after training the script prints the representation summary it can compute on the device
-(latent codes / attributes of the evaluation split, test loss and accuracy) instead of the sklearn metric suite and
-the GIF plots, which are outside this build's scope.
+second epoch, and after training the script prints a representation summary computed on the device (latent codes /
+attributes of the evaluation split, test loss and accuracy); `--metrics` adds the reference's disentanglement metrics
+(Interpretability, SCC, Modularity, MIG, SAP: arvae_amd.evaluation, KSG estimator in HIP) to it.  The GIF plots and the
+Morpho-MNIST ResNet accuracy stay outside this build's scope.
 """
 import json
 import os
@@ -17,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from arvae_amd.evaluation import eval_metrics_or_warn  # noqa: E402
 from arvae_amd.data import DspritesDataset, MorphoMnistDataset  # noqa: E402
 from arvae_amd.image_vae import DspritesVAE, MnistVAE  # noqa: E402
 from arvae_amd.image_vae_trainer import DSPRITES_REG_TYPE, MNIST_REG_TYPES, ImageVAETrainer  # noqa: E402
@@ -47,12 +49,18 @@ IMAGE_FLAGS = [
     (('--rand',), dict(default=None, help='random seed for the random number generator')),
     (('--reg_type', '-r'), dict(default=None, multiple=True, help='attribute name string to be used for regularization')),
 ]
+# not in the reference script (whose evaluation always prints the metrics): opt-in here, so that the summary stays as it was.  It
+# is read by run() around the reference's flag surface (main's parameters stay exactly the reference's)
+METRICS_FLAG = '--metrics'
+METRICS_HELP = (f'{METRICS_FLAG}: add the disentanglement metrics (Interpretability, SCC, Modularity, MIG, SAP; '
+                'arvae_amd.evaluation) to the evaluation summary.')
+with_metrics = False
 
 
 def with_options(fn):
     for names, kwargs in reversed(IMAGE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command()(fn)
+    return click.command(epilog=METRICS_HELP)(fn)
 
 
 @with_options
@@ -114,8 +122,18 @@ def main(dataset_type, batch_size, num_epochs, lr, beta, capacity, gamma, delta,
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'latent_mean_abs': [float(v) for v in abs(codes).mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
+        if with_metrics:
+            summary.update(eval_metrics_or_warn(codes, attrs, names))
         print(json.dumps(summary, indent=2))
 
 
+def run(argv=None):
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics"""
+    global with_metrics
+    argv = sys.argv[1:] if argv is None else list(argv)
+    with_metrics = METRICS_FLAG in argv
+    main(args=[a for a in argv if a != METRICS_FLAG])
+
+
 if __name__ == '__main__':
-    main()
+    run()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Train / evaluate the MeasureVAE on MI355X: counterpart of the reference's train_measure_vae.py (same flags and
 defaults).  Only the `folk` one-bar dataset in its pre-built tensor form is supported (arvae_amd.data.FolkNBarDataset):
-building it from ABC files with music21, and the `bach` chorales, are offline steps outside this build."""
+building it from ABC files with music21, and the `bach` chorales, are offline steps outside this build.  `--metrics` adds the
+reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary."""
 import json
 import os
 import sys
@@ -11,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from arvae_amd.evaluation import eval_metrics_or_warn  # noqa: E402
 from arvae_amd.data import FolkNBarDataset  # noqa: E402
 from arvae_amd.measure_vae import MeasureVAE  # noqa: E402
 from arvae_amd.measure_vae_trainer import MUSIC_REG_TYPE, MeasureVAETrainer  # noqa: E402
@@ -49,12 +51,18 @@ MEASURE_FLAGS = [
     (('--rand',), dict(default=None, help='random seed for the random number generator')),
     (('--reg_type', '-r'), dict(default=None, multiple=True, help='attribute name string to be used for regularization')),
 ]
+# not in the reference script (whose evaluation always prints the metrics): opt-in here, so that the summary stays as it was.  It
+# is read by run() around the reference's flag surface (main's parameters stay exactly the reference's)
+METRICS_FLAG = '--metrics'
+METRICS_HELP = (f'{METRICS_FLAG}: add the disentanglement metrics (Interpretability, SCC, Modularity, MIG, SAP; '
+                'arvae_amd.evaluation) to the evaluation summary.')
+with_metrics = False
 
 
 def with_options(fn):
     for names, kwargs in reversed(MEASURE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command()(fn)
+    return click.command(epilog=METRICS_HELP)(fn)
 
 
 @with_options
@@ -123,8 +131,18 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'attribute_means': [float(v) for v in attrs.mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
+        if with_metrics:
+            summary.update(eval_metrics_or_warn(codes, attrs, names))
         print(json.dumps(summary, indent=2))
 
 
+def run(argv=None):
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics"""
+    global with_metrics
+    argv = sys.argv[1:] if argv is None else list(argv)
+    with_metrics = METRICS_FLAG in argv
+    main(args=[a for a in argv if a != METRICS_FLAG])
+
+
 if __name__ == '__main__':
-    main()
+    run()
