@@ -371,10 +371,7 @@ __global__ __launch_bounds__(256, 2) void down32s_kernel(const float *__restrict
 // ================================================================================================
 // Up on the fp16 MFMA with scaled two-term operands (conv32_common.h): 3 x 32 cycles per 16 channels.  64 weights x 2 terms
 // live in 64 registers (prepared per step, prep32.h); staggered epilogue and gating as described above.
-#ifndef ARVAE_UP_ISSUE_STEPS
-#define ARVAE_UP_ISSUE_STEPS 4
-#endif
-constexpr int UP_ISSUE_STEPS = ARVAE_UP_ISSUE_STEPS;
+constexpr int UP_ISSUE_STEPS = 4;
 template <int LO, int MODE, int PX = 128>
 __device__ __forceinline__ void up32x_body(const float *__restrict__ lo, Ep32 ep, int n_img, int n_tiles, const int BID, const int NBLK) {
     using PL = PatchLoader<LO, 1, PX>;
@@ -1230,28 +1227,24 @@ template <int MODE> static void launch_down_small(const Operand &hi, const Ep32 
 template <int LO, int MODE, int PX>
 static void launch_up_px(const Operand &lo, const Ep32 &ep, int n, hipStream_t s) {
     const int tiles = tiles_for<LO, PX>(n), grid = grid_for_tiles(tiles);
-    if constexpr (LO == 16 && PX == 128) {                      // compute / store waves
-        static const bool pc = diag_env("ARVAE_UP32_NO_PC") == nullptr;       // A/B: up32x_kernel
-        if constexpr (MODE != EP_GATE_F) if (pc) {
-            constexpr int LDSP = (2 * 2 * PatchLoader<16, 1, 128>::PLANE_DW) * 4 + 4 * 4 * 4 * 64 * 16;
-            static std::once_flag attrp;
-            std::call_once(attrp, [&] { allow_lds(up32p_kernel<MODE>, LDSP); });
-            ARVAE_LAUNCH((up32p_kernel<MODE>), dim3(grid), dim3(512), LDSP, s, lo.v, ep, n, tiles);
-            return;
-        }
+    if constexpr (LO == 16 && PX == 128 && MODE != EP_GATE_F) {   // compute / store waves
+        constexpr int LDSP = (2 * 2 * PatchLoader<16, 1, 128>::PLANE_DW) * 4 + 4 * 4 * 4 * 64 * 16;
+        static std::once_flag attrp;
+        std::call_once(attrp, [&] { allow_lds(up32p_kernel<MODE>, LDSP); });
+        ARVAE_LAUNCH((up32p_kernel<MODE>), dim3(grid), dim3(512), LDSP, s, lo.v, ep, n, tiles);
+    } else {
+        constexpr int LDSX = 2 * PatchLoader<LO, 1, PX>::PLANE_DW * 4;
+        static std::once_flag attrx;
+        std::call_once(attrx, [&] { allow_lds(up32x_kernel<LO, MODE, PX>, LDSX); });
+        ARVAE_LAUNCH((up32x_kernel<LO, MODE, PX>), dim3(grid), dim3(256), LDSX, s, lo.v, ep, n, tiles);
     }
-    constexpr int LDSX = 2 * PatchLoader<LO, 1, PX>::PLANE_DW * 4;
-    static std::once_flag attrx;
-    std::call_once(attrx, [&] { allow_lds(up32x_kernel<LO, MODE, PX>, LDSX); });
-    ARVAE_LAUNCH((up32x_kernel<LO, MODE, PX>), dim3(grid), dim3(256), LDSX, s, lo.v, ep, n, tiles);
 }
 // 128-pixel tiles, or 32-pixel tiles when the former give a CU at most one tile (nothing to pipeline, or idle CUs:
 // the 8x8 and 4x4 layers at batch 512)
 template <int LO, int MODE>
 static void launch_up_v(const Operand &lo, const Ep32 &ep, int n, hipStream_t s) {
-    static const bool small_ok = diag_env("ARVAE_NO_SMALL_TILES") == nullptr;     // diagnostic switch
-    if (LO == 4 && small_ok && 2 * tiles_for<LO, 128>(n) <= cu_count()) launch_up_px<4, MODE, 32>(lo, ep, n, s);
-    else if (LO == 8 && small_ok && tiles_for<LO, 128>(n) <= cu_count()) launch_up_px<8, MODE, 32>(lo, ep, n, s);
+    if (LO == 4 && 2 * tiles_for<LO, 128>(n) <= cu_count()) launch_up_px<4, MODE, 32>(lo, ep, n, s);
+    else if (LO == 8 && tiles_for<LO, 128>(n) <= cu_count()) launch_up_px<8, MODE, 32>(lo, ep, n, s);
     else launch_up_px<LO, MODE, 128>(lo, ep, n, s);
 }
 
@@ -1360,7 +1353,7 @@ template <int LO> static int launch_up(const arvae_link_t *l, const Operand &lo,
 // conv32_up of a 4x4 -> 8x8 ReLU layer (forward pass, small tiles) with the regulariser's workgroups riding in
 // the same grid (up32x_reg_kernel); false: not that case, launch the two separately
 bool conv32_up_reg_fits(const arvae_link_t *l) {
-    static const bool off = diag_env("ARVAE_NO_PAIR_REG") != nullptr || diag_env("ARVAE_NO_SMALL_TILES") != nullptr;
+    static const bool off = diag_env("ARVAE_NO_PAIR_REG") != nullptr;
     return !off && conv32_fits(l) && ((l->lh == 4 && 2 * tiles_for<4, 128>(l->n) <= cu_count()) ||
                                       (l->lh == 8 && tiles_for<8, 128>(l->n) <= cu_count()));      // (the cases launch_up_v runs on 32-pixel tiles)
 }
@@ -1437,16 +1430,11 @@ int conv32_amax(const float *x, int64_t count, unsigned *out, hipStream_t s) {
 }
 
 // row-stream weight gradient with producer / consumer waves (wgrad32r.h): the 16x16 and 8x8 layers
-static bool conv32_wgrad_stream_fits(const arvae_link_t *l) {
-    static const bool off = diag_env("ARVAE_WGRAD_NO_STREAM") != nullptr;     // diagnostic: the patch-staged wgrad32x_kernel instead
-    return !off && (l->lh == 16 || l->lh == 8);
-}
+static bool conv32_wgrad_stream_fits(const arvae_link_t *l) { return l->lh == 16 || l->lh == 8; }
 // steps of the whole launch, steps per workgroup and workgroups when `groups` workgroups (at most) share the stream
 static void stream_geometry(const arvae_link_t *l, int groups, int &total, int &spw, int &grid) {
     total = l->n * (l->lh * l->lh / 32);
     spw = (total + groups - 1) / groups;
-    static const int forced = diag_env("ARVAE_WGR_SPW") != nullptr ? atoi(diag_env("ARVAE_WGR_SPW")) : 0;   // diagnostic: steps per workgroup
-    if (forced > 0) spw = forced;
     if (spw < 1) spw = 1;
     grid = (total + spw - 1) / spw;
 }
@@ -1479,10 +1467,8 @@ static int conv32_wgrad_stream(const arvae_link_t *l, const Operand &lo, const O
 
 int conv32_wgrad_groups(const arvae_link_t *l) {
     if (conv32_wgrad_stream_fits(l)) return conv32_wgrad_stream_groups(l);
-    // the patch-staged kernel (4x4 layers; every size with ARVAE_WGRAD_NO_STREAM): 64-pixel tiles, one persistent
-    // workgroup per CU, one 64 KB partial each
-    const int tiles = l->lh == 16 ? tiles_for<16, 64>(l->n) : l->lh == 8 ? tiles_for<8, 64>(l->n) : tiles_for<4, 64>(l->n);
-    return grid_for_tiles(tiles);
+    // the patch-staged kernel (4x4 layers): 64-pixel tiles, one persistent workgroup per CU, one 64 KB partial each
+    return grid_for_tiles(tiles_for<4, 64>(l->n));
 }
 
 int64_t conv32_wgrad_ws_floats(const arvae_link_t *l) {
@@ -1490,23 +1476,22 @@ int64_t conv32_wgrad_ws_floats(const arvae_link_t *l) {
 }
 
 constexpr int LDS_WGRAD_X4 = 2 * (PatchLoader<4, 2, 64>::PLANE_DW / PSB * WGRAD_PSB_H + 64 * WGRAD_PSB_L) * 4;
-template <int LO> static int launch_wgrad_x(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *slab, int bias_mode,
-                                            int grid, const unsigned *amax_lo, const unsigned *amax_hi, hipStream_t s) {
-    constexpr int LDS = 2 * (PatchLoader<LO, 2, 64>::PLANE_DW / PSB * WGRAD_PSB_H + 64 * WGRAD_PSB_L) * 4;
-    const int tiles = tiles_for<LO, 64>(l->n);
+static int launch_wgrad_x4(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *slab, int bias_mode, int grid,
+                           const unsigned *amax_lo, const unsigned *amax_hi, hipStream_t s) {
+    const int tiles = tiles_for<4, 64>(l->n);
     static std::once_flag attr;
     std::call_once(attr, [&] {
-        allow_lds(wgrad32x_kernel<LO, 0>, LDS);
-        allow_lds(wgrad32x_kernel<LO, 1>, LDS);
-        allow_lds(wgrad32x_kernel<LO, 2>, LDS);
+        allow_lds(wgrad32x_kernel<4, 0>, LDS_WGRAD_X4);
+        allow_lds(wgrad32x_kernel<4, 1>, LDS_WGRAD_X4);
+        allow_lds(wgrad32x_kernel<4, 2>, LDS_WGRAD_X4);
     });
     if (bias_mode == 1)
-        ARVAE_LAUNCH((wgrad32x_kernel<LO, 1>), dim3(grid), dim3(256), LDS, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
+        ARVAE_LAUNCH((wgrad32x_kernel<4, 1>), dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
     else if (bias_mode == 2)
-        ARVAE_LAUNCH((wgrad32x_kernel<LO, 2>), dim3(grid), dim3(256), LDS, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
+        ARVAE_LAUNCH((wgrad32x_kernel<4, 2>), dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
     else
-        ARVAE_LAUNCH((wgrad32x_kernel<LO, 0>), dim3(grid), dim3(256), LDS, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
-    return check_launch(LO == 16 ? "wgrad32_kernel<16>" : LO == 8 ? "wgrad32_kernel<8>" : "wgrad32_kernel<4>");
+        ARVAE_LAUNCH((wgrad32x_kernel<4, 0>), dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
+    return check_launch("wgrad32_kernel<4>");
 }
 
 // per-workgroup partial sums into `slab`; the returned job describes the reduction that finishes the layer
@@ -1516,9 +1501,7 @@ int conv32_wgrad_partial(const arvae_link_t *l, const Operand &lo, const Operand
     ARVAE_REQUIRE(amax_lo != nullptr && amax_hi != nullptr, "conv32_wgrad: the operands' maxima are needed");
     const int grid = conv32_wgrad_groups(l);
     const int rc = conv32_wgrad_stream_fits(l) ? conv32_wgrad_stream(l, lo, hi, slab, bias_mode, amax_lo, amax_hi, s)
-                   : l->lh == 16             ? launch_wgrad_x<16>(l, lo, hi, slab, bias_mode, grid, amax_lo, amax_hi, s)
-                   : l->lh == 8              ? launch_wgrad_x<8>(l, lo, hi, slab, bias_mode, grid, amax_lo, amax_hi, s)
-                                             : launch_wgrad_x<4>(l, lo, hi, slab, bias_mode, grid, amax_lo, amax_hi, s);
+                                               : launch_wgrad_x4(l, lo, hi, slab, bias_mode, grid, amax_lo, amax_hi, s);
     *job = SlabJob{slab, dwt, bias_mode ? dbias : nullptr, grid, SLAB_C32, bias_mode};
     return rc;
 }
@@ -1527,30 +1510,19 @@ int conv32_wgrad_partial(const arvae_link_t *l, const Operand &lo, const Operand
 // up == true: the layer is a forward UP link (data gradient = DOWN map on g, weight gradient with g on the hi side, bias mode 2);
 // up == false: a forward DOWN link (data gradient = UP map, g on the lo side, bias mode 1).  Only the combinations the image
 // executor produces are instantiated; everything else (and the experiment switches) goes the two-launch way.
-// ... when the Up half of the 16x16 pair stores nothing (C1Wgrad: the first layer's weight gradient in its store waves)
-static int pair_split_c1_percent() {
-    static const int forced = diag_env("ARVAE_PAIR_SPLIT_C1") != nullptr ? atoi(diag_env("ARVAE_PAIR_SPLIT_C1")) : 0;
-    return (forced > 0 && forced < 100) ? forced : 62;        // (same-box sweep at B = 512: 38 / 44 / 50 / 56 / 62 / 68 % -> 55.1 / 50.8 / 43.6 / 43.8 / 39.1 / 43.3 us)
-}
-static int pair_split_percent(int lh, bool up) {              // share of the workgroups that runs the data gradient
-    // ARVAE_PAIR_SPLIT16 / _SPLIT8: both pairs of that size; ..._SPLIT16U / 16D / 8U / 8D: the pair whose data gradient is the Up
-    // (forward Down layer) / Down map
-    auto env = [](const char *name) { const char *v = diag_env(name); return v != nullptr ? atoi(v) : 0; };
-    static const int e16 = env("ARVAE_PAIR_SPLIT16"), e8 = env("ARVAE_PAIR_SPLIT8");
-    static const int e16u = env("ARVAE_PAIR_SPLIT16U"), e16d = env("ARVAE_PAIR_SPLIT16D"), e8u = env("ARVAE_PAIR_SPLIT8U"), e8d = env("ARVAE_PAIR_SPLIT8D");
-    const int one = lh == 16 ? (up ? e16d : e16u) : (up ? e8d : e8u), both = lh == 16 ? e16 : e8;
-    const int forced = one > 0 ? one : both;
-    if (forced > 0 && forced < 100) return forced;
-    // 50 % everywhere: both halves then give workgroup w the SAME images (equal ranges of whole images at the benchmark batches)
-    // and workgroup w of either half sits on XCD w % 8 (grid_a a multiple of 8): the tensor both halves read (the gradient g) is
-    // fetched from HBM once and the later reader hits that XCD's L2.  Round 6, pair(down32<16> + wgrad32<16>) at B = 512, same
-    // box: 48 % (121 + 133 workgroups, 17 tiles against 31 steps: the ranges and the XCDs drift apart) 177.7 MB and 39.1 us per
-    // launch, 50 % (128 + 128, 16 tiles and 32 steps = the same four images) 112.7 MB and 36.9 us: one read of g (67 MB) gone
-    // (tools/run_l2_align_ab.sh, profiles/r6_l2_align_ab.txt; the counters are calibrated in profiles/r6_fetch_calib.txt)
-    return 50;
-}
+// Share of the workgroups that runs the data gradient.  When the Up half of the 16x16 pair stores nothing (C1Wgrad: the
+// first layer's weight gradient in its store waves): 62 % (same-box sweep at B = 512: 38 / 44 / 50 / 56 / 62 / 68 % ->
+// 55.1 / 50.8 / 43.6 / 43.8 / 39.1 / 43.3 us).
+constexpr int PAIR_SPLIT_C1_PERCENT = 62;
+// Every other pair: 50 %: both halves then give workgroup w the SAME images (equal ranges of whole images at the benchmark batches)
+// and workgroup w of either half sits on XCD w % 8 (grid_a a multiple of 8): the tensor both halves read (the gradient g) is
+// fetched from HBM once and the later reader hits that XCD's L2.  Round 6, pair(down32<16> + wgrad32<16>) at B = 512, same
+// box: 48 % (121 + 133 workgroups, 17 tiles against 31 steps: the ranges and the XCDs drift apart) 177.7 MB and 39.1 us per
+// launch, 50 % (128 + 128, 16 tiles and 32 steps = the same four images) 112.7 MB and 36.9 us: one read of g (67 MB) gone
+// (profiles/r6_l2_align_ab.txt; the counters are calibrated in profiles/r6_fetch_calib.txt)
+constexpr int PAIR_SPLIT_PERCENT = 50;
 bool conv32_pair_fits(const arvae_link_t *l, bool up, const float *gate, const uint16_t *gate_bits, int bias_mode) {
-    static const bool off4 = diag_env("ARVAE_NO_PAIR4") != nullptr || diag_env("ARVAE_NO_SMALL_TILES") != nullptr;
+    static const bool off4 = diag_env("ARVAE_NO_PAIR4") != nullptr;
     static const bool off = diag_env("ARVAE_NO_PAIR32") != nullptr;
     if ((gate == nullptr && gate_bits == nullptr) || bias_mode != (up ? 2 : 1)) return false;
     if (l->lh == 4) {
@@ -1561,8 +1533,7 @@ bool conv32_pair_fits(const arvae_link_t *l, bool up, const float *gate, const u
     // 32-pixel-tile kernel (what launch_up_v picks at this batch)
     if (off || gate_bits == nullptr || !conv32_wgrad_stream_fits(l)) return false;
     if (l->n * (l->lh * l->lh / 32) < 4 * cu_count()) return false;
-    if (!up && l->lh == 8 && !(diag_env("ARVAE_NO_SMALL_TILES") == nullptr && tiles_for<8, 128>(l->n) <= cu_count())) return false;
-    if (!up && l->lh == 16 && diag_env("ARVAE_UP32_NO_PC") != nullptr) return false;
+    if (!up && l->lh == 8 && tiles_for<8, 128>(l->n) > cu_count()) return false;
     return true;
 }
 
@@ -1570,7 +1541,7 @@ template <int LO> static int launch_pair_big(const arvae_link_t *l, bool up, con
                                              const unsigned *amax_g, const unsigned *amax_x, hipStream_t s, int *grid_b_out,
                                              const C1Wgrad *c1 = nullptr, int *grid_a_out = nullptr) {
     const int cus = cu_count() < AMAX_N / 4 ? cu_count() : AMAX_N / 4;
-    int grid_a = cus * (c1 != nullptr ? pair_split_c1_percent() : pair_split_percent(LO, up)) / 100;
+    int grid_a = cus * (c1 != nullptr ? PAIR_SPLIT_C1_PERCENT : PAIR_SPLIT_PERCENT) / 100;
     if (grid_a < 1) grid_a = 1;
     // every body walks a contiguous run of ceil(tiles / grid_a) tiles: the workgroups past the last non-empty run would find nothing
     // to do, so the weight gradient gets them instead (round 6; the first-layer pair at B = 512: 158 workgroups asked for, 1024 tiles
@@ -1627,8 +1598,7 @@ template <int LO> static int launch_pair_big(const arvae_link_t *l, bool up, con
 // c1_img / c1_slab / c1_job (all or none; the 16x16 layer behind a single-channel first layer, sign-bit gates): the first
 // layer's weight gradient comes out of this launch too (up32p_body, C1Wgrad) and the data gradient is NOT stored (d_in unused)
 bool conv32_pair_c1_fits(const arvae_link_t *l, bool up, const uint16_t *gate_bits) {
-    static const bool off = diag_env("ARVAE_NO_PAIR_C1W") != nullptr;
-    return !off && !up && l->lh == 16 && gate_bits != nullptr && diag_env("ARVAE_UP32_NO_PC") == nullptr;
+    return !up && l->lh == 16 && gate_bits != nullptr;
 }
 int conv32_pair(const arvae_link_t *l, bool up, const float *g, const float *x_in, const float *gate, const uint16_t *gate_bits,
                 float *d_in, const float *wprep, float *dwt, float *dbias, float *slab, hipStream_t s, SlabJob *job,

@@ -17,13 +17,7 @@ constexpr int PSB2 = 36;                // LDS pixel stride in dwords of the pac
                                         // 36 rc and 72 rc mod 64 are eight disjoint groups of four banks)
 constexpr int PSB = 20;                 // LDS pixel stride in dwords of one 16-bit plane (16 payload + 4 pad: conflict-free
                                         // 16-byte reads for pixel walks of stride 1 and 2)
-#ifndef ARVAE_WGRAD_PSB_H
-#define ARVAE_WGRAD_PSB_H 24
-#endif
-#ifndef ARVAE_WGRAD_PSB_L
-#define ARVAE_WGRAD_PSB_L 16
-#endif
-constexpr int WGRAD_PSB_H = ARVAE_WGRAD_PSB_H, WGRAD_PSB_L = ARVAE_WGRAD_PSB_L;   // plane pitches of wgrad32x_kernel (see there)
+constexpr int WGRAD_PSB_H = 24, WGRAD_PSB_L = 16;   // plane pitches of wgrad32x_kernel (see there)
 constexpr int PIXB = C32 * 4;           // bytes of one 32-channel pixel
 constexpr unsigned OOB = 0x7fffffffu;   // byte offset beyond any tensor here: loads return 0, stores are dropped
 

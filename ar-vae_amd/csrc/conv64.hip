@@ -563,10 +563,9 @@ static bool plain_op(const Operand &o) { return o.y == nullptr || (o.act == ARVA
 
 // links this file serves: k x k (<= 16 taps), stride 1, 32 | channels on the reduction side, channels-last, no permutation
 bool conv64_fits(const arvae_link_t *l, bool up) {
-    static const bool off = diag_env("ARVAE_CONV64_GENERIC") != nullptr;
     const int red = up ? l->clo : l->chi, outc = up ? l->chi : l->clo;
     // narrow outputs (the 64 -> 8 layers) waste MFMA columns but these products are bound by the gather, not the MFMA
-    return !off && l->stride == 1 && l->kh * l->kw <= 16 && l->kh * l->kw > 1 && red % 4 == 0 && red >= 8 &&
+    return l->stride == 1 && l->kh * l->kw <= 16 && l->kh * l->kw > 1 && red % 4 == 0 && red >= 8 &&
            (l->kh * l->kw * red) % RG_R == 0 && outc >= 4 && red <= 128 && outc <= 128 && l->hi_perm_c == 0 && l->lo_perm_c == 0;
 }
 
@@ -574,8 +573,7 @@ static int launch_conv_rows(ConvRows g, const float *wt, bool transposed, float 
                             unsigned *amax_out = nullptr, const unsigned *amax_in = nullptr) {
     const int taps = g.kh * g.kw, wcount = g.q * taps * g.cs;
     g.amax_out = amax_out;
-    static const bool no_h2 = diag_env("ARVAE_CONV_ROWS_X3") != nullptr;        // A/B: the three-term bf16 kernel
-    const bool h2 = !no_h2 && amax_in != nullptr && plain_op(g.src);            // (one float behind the packed weights holds max |wt|)
+    const bool h2 = amax_in != nullptr && plain_op(g.src);            // (one float behind the packed weights holds max |wt|)
     g.amax_in = amax_in;
     g.w_amax = reinterpret_cast<const unsigned *>(packed + wcount);
     if (packed == nullptr || (reinterpret_cast<uintptr_t>(packed) & 15) != 0)
@@ -585,9 +583,8 @@ static int launch_conv_rows(ConvRows g, const float *wt, bool transposed, float 
     g.wt = packed;
     const int M = g.n * g.oh * g.ow;
     const dim3 grid((M + C64_TP - 1) / C64_TP, (g.q + C64_TQ - 1) / C64_TQ);
-    static const bool no_s8 = diag_env("ARVAE_CONV_S8_GATHER") != nullptr;      // A/B: the gathering kernel for 8-channel sources too
     const int span_rows = 63 / g.ow + 2 + 3;                                    // source rows a 64-pixel tile can touch
-    if (h2 && !no_s8 && g.cs == 8 && g.kh == 4 && g.kw == 4 && g.q <= 64 && (g.q & 3) == 0 && span_rows * g.sw <= S8_PIX &&
+    if (h2 && g.cs == 8 && g.kh == 4 && g.kw == 4 && g.q <= 64 && (g.q & 3) == 0 && span_rows * g.sw <= S8_PIX &&
         (reinterpret_cast<uintptr_t>(g.out) & 15) == 0 && (int64_t)M * g.q * 4 < 0x7fff0000ll) {       // (32-bit byte offsets into the output)
         ConvRows p = g;
         p.src.y = nullptr;
@@ -600,7 +597,6 @@ static int launch_conv_rows(ConvRows g, const float *wt, bool transposed, float 
                 (void)hipGetLastError();
                 n = 2;
             }
-            if (const char *e = diag_env("ARVAE_S8_PER_CU")) n = atoi(e) > 0 ? atoi(e) : n;
             return n;
         }();
         const int slots = per_cu * device_cu_count();
@@ -1181,13 +1177,11 @@ static int wr_img_per_wg(const arvae_link_t *l) {
 }
 
 static bool conv64_wgrad_rows_fits(const arvae_link_t *l) {
-    static const bool off = diag_env("ARVAE_CONV64_WGRAD_TAPS") != nullptr;      // A/B: the per-tap kernel
-    return !off && l->kh <= 4 && l->kw == 4 && l->lw <= 32 && l->lw + l->kw - 1 <= WR_HROWS && l->pad <= 4;
+    return l->kh <= 4 && l->kw == 4 && l->lw <= 32 && l->lw + l->kw - 1 <= WR_HROWS && l->pad <= 4;
 }
 
 bool conv64_wgrad_fits(const arvae_link_t *l) {
-    static const bool off = diag_env("ARVAE_CONV64_GENERIC") != nullptr;
-    return !off && l->stride == 1 && l->kh * l->kw <= 16 && l->kh * l->kw > 1 && l->clo % 4 == 0 && l->chi % 4 == 0 &&
+    return l->stride == 1 && l->kh * l->kw <= 16 && l->kh * l->kw > 1 && l->clo % 4 == 0 && l->chi % 4 == 0 &&
            l->clo >= 4 && l->chi >= 4 && l->clo <= 64 && l->chi <= 64 && (l->clo >= 32 || l->chi >= 32) &&
            l->hi_perm_c == 0 && l->lo_perm_c == 0 &&
            // (the paired-rows kernel addresses plain operands with 32-bit byte offsets)
@@ -1216,8 +1210,7 @@ int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
     const bool pl = plain_op(lo), ph = plain_op(hi);
     if (pl) g.lo.y = nullptr;
     if (ph) g.hi.y = nullptr;
-    static const bool no_pairs = diag_env("ARVAE_CONV64_WGRAD_ROWS") != nullptr;     // diagnostic: one lo row per step
-    if (conv64_wgrad_rows_fits(l) && !no_pairs && l->lw <= 24 && l->kh == 4) {
+    if (conv64_wgrad_rows_fits(l) && l->lw <= 24 && l->kh == 4) {
         const int ipw = (wr_img_per_wg(l) + 1) / 2, slices = (l->n + ipw - 1) / ipw;      // two workgroups per CU
         const dim3 grid((l->chi + 31) / 32, slices);
         const size_t lds = (2 * WP_APLANE + WP_RING * 2 * WP_HPLANE) * sizeof(unsigned short);
@@ -1231,8 +1224,7 @@ int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
         // maxima of the operands AS MULTIPLIED: the caller's (plain tensors only) or taken here, behind the partial sums in ws
         unsigned *am = reinterpret_cast<unsigned *>(ws + conv64_wgrad_ws_floats(l) - 2 * AMAX_N);
         // the bias gradient (column sums of lo or of hi) rides in the kernel: both tensors pass through its registers anyway
-        static const bool bias_apart = diag_env("ARVAE_CONV64_BIAS_APART") != nullptr;     // A/B: the separate channel-sum launches
-        const bool ride = dbias != nullptr && (bias_side == 1 || bias_side == 2) && bias_done != nullptr && !bias_apart &&
+        const bool ride = dbias != nullptr && (bias_side == 1 || bias_side == 2) && bias_done != nullptr &&
                           (bias_side == 1 ? l->clo : l->chi) <= 64;
         if (ride) {
             g.bias_ws = reinterpret_cast<float *>(am) - (int64_t)slices * 64;

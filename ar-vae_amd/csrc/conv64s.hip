@@ -148,17 +148,11 @@ template <int MT, int NT, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv64s_kernel(ConvStage g) {
     CSTAMP(0);
     constexpr int S_WSTEP = NT * 2 * 64;
-#ifndef C64S_EP_STEPS
-#define C64S_EP_STEPS 3
-#endif
+    constexpr int W_AHEAD = NT == 1 ? 3 : 2;        // reduction steps between a weight operand's request and its MFMAs
     // the epilogue operands (keep-mask bytes / gate values: scattered requests from HBM) are requested in the LAST reduction steps,
     // behind the tile's last weight request (step 13): memory operations return in order, and a weight request queued behind
     // one of these waits out an HBM round trip instead of an L2 hit
-#ifndef C64S_W_AHEAD
-#define C64S_W_AHEAD (NT == 1 ? 3 : 2)
-#endif
-    constexpr int W_AHEAD = C64S_W_AHEAD;        // reduction steps between a weight operand's request and its MFMAs
-    constexpr int EP_STEPS = C64S_EP_STEPS, EP_FIRST = 16 - EP_STEPS, EP_PER = (MT * NT + EP_STEPS - 1) / EP_STEPS;
+    constexpr int EP_STEPS = 3, EP_FIRST = 16 - EP_STEPS, EP_PER = (MT * NT + EP_STEPS - 1) / EP_STEPS;
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];          // 2 x S_BUF
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5, rc = lane & 31;
@@ -335,11 +329,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             constexpr int mt = decltype(kc_)::value / NT, nt = decltype(kc_)::value % NT;
                 {
                     const int P = opix[mt];
-#ifdef C64S_ABL_NOEPLOAD
-                    const bool ok = false;
-#else
                     const bool ok = P >= 0 && oy0 + P / g.ow < g.oh && ch_ok[nt];
-#endif
                     const unsigned o = ok ? (unsigned)((((int64_t)img * g.oh + oy0) * g.ow + P) * g.q + nt * 32 + 8 * wave + 4 * half) : 0u;
                     gy[mt][nt] = buf_load4(rs_gy, o * 4u);
                     const unsigned m = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs_km, (int)o, 0, 0);
@@ -474,11 +464,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     // unconditional: under the lane test the stores sat behind a branch, and the next tile's first weight operands
                     // (requested before the exchange) were then waited for with vmcnt(0) -- every store of this epilogue included
                     amax_run = ok ? fmaxf(amax_run, amax4(v)) : amax_run;
-#ifdef C64S_ABL_NOSTORE
-                    buf_store4(v, rs_out, (ok && v.x == 1234.5f) ? (unsigned)o * 4u : OOB);
-#else
                     buf_store4(v, rs_out, ok ? (unsigned)o * 4u : OOB);
-#endif
                 }
             }
             __syncthreads();
@@ -515,11 +501,10 @@ int64_t conv64s_ws_floats() { return (S_PREP_UINT4 + 1) * 4 + AMAX_N; }      // 
 // 64 source channels, 64 or 4..32 (a multiple of 4) output channels, 4x4 taps, stride 1, channels-last without permutation,
 // a row group that fits the staging buffers
 bool conv64s_fits(const arvae_link_t *l, bool up) {
-    static const bool off = diag_env("ARVAE_CONV64_NO_STAGE") != nullptr;      // diagnostic: the gathering kernel instead
     int rows, mt;
     const int ow = up ? l->hw : l->lw, sw = up ? l->lw : l->hw, cs = up ? l->clo : l->chi, q = up ? l->chi : l->clo;
     const int oh = up ? l->hh : l->lh;
-    return !off && l->stride == 1 && l->kh == 4 && l->kw == 4 && cs == 64 && (q == 64 || (q <= 32 && q >= 4 && (q & 3) == 0)) &&
+    return l->stride == 1 && l->kh == 4 && l->kw == 4 && cs == 64 && (q == 64 || (q <= 32 && q >= 4 && (q & 3) == 0)) &&
            l->hi_perm_c == 0 && l->lo_perm_c == 0 && stage_geometry(ow, sw, rows, mt) &&
            (int64_t)l->n * oh * ow * q * 4 < ((int64_t)1 << 31) - 65536 &&    // the result and the source are addressed through
            (int64_t)l->n * (up ? l->lh : l->hh) * sw * 64 * 4 < ((int64_t)1 << 31) - (1 << 20);   // buffer resources (32-bit byte offsets)

@@ -457,9 +457,8 @@ int conv_c1_down_with_prep(const arvae_link_t *l, const Operand &img, const floa
 int conv_c1_down(const arvae_link_t *l, const Operand &img, const float *wt, const float *bias, int relu,
                  const float *gate, const uint16_t *gate_bits, uint16_t *bits_out, float *out, hipStream_t s, unsigned *amax_out) {
     Ep1 ep{bias, gate, gate_bits, bits_out, out, relu, amax_out};
-    static const int waves_per_cu = diag_env("ARVAE_C1_DOWN_WAVES") ? atoi(diag_env("ARVAE_C1_DOWN_WAVES")) : 16;
     const int n_rows = l->n * LO1;
-    int grid = 256 * waves_per_cu / 4;                           // workgroups of four independent waves
+    int grid = 256 * 16 / 4;                                     // 16 waves per CU, in workgroups of four independent waves
     if (grid > (n_rows + 3) / 4) grid = (n_rows + 3) / 4;
     if (amax_out != nullptr && grid > AMAX_N) grid = AMAX_N;     // one AMAX writer unit per workgroup
     if (gate_bits != nullptr) ARVAE_LAUNCH(down_c1s_kernel<1>, dim3(grid), dim3(256), 0, s, img, wt, ep, n_rows);
@@ -476,8 +475,6 @@ static int up_c1_grid(int tiles) {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
         cached = cus > 0 ? cus : 256;
     }
-    static const int cap = diag_env("ARVAE_C1_UP_GRID") ? atoi(diag_env("ARVAE_C1_UP_GRID")) : 0;
-    if (cap > 0) return tiles < cap ? tiles : cap;
     return tiles < 2 * cached ? tiles : 2 * cached;
 }
 
@@ -521,7 +518,7 @@ int conv_c1_up_recon(const arvae_link_t *l, const float *lo, const float *wt, co
 }
 
 int wgrad_c1_groups(const arvae_link_t *l) {
-    static const int cap = diag_env("ARVAE_C1_WGRAD_GRID") ? atoi(diag_env("ARVAE_C1_WGRAD_GRID")) : 256;       // streaming form: one 8-wave workgroup per CU (256 / 512 / 1024 measured: 19.3 / 19.0 / 21.8 us, and the slab reduce grows with it)
+    constexpr int cap = 256;       // streaming form: one 8-wave workgroup per CU (256 / 512 / 1024 measured: 19.3 / 19.0 / 21.8 us, and the slab reduce grows with it)
     const int units = (l->n * LO1 + WGS_WAVES - 1) / WGS_WAVES;
     return units < cap ? units : cap;
 }
@@ -575,8 +572,7 @@ int conv_c1_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &img, 
 
 // ---- the stride-1 64-channel single-channel links (Morpho-MNIST) ----------------------------------------------------
 bool conv_c1w_fits(const arvae_link_t *l) {
-    static const bool off = diag_env("ARVAE_C1W_GENERIC") != nullptr;            // diagnostic: the generic gather-GEMM instead
-    return !off && l->chi == 1 && l->clo == W1_CH && l->kh == 4 && l->kw == 4 && l->stride == 1 && l->pad == 0 && l->lw <= W1_SLOTS &&
+    return l->chi == 1 && l->clo == W1_CH && l->kh == 4 && l->kw == 4 && l->stride == 1 && l->pad == 0 && l->lw <= W1_SLOTS &&
            l->hw == l->lw + 3 && l->hh == l->lh + 3 && l->hw < W1_IMS && 4 * l->hw <= 128 && l->hi_perm_c == 0 && l->lo_perm_c == 0;
 }
 static int wgrad_c1w_groups(const arvae_link_t *l) {

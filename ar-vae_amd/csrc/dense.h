@@ -48,7 +48,8 @@ struct WideGemm {
     int act;                    // finished: activation (ARVAE_ACT_*)
     const float *gate;          // finished: optional ReLU gate: out = gate[m][n] > 0 ? value : 0
     unsigned *amax_out;         // finished: AMAX array of the result (conv32_common.h), may be null
-    int dbg;                    // tools/probes/wide_gemm.py only (0 in the product): 1 no MFMAs, 2 no LDS commits, 4 no result stores
+    int dbg;                    // always 0: ablation bits of a retired timing probe (1 no MFMAs, 2 no LDS commits, 4 no result
+                                // stores), left in so that the kernels' code stays the code that was measured
 };
 // dW'[p][q] (+)= sum_m A(p, m) B(q, m), operands [batch][features] ("K x rows"), exactly one of them as bf16 planes; rows / columns
 // of dW' land at p_perm / q_perm.to_feat(.) of the [rows][ldw] gradient; dbias (may be null) += row sums of A

@@ -50,10 +50,9 @@ __device__ __forceinline__ void reduce_waves(float *red, const f32x16 &acc, int 
 // and over 4 when it is short and the tiles are many (K <= 512 with >= 512 tiles: the 16-way LDS reduction of 16 accumulator
 // registers per wave then costs more than the 8 MFMAs each wave contributes -- Morpho-MNIST's 256 <-> 2888 layers)
 static bool dense_short_k(int k, int tiles) {
-    static const bool off = diag_env("ARVAE_DENSE_NW16") != nullptr;
     // (and whenever the reduction is at most 160 long: 16 waves would contribute one or two MFMAs each to a tile and then spend
     // longer reducing it -- the tick RNN's vocab + 1 + 4B rows x 138 inputs: 24 us on sixteen waves)
-    return !off && k <= 512 && (tiles >= 512 || k <= 160);
+    return k <= 512 && (tiles >= 512 || k <= 160);
 }
 
 // ---- forward: Y[m][out_perm(n)] = act( sum_k X[m][km] * W[n][feat(km)] + b[n] ),  km = memory column ----------
@@ -266,14 +265,12 @@ __global__ __launch_bounds__(64 * NW) void dense_dgrad_kernel(DenseArgs p) {
 
 // ---- long-batch variants (M >= DENSE_SPLIT_MIN_ROWS rows: the MeasureVAE's whole-sequence GEMMs, 24 ticks x batch) --
 // Thousands of rows make these throughput problems: C[P][Q] = sum_r A(p,r) B(q,r) with both operand tiles staged
-// through LDS in reduction-major order [r][p] by coalesced 16-byte global loads (next chunk prefetched into registers
-// while the current one is multiplied), 64 x 64 outputs per workgroup = 2 x 2 waves on the 32x32x2 MFMA (small tiles: these
-// are 0.3-1.2 GFLOP problems, and two or three workgroups per CU hide each other's load latency).  An operand is either
+// through LDS by coalesced 16-byte global loads (next chunk prefetched into registers while the current one is multiplied),
+// 64 x 64 outputs per workgroup = 2 x 2 waves of 32 x 32 MFMA tiles (small tiles: these are 0.3-1.2 GFLOP problems, and two or three workgroups per CU hide each other's load latency).  An operand is either
 // "rows x K" (reduction index contiguous in memory: X, W and G of the forward / data-gradient products) or "K x rows"
 // (output index contiguous: W of the data gradient, G and X of the weight gradient); the weight gradient additionally
 // splits the row axis over blockIdx.z into workspace slices that dense_split_reduce_kernel adds up in slice order.
 constexpr int RG_TP = 64, RG_TQ = 64;
-constexpr int RG_PA = RG_TP + 4, RG_PB = RG_TQ + 4;
 enum { RG_EP_FWD = 0, RG_EP_SLICE = 1 };
 
 struct RowsGemm {
@@ -330,21 +327,6 @@ struct TileLoader {
             }
         }
     }
-    // LDS image [RG_R][pitch], reduction-major
-    __device__ __forceinline__ void commit(float *lds, int pitch) const {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = threadIdx.x + 256 * i;
-            if (LAY == RG_ROWSK) {
-                const int p = idx / (RG_R / 4), r = 4 * (idx % (RG_R / 4));
-                lds[(r + 0) * pitch + p] = v[i].x; lds[(r + 1) * pitch + p] = v[i].y;
-                lds[(r + 2) * pitch + p] = v[i].z; lds[(r + 3) * pitch + p] = v[i].w;
-            } else {
-                const int r = idx / (TP / 4), p = 4 * (idx % (TP / 4));
-                *reinterpret_cast<float4 *>(lds + r * pitch + p) = v[i];
-            }
-        }
-    }
     // three bf16 planes for the split-bf16 MFMA (x3tile.h)
     typedef X3Plane<LAY, TP> Plane;
     static constexpr int PLANE = Plane::PLANE;
@@ -358,60 +340,9 @@ struct TileLoader {
     }
 };
 
-template <int LA, int LB, int EP, bool VA, bool VB>
-__global__ __launch_bounds__(256) void rows_gemm_kernel(RowsGemm g) {
-    __shared__ float As[RG_R * RG_PA];
-    __shared__ float Bs[RG_R * RG_PB];
-    const int lane = threadIdx.x & 63, half = lane >> 5, rc = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int p0 = blockIdx.x * RG_TP, q0 = blockIdx.y * RG_TQ;
-    const int rbeg = blockIdx.z * g.rslice, rend = min(g.Rn, rbeg + g.rslice);
-    TileLoader<LA, RG_TP, VA> la;
-    TileLoader<LB, RG_TQ, VB> lb;
-    const int wp = wave & 1, wq = wave >> 1;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float bsum = 0.f;
-    la.load(g.a, g.lda, p0, g.P, rbeg, rend);
-    lb.load(g.b, g.ldb, q0, g.Q, rbeg, rend);
-    for (int r0 = rbeg; r0 < rend; r0 += RG_R) {
-        __syncthreads();
-        la.commit(As, RG_PA);
-        lb.commit(Bs, RG_PB);
-        __syncthreads();
-        if (r0 + RG_R < rend) {
-            la.load(g.a, g.lda, p0, g.P, r0 + RG_R, rend);
-            lb.load(g.b, g.ldb, q0, g.Q, r0 + RG_R, rend);
-        }
-#pragma unroll
-        for (int s = 0; s < RG_R / 2; ++s) {
-            const float a = As[(2 * s + half) * RG_PA + 32 * wp + rc];
-            const float b = Bs[(2 * s + half) * RG_PB + 32 * wq + rc];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-        if (EP == RG_EP_SLICE && g.want_bias && blockIdx.y == 0 && threadIdx.x < RG_TP) {
-#pragma unroll 8
-            for (int r = 0; r < RG_R; ++r) bsum += As[r * RG_PA + threadIdx.x];
-        }
-    }
-    float *out = g.out + (EP == RG_EP_SLICE ? blockIdx.z * g.slice_floats : 0);
-    const int q = q0 + 32 * wq + rc;
-    const float bias = (EP == RG_EP_FWD && g.bias != nullptr && q < g.Q) ? g.bias[q] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int p = p0 + 32 * wp + (r & 3) + 8 * (r >> 2) + 4 * half;
-        float v = acc[r];
-        if (EP == RG_EP_FWD) v = act_fwd(v + bias, g.act);
-        if (p < g.P && q < g.Q) out[(int64_t)p * g.ldo + q] = v;
-    }
-    if (EP == RG_EP_SLICE && g.want_bias && blockIdx.y == 0 && threadIdx.x < RG_TP && p0 + (int)threadIdx.x < g.P)
-        out[(int64_t)g.P * g.ldo + p0 + threadIdx.x] = bsum;
-}
-
-// The same product on the bf16 MFMA at fp32 accuracy: operands split into three bf16 terms when they are committed to
+// The product on the bf16 MFMA at fp32 accuracy: operands split into three bf16 terms when they are committed to
 // LDS ([p][r] planes, r contiguous), six partial products per multiply-add on v_mfma_f32_32x32x16_bf16, smallest first
-// (2.7x fewer MFMA cycles than the fp32 32x32x2; ARVAE_ROWS_GEMM_FP32=1 selects the kernel above).
+// (2.7x fewer MFMA cycles than the fp32 32x32x2).
 #ifdef RG_STAMPS
 // diagnostic build only (tools/stamp_rg.py): phase timeline of the first 512 workgroups of a rows-GEMM launch, 100 MHz wall clock
 __device__ unsigned long long g_rg_stamps[512 * 32];
@@ -521,10 +452,7 @@ __global__ __launch_bounds__(256) void rows_gemm_x3_kernel(RowsGemm g) {
 //     activation or ReLU gate, the tensor's AMAX entry for the conv kernel that reads it next).
 enum { WG_EP_PARTIAL = 0, WG_EP_FULL = 1 };
 constexpr int WG_DEPTH = 3;
-#ifndef ARVAE_WG_SINGLE
-#define ARVAE_WG_SINGLE 1
-#endif
-constexpr int WG_NBUF = ARVAE_WG_SINGLE ? 1 : 2;     // LDS buffers of the 64-tile kernels (128-tile: always 2)
+constexpr int WG_NBUF = 1;     // LDS buffers of the 64-tile kernels (128-tile: always 2)
 // Operand sources (T = tile extent along the operand's output axis, 64 or 128).  WideF32: an fp32 matrix, split into the three bf16
 // terms on its way to LDS (TileLoader: ~11 vector instructions per value pair).  WidePlanes: the three bf16 planes already in
 // memory -- the weights (mid_prep writes them once per step) and the small activations that dozens of tiles re-read (the latent
@@ -559,7 +487,7 @@ struct WidePlanes {
     // whole chunks: the 32 x (rows) block of one chunk is contiguous, so a wave's load is whole cache lines whichever axis is the
     // reduction -- "rows x K" (reduce along K: chunk c = block c, 64 bytes per row, rows adjacent) or "K x rows" (reduce along the
     // rows: 32 consecutive rows of one K block are 2 KB).  (Row-major planes made every request half a line: 13 TB/s of L2 -> LDS,
-    // tools/probes/wide_gemm.py.)  `rows_` = the row count of the planes.
+    // DESIGN.md section 4, item 49.)  `rows_` = the row count of the planes.
     __device__ __forceinline__ void init(const void *b, int64_t rows_, int64_t pstride, int p0_, int pmax_) {
         rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(b), 0, 0x7fffffff, 0x00020000);
         ld2 = (int)rows_ * 64;                                   // bytes of one K block of all rows
@@ -893,38 +821,15 @@ int wide_wgrad(const WideWgradJob *jobs, int count, hipStream_t s) {
     return check_launch("wide_wgrad");
 }
 
-// tools/probes/wide_gemm.py (diagnostic build): one launch of the tile GEMM on caller buffers (contents are the caller's business: timing only)
-#ifdef ARVAE_DIAG
-extern "C" int arvae_debug_wide_gemm(int32_t a_planes, int32_t b_krows, int32_t partial, int32_t M, int32_t N, int32_t K, const void *a, const void *b,
-                                     float *out, int32_t slices, int32_t dbg, arvae_stream_t stream) {
-    const int kpad = (K + RG_R - 1) / RG_R * RG_R, npad = (N + 31) / 32 * 32;
-    WideGemm g{};
-    g.a = a; g.lda = a_planes ? M : K; g.a_pstride = (int64_t)M * kpad; g.a_planes = a_planes;
-    g.b = b; g.b_planes = 1; g.b_krows = b_krows;
-    g.ldb = b_krows ? kpad : npad; g.b_pstride = (int64_t)npad * kpad;      // (planes: ld = their row count; K x rows: the rows are the reduction)
-    g.M = M; g.N = N; g.K = K; g.out = out; g.ldo = N; g.slice_floats = (int64_t)M * N; g.act = ARVAE_ACT_NONE; g.dbg = dbg;
-    return wide_gemm(g, slices, partial != 0, as_stream(stream));
-}
-#endif
-
-// The tile extent a product runs with.  64 x 64, four or five 32 KB workgroups per CU.  The 128 x 128 form (half the operand
-// traffic per multiply-add, one 120 KB workgroup per CU) is kept in the diagnostic build for A/B runs: with every MFMA, LDS write
-// and result store switched off it moves its bytes in 9.3 us against 12.3 (tools/probes/wide_gemm.py), but one wave per SIMD then
-// runs loads, commits, MFMAs and stores one after the other: 31-34 us per product against 20-21.
-static int wide_tile(int M, int N) {
-#ifdef ARVAE_DIAG
-    static const bool big = diag_env("ARVAE_WIDE_TILE128") != nullptr;      // diagnostic build only: the 128 x 128 form
-    return (big && M > 64 && N > 64) ? 128 : 64;
-#else
-    (void)M; (void)N;
-    return 64;
-#endif
-}
-// K slices that fill the chip: tiles x slices ~ one (128) or two (64) workgroups per CU, a slice at least four chunks long
+// The tile extent of every product is 64 x 64: four or five 32 KB workgroups per CU.  (A 128 x 128 form -- half the operand
+// traffic per multiply-add, one 120 KB workgroup per CU -- moved its bytes in 9.3 us against 12.3 with every MFMA, LDS write and
+// result store switched off, but one wave per SIMD then runs loads, commits, MFMAs and stores one after the other: 31-34 us per
+// product against 20-21.)
+constexpr int WIDE_T = 64;
+// K slices that fill the chip: tiles x slices ~ two workgroups per CU, a slice at least four chunks long
 int wide_gemm_slices(int M, int N, int K) {
-    const int T = wide_tile(M, N);
-    const int tiles = ((M + T - 1) / T) * ((N + T - 1) / T), chunks = (K + RG_R - 1) / RG_R;
-    int s = ((T == 128 ? 1 : 2) * device_cu_count() + tiles - 1) / tiles;
+    const int tiles = ((M + WIDE_T - 1) / WIDE_T) * ((N + WIDE_T - 1) / WIDE_T), chunks = (K + RG_R - 1) / RG_R;
+    int s = (2 * device_cu_count() + tiles - 1) / tiles;
     if (s > chunks / 4) s = chunks / 4;
     if (s > WIDE_MAX_SLICES) s = WIDE_MAX_SLICES;
     return s < 1 ? 1 : s;
@@ -933,8 +838,7 @@ bool wide_gemm_fits(const WideGemm &g, int slices) {
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const int64_t a_bytes = g.a_planes ? 3 * g.a_pstride * 2 : (int64_t)g.M * g.lda * 4;
     const int64_t b_bytes = 3 * g.b_pstride * 2;
-    const int T = wide_tile(g.M, g.N);
-    const int tiles = ((g.M + T - 1) / T) * ((g.N + T - 1) / T);
+    const int tiles = ((g.M + WIDE_T - 1) / WIDE_T) * ((g.N + WIDE_T - 1) / WIDE_T);
     // fp32 A: 16-byte rows.  Plane operands (tiled layout, ld = their row count, K padded to whole chunks by their writer): "rows x K"
     // needs at least the output rows; "K x rows" reduces along the rows (padded with zero rows for weights) and emits 8 columns per load
     const bool a_ok = g.a_planes ? (g.lda >= g.M && (g.K % RG_R) == 0 && (g.a_pstride & 7) == 0) : ((g.lda & 3) == 0 && (g.K & 3) == 0);
@@ -943,33 +847,14 @@ bool wide_gemm_fits(const WideGemm &g, int slices) {
            a_bytes < ((int64_t)1 << 31) && b_bytes < ((int64_t)1 << 31) && slices >= 1 && slices <= WIDE_MAX_SLICES &&
            (g.amax_out == nullptr || tiles <= AMAX_N);
 }
-template <class SA, class SB, int EP, int NT>
+template <class SA, class SB, int EP>
 static void launch_wide(const WideGemm &g, dim3 grid, hipStream_t s) {
     static std::once_flag once;
     std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void *)wide_gemm_x3_kernel<SA, SB, EP, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideLds<SA, SB>::BYTES);
+        (void)hipFuncSetAttribute((const void *)wide_gemm_x3_kernel<SA, SB, EP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideLds<SA, SB>::BYTES);
     });
     constexpr size_t lds_bytes = WideLds<SA, SB>::BYTES;
-    ARVAE_LAUNCH((wide_gemm_x3_kernel<SA, SB, EP, NT>), grid, dim3(256), lds_bytes, s, g);
-}
-template <int NT>
-static void dispatch_wide(const WideGemm &g, bool partial, dim3 grid, hipStream_t s) {
-    constexpr int T = 64 * NT;
-    typedef WideF32<RG_ROWSK, T> AF;
-    typedef WidePlanes<RG_ROWSK, T> AP;
-    typedef WidePlanes<RG_ROWSK, T> BR;
-    typedef WidePlanes<RG_KROWS, T> BK;
-    const int sel = (g.a_planes ? 4 : 0) + (g.b_krows ? 2 : 0) + (partial ? 0 : 1);
-    switch (sel) {
-        case 0: launch_wide<AF, BR, WG_EP_PARTIAL, NT>(g, grid, s); break;
-        case 1: launch_wide<AF, BR, WG_EP_FULL, NT>(g, grid, s); break;
-        case 2: launch_wide<AF, BK, WG_EP_PARTIAL, NT>(g, grid, s); break;
-        case 3: launch_wide<AF, BK, WG_EP_FULL, NT>(g, grid, s); break;
-        case 4: launch_wide<AP, BR, WG_EP_PARTIAL, NT>(g, grid, s); break;
-        case 5: launch_wide<AP, BR, WG_EP_FULL, NT>(g, grid, s); break;
-        case 6: launch_wide<AP, BK, WG_EP_PARTIAL, NT>(g, grid, s); break;
-        default: launch_wide<AP, BK, WG_EP_FULL, NT>(g, grid, s); break;
-    }
+    ARVAE_LAUNCH((wide_gemm_x3_kernel<SA, SB, EP, 1>), grid, dim3(256), lds_bytes, s, g);
 }
 // slices > 1 (or partial): g.out = workspace of `slices` x slice_floats, the consumer sums them; else the finished product
 int wide_gemm(WideGemm g, int slices, bool partial, hipStream_t s) {
@@ -977,13 +862,21 @@ int wide_gemm(WideGemm g, int slices, bool partial, hipStream_t s) {
     ARVAE_REQUIRE(partial || slices == 1, "wide_gemm: a split reduction leaves partial sums");
     const int chunks = (g.K + RG_R - 1) / RG_R;
     g.kslice = ((chunks + slices - 1) / slices) * RG_R;
-    const int T = wide_tile(g.M, g.N);
-    const dim3 grid((g.M + T - 1) / T, (g.N + T - 1) / T, slices);
-#ifdef ARVAE_DIAG
-    if (T == 128) dispatch_wide<2>(g, partial, grid, s);
-    else
-#endif
-        dispatch_wide<1>(g, partial, grid, s);
+    const dim3 grid((g.M + WIDE_T - 1) / WIDE_T, (g.N + WIDE_T - 1) / WIDE_T, slices);
+    typedef WideF32<RG_ROWSK, WIDE_T> AF;
+    typedef WidePlanes<RG_ROWSK, WIDE_T> AP;
+    typedef WidePlanes<RG_ROWSK, WIDE_T> BR;
+    typedef WidePlanes<RG_KROWS, WIDE_T> BK;
+    switch ((g.a_planes ? 4 : 0) + (g.b_krows ? 2 : 0) + (partial ? 0 : 1)) {
+        case 0: launch_wide<AF, BR, WG_EP_PARTIAL>(g, grid, s); break;
+        case 1: launch_wide<AF, BR, WG_EP_FULL>(g, grid, s); break;
+        case 2: launch_wide<AF, BK, WG_EP_PARTIAL>(g, grid, s); break;
+        case 3: launch_wide<AF, BK, WG_EP_FULL>(g, grid, s); break;
+        case 4: launch_wide<AP, BR, WG_EP_PARTIAL>(g, grid, s); break;
+        case 5: launch_wide<AP, BR, WG_EP_FULL>(g, grid, s); break;
+        case 6: launch_wide<AP, BK, WG_EP_PARTIAL>(g, grid, s); break;
+        default: launch_wide<AP, BK, WG_EP_FULL>(g, grid, s); break;
+    }
     return check_launch(partial ? "wide_gemm(partial)" : "wide_gemm(full)");
 }
 
@@ -1213,7 +1106,7 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_wgrad_kernel(DenseArgs p)
     dense_wgrad_tile<NW>(p, blockIdx.x, blockIdx.y, red);
 }
 
-// Adds the row slices written by the long-batch weight gradient (rows_gemm_kernel, RG_EP_SLICE) to dW / db in slice order.
+// Adds the row slices written by the long-batch weight gradient (rows_gemm_x3_kernel, RG_EP_SLICE) to dW / db in slice order.
 __global__ __launch_bounds__(256) void dense_split_reduce_kernel(const float *__restrict__ ws, int64_t slice_floats, int slices,
                                                                   int64_t w_floats, int n_out, float *__restrict__ dw,
                                                                   float *__restrict__ dbias) {
@@ -1349,10 +1242,9 @@ __global__ __launch_bounds__(64 * NWB, 2) void dense_wgrad_slab_kernel(DenseWgra
     }
 }
 
-// both queues in one launch when both hold work; either alone otherwise (ARVAE_NO_PAIR_CLOSE in the diagnostic build: back to back)
+// both queues in one launch when both hold work; either alone otherwise
 int dense_wgrad_slab_flush(DenseWgradBatch *b, SlabReduceBatch *r, hipStream_t s) {
-    static const bool off = diag_env("ARVAE_NO_PAIR_CLOSE") != nullptr || diag_env("ARVAE_DENSE_BATCH_SPLIT") != nullptr;
-    if (off || b->count == 0 || r->count == 0) {
+    if (b->count == 0 || r->count == 0) {
         if (int rc = slab_reduce_flush(r, s)) return rc;
         return dense_wgrad_flush(b, s);
     }
@@ -1381,14 +1273,6 @@ static void launch_rows_gemm(const RowsGemm &g, int slices, hipStream_t s) {
     };
     const bool va = vec_ok(g.a, g.lda, LA, g.P), vb = vec_ok(g.b, g.ldb, LB, g.Q);
     const dim3 grid((g.P + RG_TP - 1) / RG_TP, (g.Q + RG_TQ - 1) / RG_TQ, slices);
-    static const bool fp32_mfma = diag_env("ARVAE_ROWS_GEMM_FP32") != nullptr;
-    if (fp32_mfma) {
-        if (va && vb) ARVAE_LAUNCH((rows_gemm_kernel<LA, LB, EP, true, true>), grid, dim3(256), 0, s, g);
-        else if (va) ARVAE_LAUNCH((rows_gemm_kernel<LA, LB, EP, true, false>), grid, dim3(256), 0, s, g);
-        else if (vb) ARVAE_LAUNCH((rows_gemm_kernel<LA, LB, EP, false, true>), grid, dim3(256), 0, s, g);
-        else ARVAE_LAUNCH((rows_gemm_kernel<LA, LB, EP, false, false>), grid, dim3(256), 0, s, g);
-        return;
-    }
     if (va && vb) ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, true, true>), grid, dim3(256), 0, s, g);
     else if (va) ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, true, false>), grid, dim3(256), 0, s, g);
     else if (vb) ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, false, true>), grid, dim3(256), 0, s, g);
@@ -1399,8 +1283,7 @@ static void launch_rows_gemm(const RowsGemm &g, int slices, hipStream_t s) {
 static bool plain_operand(const Operand &g) { return g.y == nullptr || (g.act == ARVAE_ACT_NONE && g.mask == nullptr); }
 
 static bool dense_long_batch(const DenseArgs &p) {
-    static const bool off = diag_env("ARVAE_DENSE_NO_ROWS") != nullptr;       // A/B switch
-    return !off && p.batch >= DENSE_SPLIT_MIN_ROWS && p.in_perm.c_count == 0 && p.out_perm.c_count == 0;
+    return p.batch >= DENSE_SPLIT_MIN_ROWS && p.in_perm.c_count == 0 && p.out_perm.c_count == 0;
 }
 
 static DenseArgs dense_args(const arvae_link_t *l) {
@@ -1500,10 +1383,9 @@ int64_t dense_wgrad_long_ws_floats(const arvae_link_t *l) {
     return (int64_t)((l->n + rs - 1) / rs) * (((int64_t)l->clo * l->chi + l->clo + 3) / 4 * 4);
 }
 bool dense_wgrad_long_defer(LongWgradQueue *q, const arvae_link_t *l, const Operand &g, const float *x, float *dw, float *dbias) {
-    static const bool off = diag_env("ARVAE_NO_LONG_BATCH") != nullptr;       // A/B switch
     DenseArgs p = dense_args(l);
     p.a = g;
-    if (off || q == nullptr || q->ws == nullptr || q->gemm.count >= RG_BATCH_MAX || !dense_long_batch(p) || !plain_operand(g)) return false;
+    if (q == nullptr || q->ws == nullptr || q->gemm.count >= RG_BATCH_MAX || !dense_long_batch(p) || !plain_operand(g)) return false;
     auto aligned = [](const float *ptr, int ld, int extent) { return (ld & 3) == 0 && (extent & 3) == 0 && (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
     if (!aligned(g.v, p.n_out, p.n_out) || !aligned(x, p.n_in, p.n_in)) return false;
     // (the tile loaders address a matrix with 32-bit byte offsets)
@@ -1568,18 +1450,6 @@ bool dense_wgrad_defer(DenseWgradBatch *b, const arvae_link_t *l, const Operand 
 
 int dense_wgrad_flush(DenseWgradBatch *b, hipStream_t s) {
     if (b->count == 0) return ARVAE_OK;
-    static const bool split = diag_env("ARVAE_DENSE_BATCH_SPLIT") != nullptr;     // diagnostic: one launch per job
-    if (split) {
-        for (int j = 0; j < b->count; ++j) {
-            DenseWgradBatch one{};
-            one.count = 1;
-            one.job[0] = b->job[j];
-            one.tile_end[0] = b->tile_end[j] - (j > 0 ? b->tile_end[j - 1] : 0);
-            ARVAE_LAUNCH(dense_wgrad_batch_kernel, dim3(one.tile_end[0]), dim3(64 * NWB), 0, s, one);
-        }
-        b->count = 0;
-        return check_launch("dense_wgrad_batch_kernel");
-    }
     ARVAE_LAUNCH(dense_wgrad_batch_kernel, dim3(b->tile_end[b->count - 1]), dim3(64 * NWB), 0, s, *b);
     b->count = 0;
     return check_launch("dense_wgrad_batch_kernel");
@@ -1588,7 +1458,7 @@ int dense_wgrad_flush(DenseWgradBatch *b, hipStream_t s) {
 // the queued Linear weight gradients and the single-channel layer's weight-gradient partials (conv_c1.hip) in one launch
 int wgrad_c1_groups(const arvae_link_t *l);
 bool dense_wgrad_c1_fits(const DenseWgradBatch *b) {
-    static const bool off = diag_env("ARVAE_NO_PAIR_TAIL") != nullptr || diag_env("ARVAE_DENSE_BATCH_SPLIT") != nullptr;
+    static const bool off = diag_env("ARVAE_NO_PAIR_TAIL") != nullptr;
     return !off && b != nullptr && b->count > 0;
 }
 int dense_wgrad_flush_with_c1(DenseWgradBatch *b, const arvae_link_t *l, const Operand &lo, const Operand &img, float *dwt, float *dbias,

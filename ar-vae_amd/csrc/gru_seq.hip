@@ -93,195 +93,15 @@ __device__ __forceinline__ void gru_st(float v, __amdgpu_buffer_rsrc_t r, int vo
 }
 __device__ __forceinline__ int gru_off(int row, int pitch_bytes, int base_bytes) { return (int)__umul24(row, pitch_bytes) + base_bytes; }
 
-template <int H>
-__global__ __launch_bounds__(H * 4) void gru_seq_fwd_kernel(GruSeqBatch batch, int T, int R) {
-    constexpr int KQ = H / 16;             // groups of 16 k values (4 MFMAs each)
-    constexpr int HS = H + 4;              // LDS row stride (floats)
-    __shared__ float hbuf[2][16][HS];
-    const GruSeq &s = batch.seq[blockIdx.y];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int col = lane & 15, quad = lane >> 4;
-    const int unit = 16 * w + col;
-    const int row0 = blockIdx.x * 16;
-
-    f32x4 wreg[3][KQ];
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int kq = 0; kq < KQ; ++kq)
-            wreg[g][kq] = *reinterpret_cast<const f32x4 *>(s.w_hh + (int64_t)(g * H + unit) * H + 16 * kq + 4 * quad);
-    const float bh_r = s.b_hh[unit], bh_z = s.b_hh[H + unit], bh_n = s.b_hh[2 * H + unit];
-
-    int rows[4];
-    bool live[4];
-    float h[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = row0 + 4 * quad + i;
-        live[i] = r < R;
-        rows[i] = live[i] ? r : R - 1;
-        h[i] = (s.h0 != nullptr && live[i]) ? s.h0[(int64_t)rows[i] * s.h0_stride + unit] : 0.f;
-        hbuf[0][4 * quad + i][unit] = h[i];
-    }
-    float gi_next[4][3];
-    {
-        const int t0 = s.reverse ? T - 1 : 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float *p = s.gi + t0 * s.gi_tstride + (int64_t)rows[i] * s.gi_rstride + unit;
-            gi_next[i][0] = p[0]; gi_next[i][1] = p[H]; gi_next[i][2] = p[2 * H];
-        }
-    }
-    lds_barrier();
-
-    for (int step = 0; step < T; ++step) {
-        const int t = s.reverse ? T - 1 - step : step;
-        const int cur = step & 1;
-        float gi[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int g = 0; g < 3; ++g) gi[i][g] = gi_next[i][g];
-        if (step + 1 < T) {
-            const int tn = s.reverse ? t - 1 : t + 1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float *p = s.gi + tn * s.gi_tstride + (int64_t)rows[i] * s.gi_rstride + unit;
-                gi_next[i][0] = p[0]; gi_next[i][1] = p[H]; gi_next[i][2] = p[2 * H];
-            }
-        }
-        f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int kq = 0; kq < KQ; ++kq) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(&hbuf[cur][col][16 * kq + 4 * quad]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int g = 0; g < 3; ++g)
-                    acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], wreg[g][kq][j], acc[g], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float r = fast_sigmoid(gi[i][0] + acc[0][i] + bh_r);
-            const float z = fast_sigmoid(gi[i][1] + acc[1][i] + bh_z);
-            const float ghn = acc[2][i] + bh_n;
-            const float n = fast_tanh(gi[i][2] + r * ghn);
-            const float hn = (1.f - z) * n + z * h[i];
-            h[i] = hn;
-            hbuf[cur ^ 1][4 * quad + i][unit] = hn;
-            if (live[i]) {
-                const int64_t tr = (int64_t)t * R + rows[i];
-                s.h_all[tr * s.h_stride + unit] = hn;
-                *reinterpret_cast<f32x4 *>(s.saved + (tr * H + unit) * 4) = f32x4{r, z, n, ghn};
-                if (step == T - 1 && s.h_fin != nullptr) s.h_fin[(int64_t)rows[i] * s.h_fin_stride + unit] = hn;
-            }
-        }
-        lds_barrier();
-    }
-}
-
+// ------------------------------------------------------------------------------------------------------------------
 // Backward through time.  Per step (in the reverse of the forward's processing order):
 //   g = dh_all[t] + carry;  dpn = g (1-z)(1-n^2);  dpz = g (h_prev - n) z (1-z);  dpr = dpn gh_n r (1-r)
 //   dgi = [dpr, dpz, dpn];  dgh = [dpr, dpz, dpn r];  carry = g z + dgh . W_hh
-template <int H>
-__global__ __launch_bounds__(H * 4) void gru_seq_bwd_kernel(GruSeqBatch batch, int T, int R) {
-    constexpr int KQ = 3 * H / 16;
-    constexpr int DS = 3 * H + 4;
-    __shared__ float dbuf[2][16][DS];
-    const GruSeq &s = batch.seq[blockIdx.y];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int col = lane & 15, quad = lane >> 4;
-    const int unit = 16 * w + col;
-    const int row0 = blockIdx.x * 16;
-
-    // B[k = c][n = unit] = W_hh[c][unit], c = 16 kq + 4 quad + j
-    f32x4 wreg[KQ];
-#pragma unroll
-    for (int kq = 0; kq < KQ; ++kq)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wreg[kq][j] = s.w_hh[(int64_t)(16 * kq + 4 * quad + j) * H + unit];
-
-    int rows[4];
-    bool live[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = row0 + 4 * quad + i;
-        live[i] = r < R;
-        rows[i] = live[i] ? r : R - 1;
-    }
-    float carry[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        carry[i] = (s.dh_last != nullptr && live[i]) ? s.dh_last[(int64_t)rows[i] * s.dh_last_stride + unit] : 0.f;
-
-    // operands of one step: dh, r, z, n, gh_n, h_prev
-    float nx[4][6];
-    auto fetch = [&](int step) {
-        const int t = s.reverse ? step : T - 1 - step;
-        const bool has_prev = step + 1 < T;
-        const int tp = s.reverse ? t + 1 : t - 1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t tr = (int64_t)t * R + rows[i];
-            nx[i][0] = s.dh_all != nullptr ? s.dh_all[tr * s.dh_stride + unit] : 0.f;
-            const f32x4 sv = *reinterpret_cast<const f32x4 *>(s.saved + (tr * H + unit) * 4);
-            nx[i][1] = sv[0]; nx[i][2] = sv[1]; nx[i][3] = sv[2]; nx[i][4] = sv[3];
-            if (has_prev) nx[i][5] = s.h_all[((int64_t)tp * R + rows[i]) * s.h_stride + unit];
-            else nx[i][5] = s.h0 != nullptr ? s.h0[(int64_t)rows[i] * s.h0_stride + unit] : 0.f;
-        }
-    };
-    fetch(0);
-
-    for (int step = 0; step < T; ++step) {
-        const int t = s.reverse ? step : T - 1 - step;
-        const int cur = step & 1;
-        float gz[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float g = live[i] ? nx[i][0] + carry[i] : 0.f;
-            const float r = nx[i][1], z = nx[i][2], n = nx[i][3], ghn = nx[i][4], hp = nx[i][5];
-            const float dpn = g * (1.f - z) * (1.f - n * n);
-            const float dpz = g * (hp - n) * z * (1.f - z);
-            const float dpr = dpn * ghn * r * (1.f - r);
-            const float dhn = dpn * r;
-            gz[i] = g * z;
-            float *d = &dbuf[cur][4 * quad + i][unit];
-            d[0] = dpr; d[H] = dpz; d[2 * H] = dhn;
-            if (live[i]) {
-                const int64_t o = ((int64_t)t * R + rows[i]) * 3 * H + unit;
-                const int64_t og = ((int64_t)t * R + rows[i]) * s.dgi_rstride + unit;
-                s.dgi[og] = dpr; s.dgi[og + H] = dpz; s.dgi[og + 2 * H] = dpn;
-                s.dgh[o] = dpr; s.dgh[o + H] = dpz; s.dgh[o + 2 * H] = dhn;
-                if (s.h_prev_out != nullptr) s.h_prev_out[((int64_t)t * R + rows[i]) * H + unit] = hp;
-            }
-        }
-        if (step + 1 < T) fetch(step + 1);
-        lds_barrier();
-        f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int kq = 0; kq < KQ; ++kq) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(&dbuf[cur][col][16 * kq + 4 * quad]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[kq % 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], wreg[kq][j], acc[kq % 3], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) carry[i] = gz[i] + (acc[0][i] + acc[1][i] + acc[2][i]);
-    }
-    if (s.dh0 != nullptr)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (live[i]) s.dh0[(int64_t)rows[i] * s.dh0_stride + unit] = carry[i];
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The same two kernels on the bf16 MFMA at fp32 accuracy (the three-term split of conv32.hip): W_hh is split once into
-// hi + mid + lo bf16 terms per lane (144 VGPRs at H = 128), h (or dgh) is split when it is written to LDS as three
-// bf16 planes, and a multiply-add is the six partial products >= 2^-18 on v_mfma_f32_16x16x32_bf16 (16 cycles each
-// instead of 8 x 32 for the fp32 16x16x4), smallest first: 72 instead of 96 MFMAs per wave and step at half the
-// cycles each.  Results are within one fp32 rounding of the fp32-MFMA kernels' (same tests, same tolerances).
+//
+// The backward recurrence on the bf16 MFMA at fp32 accuracy (the three-term split of conv32.hip; the diagnostic build's
+// ARVAE_GRU_BF16_BWD form): W_hh is split once into hi + mid + lo bf16 terms per lane (144 VGPRs at H = 128), dgh is split
+// when it is written to LDS as three bf16 planes, and a multiply-add is the six partial products >= 2^-18 on
+// v_mfma_f32_16x16x32_bf16 (16 cycles each instead of 8 x 32 for the fp32 16x16x4), smallest first.
 typedef __bf16 bf16x8g __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2g __attribute__((ext_vector_type(2)));
 typedef float f32x2g __attribute__((ext_vector_type(2)));
@@ -322,15 +142,7 @@ __device__ __forceinline__ void store_split3_pair(unsigned short *p, int rowpitc
 __device__ __forceinline__ bf16x8g lds_x8(const unsigned short *p) {
     return __builtin_bit_cast(bf16x8g, *reinterpret_cast<const i32x4g *>(p));
 }
-// acc += a . w with a = (ah, am, al), w = (wh, wm, wl): the six products, smallest first
-#define GRU_MFMA6(ACC, AH, AM, AL, WH, WM, WL)                                         \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AL, WH, ACC, 0, 0, 0);               \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, WL, ACC, 0, 0, 0);               \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AM, WM, ACC, 0, 0, 0);               \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AM, WH, ACC, 0, 0, 0);               \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, WM, ACC, 0, 0, 0);               \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, WH, ACC, 0, 0, 0)
-
+// acc += a . w with a = (ah, am, al), w = (wh, wm, wl), the six products smallest first, into
 // three independent accumulators, product-major: consecutive MFMAs never hit the same accumulator (a dependent 16x16x32 MFMA
 // waits for its predecessor's result, about twice the issue interval), every accumulator still sees its six products in order
 #define GRU_MFMA6X3(A0, A1, A2, H0, M0, L0, H1, M1, L1, H2, M2, L2, WH0, WM0, WL0, WH1, WM1, WL1, WH2, WM2, WL2)                 \
@@ -351,149 +163,6 @@ __device__ __forceinline__ bf16x8g lds_x8(const unsigned short *p) {
 __device__ unsigned long long g_gru_stamps[8];
 __device__ unsigned long long g_tick_stamps[9];
 #endif
-template <int H>
-__global__ __launch_bounds__(H * 4) void gru_seq_fwd_x3_kernel(GruSeqBatch batch, int T, int R) {
-    constexpr int KS = H / 32;             // MFMA k-steps of 32
-    constexpr int HP = H + 8;              // LDS row pitch in bf16 elements (16 bytes of padding)
-    constexpr int PLANE = 16 * HP;
-    __shared__ __attribute__((aligned(16))) unsigned short hbuf[2][3 * PLANE];
-    const GruSeq &s = batch.seq[blockIdx.y];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int col = lane & 15, quad = lane >> 4;
-    const int unit = 16 * w + col;
-    const int row0 = blockIdx.x * 16;
-
-    bf16x8g wh[3][KS], wm[3][KS], wl[3][KS];
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const float *src = s.w_hh + (int64_t)(g * H + unit) * H + 32 * ks + 8 * quad;
-            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + 4);
-            const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            split3_x8(x, wh[g][ks], wm[g][ks], wl[g][ks]);
-        }
-    const float bh_r = s.b_hh[unit], bh_z = s.b_hh[H + unit], bh_n = s.b_hh[2 * H + unit];
-
-    int rows[4];
-    bool live[4];
-    float h[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = row0 + 4 * quad + i;
-        live[i] = r < R;
-        rows[i] = live[i] ? r : R - 1;
-        h[i] = (s.h0 != nullptr && live[i]) ? s.h0[(int64_t)rows[i] * s.h0_stride + unit] : 0.f;
-        store_split3(&hbuf[0][(4 * quad + i) * HP + unit], PLANE, h[i]);
-    }
-    // running per-row pointers, advanced by a signed stride every step (the address arithmetic of 12 loads and 8 stores
-    // per step was a quarter of the step: the kernel is vector-ALU bound around its MFMAs)
-    const int t0 = s.reverse ? T - 1 : 0;
-    const int64_t dir = s.reverse ? -1 : 1;
-    const int64_t gi_step = dir * s.gi_tstride, h_step = dir * (int64_t)R * s.h_stride, sv_step = dir * (int64_t)R * H * 4;
-    const float *gi_p[4];
-    float *h_p[4], *sv_p[4];
-    float gi_next[4][3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        gi_p[i] = s.gi + t0 * s.gi_tstride + (int64_t)rows[i] * s.gi_rstride + unit;
-        h_p[i] = s.h_all + ((int64_t)t0 * R + rows[i]) * s.h_stride + unit;
-        sv_p[i] = s.saved + (((int64_t)t0 * R + rows[i]) * H + unit) * 4;
-        gi_next[i][0] = gi_p[i][0]; gi_next[i][1] = gi_p[i][H]; gi_next[i][2] = gi_p[i][2 * H];
-        gi_p[i] += gi_step;
-    }
-    lds_barrier();
-    f32x4 keep_sv[4];                        // results of the previous step, stored after the barrier
-    float keep_h[4];
-    int keep_t = -1;
-#ifdef ARVAE_GRU_STAMPS
-    unsigned long long ph[4] = {0, 0, 0, 0}, tc = __builtin_readcyclecounter();
-#define GSTAMP(k) { const unsigned long long now = __builtin_readcyclecounter(); ph[k] += now - tc; tc = now; }
-#else
-#define GSTAMP(k)
-#endif
-
-    for (int step = 0; step < T; ++step) {
-        const int t = s.reverse ? T - 1 - step : step;
-        const int cur = step & 1;
-        float gi[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int g = 0; g < 3; ++g) gi[i][g] = gi_next[i][g];
-        GSTAMP(0);
-        f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        const unsigned short *hb = &hbuf[cur][col * HP + 8 * quad];
-        // Row i's share of the step's memory traffic (next step's three input projections in, the previous step's h and saved
-        // gates out) is issued BEHIND the MFMAs of k-step i, with a scheduling barrier pinning it there: as one block in front
-        // of the MFMAs it was 1200 of the step's 6000 cycles (tools/stamp_gru.py), all of it issue time of an in-order wave
-        // while the matrix pipe sat idle.
-        auto row_traffic = [&](int i) __attribute__((always_inline)) {
-            if (step + 1 < T) {
-                gi_next[i][0] = gi_p[i][0]; gi_next[i][1] = gi_p[i][H]; gi_next[i][2] = gi_p[i][2 * H];
-                gi_p[i] += gi_step;
-            }
-            if (keep_t >= 0) {
-                if (live[i]) {
-                    *h_p[i] = keep_h[i];
-                    *reinterpret_cast<f32x4 *>(sv_p[i]) = keep_sv[i];
-                }
-                h_p[i] += h_step; sv_p[i] += sv_step;
-            }
-        };
-        static_assert(KS <= 4, "one row's traffic per k-step; rows left over go last");
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8g ah = lds_x8(hb + 32 * ks), am = lds_x8(hb + PLANE + 32 * ks), al = lds_x8(hb + 2 * PLANE + 32 * ks);
-            GRU_MFMA6X3(acc[0], acc[1], acc[2], ah, am, al, ah, am, al, ah, am, al, wh[0][ks], wm[0][ks], wl[0][ks], wh[1][ks], wm[1][ks],
-                        wl[1][ks], wh[2][ks], wm[2][ks], wl[2][ks]);
-            __builtin_amdgcn_sched_barrier(0);
-            row_traffic(ks);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int i = KS; i < 4; ++i) row_traffic(i);
-#ifdef ARVAE_GRU_STAMPS
-        { float dep = acc[0][0] + acc[1][0] + acc[2][3]; asm volatile("" :: "v"(dep)); __builtin_amdgcn_s_waitcnt(0); }
-#endif
-        GSTAMP(1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float r = fast_sigmoid(gi[i][0] + acc[0][i] + bh_r);
-            const float z = fast_sigmoid(gi[i][1] + acc[1][i] + bh_z);
-            const float ghn = acc[2][i] + bh_n;
-            const float n = fast_tanh(gi[i][2] + r * ghn);
-            const float hn = (1.f - z) * n + z * h[i];
-            h[i] = hn;
-            keep_h[i] = hn;
-            keep_sv[i] = f32x4{r, z, n, ghn};
-        }
-        store_split3_pair(&hbuf[cur ^ 1][(4 * quad) * HP + unit], HP, PLANE, h[0], h[1]);
-        store_split3_pair(&hbuf[cur ^ 1][(4 * quad + 2) * HP + unit], HP, PLANE, h[2], h[3]);
-        keep_t = t;
-#ifdef ARVAE_GRU_STAMPS
-        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the LDS writes are done
-#endif
-        GSTAMP(2);
-        lds_barrier();
-        GSTAMP(3);
-    }
-#ifdef ARVAE_GRU_STAMPS
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        for (int k = 0; k < 4; ++k) g_gru_stamps[k] = ph[k];
-        g_gru_stamps[4] = T;
-    }
-#endif
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (live[i]) {
-            *h_p[i] = keep_h[i];
-            *reinterpret_cast<f32x4 *>(sv_p[i]) = keep_sv[i];
-            if (s.h_fin != nullptr) s.h_fin[(int64_t)rows[i] * s.h_fin_stride + unit] = keep_h[i];
-        }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // The forward recurrence on the fp16 MFMA with SCALED TWO-TERM operands (the arithmetic of conv32_common.h): s x = h + l with
 // h = fp16(s x), l = fp16(s x - h), a product = the three partial products l h', h l', h h' on v_mfma_f32_16x16x32_f16, smallest
@@ -935,7 +604,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
         f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         const unsigned short *db = &dbuf[cur][gru_arow<E>(col) * DP + 8 * quad];
         static_assert(KS % 3 == 0 && KS / 3 <= 4, "three k-steps at a time, one per accumulator; one row's stores behind each group");
-        // row i's gradients of this step leave BEHIND the MFMAs of k-step group i (pinned: see gru_seq_fwd_x3_kernel)
+        // row i's gradients of this step leave BEHIND the MFMAs of k-step group i (pinned: see gru_seq_fwd_h2_kernel)
         auto row_stores = [&](int i) __attribute__((always_inline)) {
             if (live[i]) {
                 const int og = gru_off(rows[i], dgi_p, unit4), sg = t * R * dgi_p;
@@ -1128,7 +797,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
         f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         const unsigned short *db = &dbuf[gru_arow<E>(col) * DP + 8 * quad];
         static_assert(KS % 3 == 0 && KS / 3 <= 4, "three k-steps at a time, one per accumulator; one row's stores behind each group");
-        // row i's gradients of this step leave BEHIND the MFMAs of k-step group i (pinned: see gru_seq_fwd_x3_kernel)
+        // row i's gradients of this step leave BEHIND the MFMAs of k-step group i (pinned: see gru_seq_fwd_h2_kernel)
         auto row_stores = [&](int i) __attribute__((always_inline)) {
             if (live[i]) {
                 const int og = gru_off(rows[i], dgi_p, unit4), sg = t * R * dgi_p;
@@ -1389,226 +1058,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_kernel(TickFreeRun p) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// The free-running tick decoder on the bf16 MFMA (three-term split, fp32-accurate).  Three terms of the three
-// recurrent matrices do not fit any on-chip store (885 KB), so they are streamed: tick_weight_prep_kernel writes them
-// once per call in the exact per-lane register order (group = (matrix, k-step), 9 x 16 bytes per lane and group, lanes
-// contiguous), and every wave keeps a three-slot ring of groups in registers, always two groups (and across the tick
-// boundary) ahead of the MFMAs.  Per tick a workgroup pulls 885 KB from L2 against 3 x 72 MFMAs of 16 cycles per wave:
-// the kernel is L2-bandwidth bound (the fp32-MFMA version above was bound by its 288 x 32-cycle MFMAs and the exposed
-// latency of its unpipelined weight loads).
+// the three recurrent matrices of the free-running tick decoder (tick_weight_amax_kernel, tick_weight_prep_h2_kernel)
 struct TickPrep {
     const float *w[3];           // w_hh0, w_ih1, w_hh1
     uint4 *out;
 };
-
-template <int H>
-__global__ __launch_bounds__(256) void tick_weight_prep_kernel(TickPrep p) {
-    constexpr int NW = H / 16, KS = H / 32;
-    const int tid = blockIdx.x * 256 + threadIdx.x;
-    const int lane = tid & 63;
-    int rest = tid >> 6;
-    const int g = rest % 3; rest /= 3;
-    const int w = rest % NW; rest /= NW;
-    const int ks = rest % KS;
-    const int m = rest / KS;
-    if (m >= 3) return;
-    const int col = lane & 15, quad = lane >> 4;
-    const float *src = (m == 0 ? p.w[0] : m == 1 ? p.w[1] : p.w[2]) + (int64_t)(g * H + 16 * w + col) * H + 32 * ks + 8 * quad;
-    const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + 4);
-    const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-    bf16x8g hi, mid, lo;
-    split3_x8(x, hi, mid, lo);
-    uint4 *dst = p.out + ((int64_t)((m * KS + ks) * NW + w) * 9 + g * 3) * 64 + lane;
-    dst[0] = __builtin_bit_cast(uint4, hi);
-    dst[64] = __builtin_bit_cast(uint4, mid);
-    dst[128] = __builtin_bit_cast(uint4, lo);
-}
-
-template <int H, bool MASKED>
-__global__ __launch_bounds__(H * 4) void tick_free_run_x3_kernel(TickFreeRun p, const uint4 *__restrict__ packed) {
-    constexpr int NW = H / 16, KS = H / 32, KQ = H / 16;
-    constexpr int NGG = 9 * KS;                    // weight groups per tick: (matrix, k-step, gate), 3 x 16 bytes per lane each
-    constexpr int RS = NGG % 6 == 0 ? 6 : 3;       // register ring of groups; RS - 1 groups are in flight
-    constexpr int PFD = RS - 1;
-    constexpr int HP = H + 8, PLANE = 16 * HP, HS = H + 4;
-    __shared__ __attribute__((aligned(16))) unsigned short hA0[2][3 * PLANE];
-    __shared__ __attribute__((aligned(16))) unsigned short hA1[2][3 * PLANE];
-    __shared__ __attribute__((aligned(16))) unsigned short midp[3 * PLANE];
-    __shared__ __attribute__((aligned(16))) float h1f[16][HS];
-    __shared__ __attribute__((aligned(16))) float wout_s[64][HS];
-    __shared__ float cand_v[4][16];
-    __shared__ int cand_i[4][16];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int col = lane & 15, quad = lane >> 4;
-    const int unit = 16 * w + col;
-    const int row0 = blockIdx.x * 16;
-    const int B = p.batch;
-    const int ntile = (p.vocab + 15) / 16;
-
-    // weight stream: one buffer resource, one per-lane byte offset, the group's offset as the scalar offset of each
-    // load -- per-load 64-bit addresses would be hoisted out of the tick loop into 200+ VGPRs
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(packed), 0, 3 * KS * NW * 9 * 64 * 16, 0x00020000);
-    const int wlane = (w * 9 * 64 + lane) * 16;
-    bf16x8g wb[RS][3];
-    auto fetch = [&](int gg) {                     // gg = (matrix * KS + ks) * 3 + gate, compile-time at every call site
-        const int g = gg / 3, gate = gg % 3;
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-            wb[gg % RS][term] = __builtin_bit_cast(bf16x8g, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, (g * NW * 9 + gate * 3 + term) * 64 * 16, 0));
-    };
-#pragma unroll
-    for (int d = 0; d < PFD; ++d) fetch(d % NGG);
-
-    for (int e = threadIdx.x; e < 64 * H; e += H * 4) {       // note projection weights -> LDS (rows >= vocab: zeros)
-        const int n = e / H, k = e - n * H;
-        wout_s[n][k] = n < p.vocab ? p.w_out[(int64_t)n * H + k] : 0.f;
-    }
-    const float b0r = p.b_hh0[unit], b0z = p.b_hh0[H + unit], b0n = p.b_hh0[2 * H + unit];
-    const float b1r = p.b_ih1[unit] + p.b_hh1[unit], b1z = p.b_ih1[H + unit] + p.b_hh1[H + unit];
-    const float b1in = p.b_ih1[2 * H + unit], b1hn = p.b_hh1[2 * H + unit];
-    const int note = 16 * w + col;
-    const bool note_ok = w < ntile && note < p.vocab;
-    const float bout = note_ok ? p.b_out[note] : 0.f;
-
-    int rows[4];
-    bool live[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = row0 + 4 * quad + i;
-        live[i] = r < B;
-        rows[i] = live[i] ? r : B - 1;
-    }
-    float h0[4], h1[4], gb[4][3];
-    int tok[4] = {p.vocab, p.vocab, p.vocab, p.vocab};
-    const int ticks = p.beats * p.tpb;
-    const int aoff = col * HP + 8 * quad;                     // this lane's A-operand offset inside a plane
-
-    for (int t = 0; t < ticks; ++t) {
-        const int cur = t & 1;
-        const int beat = t / p.tpb;
-        if (t % p.tpb == 0) {
-            lds_barrier();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int64_t br = (int64_t)beat * B + rows[i];
-                h0[i] = p.h0_l0[br * p.h0_stride + unit];
-                h1[i] = p.h0_l1[br * p.h0_stride + unit];
-                store_split3(&hA0[cur][(4 * quad + i) * HP + unit], PLANE, h0[i]);
-                store_split3(&hA1[cur][(4 * quad + i) * HP + unit], PLANE, h1[i]);
-                const float *g = p.gib + br * 3 * H + unit;
-                gb[i][0] = g[0]; gb[i][1] = g[H]; gb[i][2] = g[2 * H];
-            }
-            lds_barrier();
-        }
-        float gi[4][3], keep[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float *pt = p.ptab + (int64_t)tok[i] * 3 * H + unit;
-            gi[i][0] = gb[i][0] + pt[0]; gi[i][1] = gb[i][1] + pt[H]; gi[i][2] = gb[i][2] + pt[2 * H];
-            keep[i] = MASKED ? p.keep_scale * (float)p.mask[((int64_t)t * B + rows[i]) * H + unit] : 1.f;
-        }
-        // ---- layer 0: matrix 0
-        {
-            f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            const unsigned short *ab = &hA0[cur][aoff];
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const bf16x8g ah = lds_x8(ab + 32 * ks), am = lds_x8(ab + PLANE + 32 * ks), al = lds_x8(ab + 2 * PLANE + 32 * ks);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const int gg = (0 * KS + ks) * 3 + q;
-                    fetch((gg + PFD) % NGG);
-                    __builtin_amdgcn_sched_barrier(0);
-                    GRU_MFMA6(acc[q], ah, am, al, wb[gg % RS][0], wb[gg % RS][1], wb[gg % RS][2]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float r = fast_sigmoid(gi[i][0] + acc[0][i] + b0r);
-                const float z = fast_sigmoid(gi[i][1] + acc[1][i] + b0z);
-                const float n = fast_tanh(gi[i][2] + r * (acc[2][i] + b0n));
-                h0[i] = (1.f - z) * n + z * h0[i];
-                store_split3(&hA0[cur ^ 1][(4 * quad + i) * HP + unit], PLANE, h0[i]);
-                store_split3(&midp[(4 * quad + i) * HP + unit], PLANE, h0[i] * keep[i]);
-            }
-        }
-        lds_barrier();
-        // ---- layer 1: matrix 1 (W_ih1 on mid), matrix 2 (W_hh1 on h1); r and z share an accumulator
-        {
-            f32x4 a1[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // r, z, i_n, h_n
-#pragma unroll
-            for (int m = 1; m <= 2; ++m) {
-                const unsigned short *ab = m == 1 ? &midp[aoff] : &hA1[cur][aoff];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const bf16x8g ah = lds_x8(ab + 32 * ks), am = lds_x8(ab + PLANE + 32 * ks), al = lds_x8(ab + 2 * PLANE + 32 * ks);
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        const int gg = (m * KS + ks) * 3 + q;
-                        fetch((gg + PFD) % NGG);
-                        __builtin_amdgcn_sched_barrier(0);
-                        GRU_MFMA6(a1[q == 2 ? m + 1 : q], ah, am, al, wb[gg % RS][0], wb[gg % RS][1], wb[gg % RS][2]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float r = fast_sigmoid(a1[0][i] + b1r);
-                const float z = fast_sigmoid(a1[1][i] + b1z);
-                const float n = fast_tanh(a1[2][i] + b1in + r * (a1[3][i] + b1hn));
-                h1[i] = (1.f - z) * n + z * h1[i];
-                store_split3(&hA1[cur ^ 1][(4 * quad + i) * HP + unit], PLANE, h1[i]);
-                h1f[4 * quad + i][unit] = h1[i];
-            }
-        }
-        lds_barrier();
-        // ---- logits (fp32 MFMA, weights in LDS) + row argmax
-        if (w < ntile) {
-            f32x4 lg = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kq = 0; kq < KQ; ++kq) {
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(&h1f[col][16 * kq + 4 * quad]);
-                const f32x4 b = *reinterpret_cast<const f32x4 *>(&wout_s[note][16 * kq + 4 * quad]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) lg = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], lg, 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v = note_ok ? fmaxf(lg[i] + bout, 0.f) : -1.f;
-                int ix = note;
-#pragma unroll
-                for (int off = 1; off < 16; off <<= 1) {
-                    const float ov = __shfl_xor(v, off, 64);
-                    const int oi = __shfl_xor(ix, off, 64);
-                    const bool take = ov > v || (ov == v && oi < ix);
-                    v = take ? ov : v;
-                    ix = take ? oi : ix;
-                }
-                if (col == 0) { cand_v[w][4 * quad + i] = v; cand_i[w][4 * quad + i] = ix; }
-            }
-        }
-        lds_barrier();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = 4 * quad + i;
-            float v = cand_v[0][r];
-            int ix = cand_i[0][r];
-            for (int c = 1; c < ntile; ++c) {
-                const float ov = cand_v[c][r];
-                const int oi = cand_i[c][r];
-                const bool take = ov > v;                      // later tiles hold larger indices: ties keep the earlier
-                v = take ? ov : v;
-                ix = take ? oi : ix;
-            }
-            tok[i] = ix;
-            if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
-        }
-    }
-}
 
 // one accumulator: l h', h l', h h'
 #define GRU_MFMA3(ACC, AH, AL, WH, WL)                                                 \
@@ -1978,25 +1432,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
 
 using namespace arvae;
 
-// ARVAE_GRU_FP32=1: the fp32-MFMA kernels (A/B measurements; the default is the three-term bf16 split)
-static bool gru_fp32_mfma() {
-    static const bool on = diag_env("ARVAE_GRU_FP32") != nullptr;
-    return on;
-}
-
-// ARVAE_GRU_BF16_FWD=1 (diagnostic build): the forward recurrence on the three-term bf16 split, as through round 3
-static bool gru_bf16_forward() {
-    static const bool on = diag_env("ARVAE_GRU_BF16_FWD") != nullptr;
-    return on;
-}
-
 // Batch rows per workgroup (gru_seq_fwd_h2_kernel): the smallest of 4, 8, 16 whose workgroups are all on the chip at once.
-// ARVAE_GRU_WIDE=1 (diagnostic build): always sixteen, as through round 4; ARVAE_GRU_ROWS=4|8|16: that many
+// ARVAE_GRU_WIDE=1 (diagnostic build): always sixteen, as through round 4
 static int gru_rows_per_wg(int rows, int nseq) {
     static const bool wide = diag_env("ARVAE_GRU_WIDE") != nullptr;
-    static const int forced = diag_env("ARVAE_GRU_ROWS") != nullptr ? atoi(diag_env("ARVAE_GRU_ROWS")) : 0;
     if (wide) return 16;
-    if (forced == 4 || forced == 8 || forced == 16) return forced;
     for (int rw = 4; rw < 16; rw *= 2)
         if ((int64_t)((rows + rw - 1) / rw) * nseq <= device_cu_count()) return rw;
     return 16;
@@ -2030,7 +1470,7 @@ static bool any_mask(const GruSeqMask *masks, int nseq) {
     return false;
 }
 namespace arvae {
-bool gru_seq_masks_supported() { return !gru_fp32_mfma() && !gru_bf16_forward() && !gru_bf16_backward(); }
+bool gru_seq_masks_supported() { return !gru_bf16_backward(); }
 }  // namespace arvae
 
 extern "C" int arvae_gru_seq_fwd(const arvae_gru_seq_t *seqs, int32_t nseq, int32_t steps, int32_t rows, int32_t hidden,
@@ -2059,19 +1499,8 @@ int arvae::gru_seq_fwd_masked(const arvae_gru_seq_t *seqs, const GruSeqMask *mas
         ARVAE_REQUIRE(gi_bytes < GRU_RANGE && h_bytes < GRU_RANGE, "gru_seq_fwd: %d steps x %d rows do not fit 2 GB per array", steps, rows);
     }
     hipStream_t st = as_stream(stream);
-    const dim3 grid((rows + 15) / 16, nseq);
-    if (gru_fp32_mfma()) {
-        if (hidden == 128) ARVAE_LAUNCH(gru_seq_fwd_kernel<128>, grid, dim3(512), 0, st, b, steps, rows);
-        else if (hidden == 64) ARVAE_LAUNCH(gru_seq_fwd_kernel<64>, grid, dim3(256), 0, st, b, steps, rows);
-        else ARVAE_LAUNCH(gru_seq_fwd_kernel<32>, grid, dim3(128), 0, st, b, steps, rows);
-    } else if (gru_bf16_forward()) {
-        if (hidden == 128) ARVAE_LAUNCH(gru_seq_fwd_x3_kernel<128>, grid, dim3(512), 0, st, b, steps, rows);
-        else if (hidden == 64) ARVAE_LAUNCH(gru_seq_fwd_x3_kernel<64>, grid, dim3(256), 0, st, b, steps, rows);
-        else ARVAE_LAUNCH(gru_seq_fwd_x3_kernel<32>, grid, dim3(128), 0, st, b, steps, rows);
-    } else {
-        const int rw = gru_rows_per_wg(rows, nseq);
-        GRU_LAUNCH(gru_seq_fwd_h2_kernel, rw, b, steps, rows)
-    }
+    const int rw = gru_rows_per_wg(rows, nseq);
+    GRU_LAUNCH(gru_seq_fwd_h2_kernel, rw, b, steps, rows)
     return check_launch("gru_seq_fwd_kernel");
 }
 
@@ -2101,23 +1530,14 @@ int arvae::gru_seq_bwd_masked(const arvae_gru_seq_t *seqs, const GruSeqMask *mas
                       (long long)widest);
     }
     hipStream_t st = as_stream(stream);
-    const dim3 grid((rows + 15) / 16, nseq);
-    if (gru_fp32_mfma()) {
-        if (hidden == 128) ARVAE_LAUNCH(gru_seq_bwd_kernel<128>, grid, dim3(512), 0, st, b, steps, rows);
-        else if (hidden == 64) ARVAE_LAUNCH(gru_seq_bwd_kernel<64>, grid, dim3(256), 0, st, b, steps, rows);
-        else ARVAE_LAUNCH(gru_seq_bwd_kernel<32>, grid, dim3(128), 0, st, b, steps, rows);
-    } else if (gru_bf16_backward()) {
-        const int rw = gru_rows_per_wg(rows, nseq);
-        GRU_LAUNCH(gru_seq_bwd_x3_kernel, rw, b, steps, rows)
-    } else {
-        const int rw = gru_rows_per_wg(rows, nseq);
-        GRU_LAUNCH(gru_seq_bwd_h2_kernel, rw, b, steps, rows)
-    }
+    const int rw = gru_rows_per_wg(rows, nseq);
+    if (gru_bf16_backward()) GRU_LAUNCH(gru_seq_bwd_x3_kernel, rw, b, steps, rows)
+    else GRU_LAUNCH(gru_seq_bwd_h2_kernel, rw, b, steps, rows)
     return check_launch("gru_seq_bwd_kernel");
 }
 
 extern "C" int64_t arvae_tick_free_run_ws_floats(int32_t hidden) {
-    // three matrices [3H][H] as three bf16 terms each (tick_weight_prep_kernel)
+    // three matrices [3H][H] as three 16-bit terms each (tick_weight_prep_h2_kernel writes two of them and the scales behind)
     return arvae_gru_seq_supported(hidden) ? (int64_t)3 * 3 * hidden * hidden * 3 / 2 : 0;
 }
 
@@ -2144,7 +1564,7 @@ extern "C" int arvae_tick_free_run(const arvae_tick_weights_t *wts, const float 
     hipStream_t st = as_stream(stream);
     const dim3 grid((batch + 15) / 16);
     const bool m = mask != nullptr;
-    if (gru_fp32_mfma() || ws == nullptr) {
+    if (ws == nullptr) {                                         // no workspace: the fp32-MFMA kernel, weights read in place
         if (hidden == 128 && m) ARVAE_LAUNCH((tick_free_run_kernel<128, 2, true>), grid, dim3(512), 0, st, p);
         else if (hidden == 128) ARVAE_LAUNCH((tick_free_run_kernel<128, 2, false>), grid, dim3(512), 0, st, p);
         else if (hidden == 64 && m) ARVAE_LAUNCH((tick_free_run_kernel<64, 2, true>), grid, dim3(256), 0, st, p);
@@ -2157,44 +1577,28 @@ extern "C" int arvae_tick_free_run(const arvae_tick_weights_t *wts, const float 
     TickPrep tp{{wts->w_hh0, wts->w_ih1, wts->w_hh1}, reinterpret_cast<uint4 *>(ws)};
     const int items = 3 * (hidden / 32) * (hidden / 16) * 3 * 64;
     const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
-    if (!gru_bf16_forward()) {
-        const int rw = gru_rows_per_wg(batch, 1);
-        const dim3 gr((batch + rw - 1) / rw);
+    const int rw = gru_rows_per_wg(batch, 1);
+    const dim3 gr((batch + rw - 1) / rw);
 #define TICK_H2_RW(HH, MM, RWV)                                                                                                  \
-        {                                                                                                                        \
-            if ((RWV) == 4) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 4>), gr, dim3(4 * HH), 0, st, p, packed);               \
-            else if ((RWV) == 8) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 8>), gr, dim3(4 * HH), 0, st, p, packed);          \
-            else ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 16>), gr, dim3(4 * HH), 0, st, p, packed);                         \
-        }
+    {                                                                                                                        \
+        if ((RWV) == 4) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 4>), gr, dim3(4 * HH), 0, st, p, packed);               \
+        else if ((RWV) == 8) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 8>), gr, dim3(4 * HH), 0, st, p, packed);          \
+        else ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 16>), gr, dim3(4 * HH), 0, st, p, packed);                         \
+    }
 #define TICK_H2(HH)                                                                                                              \
-        {                                                                                                                        \
-            float *wmax_ = ws + 9 * HH * HH;      /* (behind the two-term layout: the workspace is sized for three terms) */ \
-            ARVAE_LAUNCH(tick_weight_amax_kernel<HH>, dim3(3), dim3(1024), 0, st, tp, wmax_);                                     \
-            ARVAE_LAUNCH(tick_weight_prep_h2_kernel<HH>, dim3((items + 255) / 256), dim3(256), 0, st, tp, wmax_);                 \
-            if (m) TICK_H2_RW(HH, true, rw)                                                                                      \
-            else TICK_H2_RW(HH, false, rw)                                                                                       \
-        }
-        if (hidden == 128) TICK_H2(128)
-        else if (hidden == 64) TICK_H2(64)
-        else TICK_H2(32)
+    {                                                                                                                        \
+        float *wmax_ = ws + 9 * HH * HH;      /* (behind the two-term layout: the workspace is sized for three terms) */ \
+        ARVAE_LAUNCH(tick_weight_amax_kernel<HH>, dim3(3), dim3(1024), 0, st, tp, wmax_);                                     \
+        ARVAE_LAUNCH(tick_weight_prep_h2_kernel<HH>, dim3((items + 255) / 256), dim3(256), 0, st, tp, wmax_);                 \
+        if (m) TICK_H2_RW(HH, true, rw)                                                                                      \
+        else TICK_H2_RW(HH, false, rw)                                                                                       \
+    }
+    if (hidden == 128) TICK_H2(128)
+    else if (hidden == 64) TICK_H2(64)
+    else TICK_H2(32)
 #undef TICK_H2
 #undef TICK_H2_RW
-        return check_launch("tick_free_run_h2_kernel");
-    }
-    if (hidden == 128) {
-        ARVAE_LAUNCH(tick_weight_prep_kernel<128>, dim3((items + 255) / 256), dim3(256), 0, st, tp);
-        if (m) ARVAE_LAUNCH((tick_free_run_x3_kernel<128, true>), grid, dim3(512), 0, st, p, packed);
-        else ARVAE_LAUNCH((tick_free_run_x3_kernel<128, false>), grid, dim3(512), 0, st, p, packed);
-    } else if (hidden == 64) {
-        ARVAE_LAUNCH(tick_weight_prep_kernel<64>, dim3((items + 255) / 256), dim3(256), 0, st, tp);
-        if (m) ARVAE_LAUNCH((tick_free_run_x3_kernel<64, true>), grid, dim3(256), 0, st, p, packed);
-        else ARVAE_LAUNCH((tick_free_run_x3_kernel<64, false>), grid, dim3(256), 0, st, p, packed);
-    } else {
-        ARVAE_LAUNCH(tick_weight_prep_kernel<32>, dim3((items + 255) / 256), dim3(256), 0, st, tp);
-        if (m) ARVAE_LAUNCH((tick_free_run_x3_kernel<32, true>), grid, dim3(128), 0, st, p, packed);
-        else ARVAE_LAUNCH((tick_free_run_x3_kernel<32, false>), grid, dim3(128), 0, st, p, packed);
-    }
-    return check_launch("tick_free_run_x3_kernel");
+    return check_launch("tick_free_run_h2_kernel");
 }
 
 #ifdef ARVAE_GRU_STAMPS

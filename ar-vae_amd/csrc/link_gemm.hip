@@ -12,7 +12,6 @@
 // gathered global -> registers (prefetched one K-tile ahead so the loads fly under the MFMAs) ->
 // LDS in k-major order [BK][BM+1], from where each lane reads the single A and B value the
 // 32x32x2 MFMA wants (lane = (row|col) + 32 * k-parity) with conflict-free ds_read_b32.
-#include "diag.h"
 #include "common.h"
 #include "conv32_common.h"
 
@@ -671,7 +670,7 @@ __global__ __launch_bounds__(256) void down_single_channel_mfma_kernel(Geom g, O
 
 static bool single_channel_mfma_fits(const arvae_link_t *l) {
     return l->chi == 1 && l->clo == 64 && l->kh * l->kw <= 16 && l->hi_perm_c == 0 && l->lo_perm_c == 0 &&
-           (size_t)l->hh * l->hw * sizeof(float) <= 64 * 1024 && diag_env("ARVAE_C1_GENERIC") == nullptr &&
+           (size_t)l->hh * l->hw * sizeof(float) <= 64 * 1024 &&
            (int64_t)l->n * l->lh * l->lw * 64 * 4 < 0x7fff0000ll;       // (32-bit byte offsets into the 64-channel tensor)
 }
 
@@ -844,12 +843,6 @@ static int launch_gemm(const P &p, int M, int N, int zdim, bool wide_m, hipStrea
 
 using namespace arvae;
 
-// experiment switch: Linear layers over >= 2048 rows (the MeasureVAE's whole-sequence GEMMs) on the LDS-staged generic kernels
-static bool dense_rows_generic(const arvae_link_t *l, int which) {
-    static const int mode = diag_env("ARVAE_DENSE_GENERIC") ? atoi(diag_env("ARVAE_DENSE_GENERIC")) : 0;
-    return l->n >= 2048 && (mode & which) != 0;
-}
-
 extern "C" int64_t arvae_link_ws_floats(const arvae_link_t *link) {
     if (link == nullptr) return 0;
     if (conv32_fits(link)) return conv32_scratch_floats();       // one layer's prepared weights + the input's AMAX array
@@ -904,7 +897,7 @@ extern "C" int arvae_link_down(const arvae_link_t *link, const arvae_operand_t *
     DownPolicy p;
     if (int rc = make_geom(link, p.g)) return rc;
     ARVAE_REQUIRE(hi && hi->v && wt && lo, "link_down: null pointer");
-    if (dense_fits(link) && out_mask == nullptr && hi->y == nullptr && !dense_rows_generic(link, 1))
+    if (dense_fits(link) && out_mask == nullptr && hi->y == nullptr)
         return dense_fwd(link, hi->v, wt, bias, out_act, lo, as_stream(stream));
     if (conv32_fits(link) && out_mask == nullptr && hi->y == nullptr && out_act != ARVAE_ACT_SELU) {
         const float *wprep;
@@ -944,19 +937,12 @@ extern "C" int arvae_link_up(const arvae_link_t *link, const arvae_operand_t *lo
                   link->kh, link->kw, s);
     ARVAE_REQUIRE(link->hh % s == 0 && link->hw % s == 0, "link_up: hi extent not a multiple of the stride");
     hipStream_t st = as_stream(stream);
-    if (dense_fits(link) && out_mask == nullptr && bias == nullptr && out_act == ARVAE_ACT_NONE && !dense_rows_generic(link, 2))
+    if (dense_fits(link) && out_mask == nullptr && bias == nullptr && out_act == ARVAE_ACT_NONE)
         return dense_dgrad(link, make_operand(lo), wt, nullptr, hi, st);
     if (conv32_fits(link) && out_mask == nullptr && lo->y == nullptr && out_act != ARVAE_ACT_SELU) {
         const float *wprep;
         const unsigned *amax;
         if (int rc = conv32_make_operands(wt, lo->v, (int64_t)link->n * link->lh * link->lw * link->clo, ws, st, &wprep, &amax)) return rc;
-#ifdef ARVAE_STAMPS
-        static const float *stamp_gate = nullptr;                // diagnostic build: time the gated variant too
-        if (diag_env("ARVAE_STAMP_GATE") != nullptr) {
-            if (stamp_gate == nullptr) (void)hipMalloc((void **)&stamp_gate, (size_t)link->n * link->hh * link->hw * link->chi * 4);
-            return conv32_up(link, make_operand(lo), nullptr, 0, stamp_gate, nullptr, nullptr, hi, st, wprep, amax, nullptr);
-        }
-#endif
         return conv32_up(link, make_operand(lo), bias, out_act == ARVAE_ACT_RELU, nullptr, nullptr, nullptr, hi, st, wprep, amax, nullptr);
     }
     if (conv_c1_fits(link) && lo->y == nullptr && out_mask == nullptr && out_act == ARVAE_ACT_NONE)
@@ -967,8 +953,7 @@ extern "C" int arvae_link_up(const arvae_link_t *link, const arvae_operand_t *lo
         const int total = link->n * link->hh * link->hw;
         Epilogue ep{bias, out_mask, hi, out_act};
         const size_t t_bytes = sizeof(float) * 17 * link->lh * link->lw;
-        if ((link->clo == 64 || link->clo == 32) && link->kh * link->kw <= 16 && t_bytes <= 96 * 1024 &&
-            diag_env("ARVAE_UP1_NAIVE") == nullptr) {
+        if ((link->clo == 64 || link->clo == 32) && link->kh * link->kw <= 16 && t_bytes <= 96 * 1024) {
             if (link->clo == 64) ARVAE_LAUNCH(up_single_channel_mfma_kernel<4>, dim3(link->n), dim3(256), t_bytes, st, p.g, lo->v, wt, ep);
             else ARVAE_LAUNCH(up_single_channel_mfma_kernel<2>, dim3(link->n), dim3(256), t_bytes, st, p.g, lo->v, wt, ep);
             return check_launch("link_up(single channel, mfma)");
@@ -1060,7 +1045,7 @@ extern "C" int arvae_link_wgrad(const arvae_link_t *link, const arvae_operand_t 
     ARVAE_REQUIRE(ws != nullptr || arvae_link_wgrad_ws_floats(link) == 0,
                   "link_wgrad: workspace of arvae_link_wgrad_ws_floats() floats needed");
     hipStream_t st = as_stream(stream);
-    if (dense_fits(link) && hi->y == nullptr && bias_side != 2 && !dense_rows_generic(link, 4))
+    if (dense_fits(link) && hi->y == nullptr && bias_side != 2)
         return dense_wgrad(link, make_operand(lo), hi->v, dwt, bias_side == 1 ? dbias : nullptr, ws, st);
     if (conv_c1_fits(link) && lo->mask == nullptr && hi->mask == nullptr && lo->act != ARVAE_ACT_SELU &&
         hi->act != ARVAE_ACT_SELU)

@@ -550,9 +550,8 @@ static bool conv_fold_layer_ok(const arvae_layer_t &l, bool up) {
            k.hw == 8 && k.lh == 4 && k.lw == 4 && k.hi_perm_c == 0 && k.lo_perm_c == 0 && l.act == ARVAE_ACT_RELU && l.dropout == 0;
 }
 static bool midc_fold_topology(const arvae_image_vae_t *m, int ne, int nd) {
-    static const bool off = diag_env("ARVAE_MIDC_NO_FOLD") != nullptr;       // diagnostic build: the four launches of round 4
     const int e = m->n_enc - ne - 1;                             // the conv layer in front of the block
-    if (off || !midc_topology(m, ne, nd) || e < 1 || nd + 1 >= m->n_dec) return false;
+    if (!midc_topology(m, ne, nd) || e < 1 || nd + 1 >= m->n_dec) return false;
     const arvae_layer_t &before = m->enc[e - 1];
     return conv_fold_layer_ok(m->enc[e], false) && conv_fold_layer_ok(m->dec[nd], true) && before.act == ARVAE_ACT_RELU &&
            before.dropout == 0 && m->dec[nd - 1].act == ARVAE_ACT_RELU;
@@ -640,8 +639,7 @@ static void mid_describe(const arvae_image_vae_t *m, const float *params, float 
     // Wide layers go to the tile GEMMs (not for the dSprites-shaped block: the clustered kernels take that one whole); they keep
     // ONE prepared copy, mb = W'[n_mem][k_mem], which the GEMMs read both ways
     {
-        static const bool no_wide = diag_env("ARVAE_MID_NO_WIDE") != nullptr;     // diagnostic build: every layer on the row kernels
-        const bool shape_ok = !no_wide && !midc_topology(m, ne, nd);
+        const bool shape_ok = !midc_topology(m, ne, nd);
         pl.wide_e = shape_ok && ne >= 1 && a.enc[0].k >= MID_WIDE_MIN && a.enc[0].k % 4 == 0 && a.enc[0].n % 4 == 0;
         pl.wide_d = shape_ok && nd >= 2 && a.dec[nd - 1].n >= MID_WIDE_MIN && a.dec[nd - 1].k % 4 == 0 && a.dec[nd - 1].n % 4 == 0;
         // their ONE prepared copy: the three bf16 terms of W'[n_mem][k_mem] as planes, in the space of the fp32 layouts they replace
@@ -737,12 +735,10 @@ static void mid_describe(const arvae_image_vae_t *m, const float *params, float 
     // Batch rows per workgroup: every workgroup streams every matrix (~115 GB/s, the L2 -> CU rate of one CU), so the layer time is
     // that stream plus the FMA / LDS work of its rows -- as few rows as still give every CU at most ONE workgroup: 1 / 2 / 4 rows
     // for B <= 256 / 512 / more on 256 CUs (B = 512: forward 32.0 -> 28.8 us, backward 34.6 -> 31.0 us against 4 rows; 8 rows per
-    // workgroup measured 49 vs 36 us forward: the FMA work per workgroup doubles).  ARVAE_MID_ROWS=n overrides.
+    // workgroup measured 49 vs 36 us forward: the FMA work per workgroup doubles).
     {
-        static const int forced = diag_env("ARVAE_MID_ROWS") != nullptr ? atoi(diag_env("ARVAE_MID_ROWS")) : 0;
         const int cus = mid_cu_count();
         pl.rows = batch > 2 * cus ? 4 : batch > cus ? 2 : 1;
-        if (forced == 1 || forced == 2 || forced == 4) pl.rows = forced;
     }
     pl.lds_bytes = (size_t)(2 * pl.rows * a.ld + mid_red(pl.rows) + pl.rows * 32) * sizeof(float);
 }
@@ -779,11 +775,9 @@ static void midc_common(McArgs &c, const MidArgs &a, int batch) {
     c.batch = batch;
     c.clusters = (batch + MC_R - 1) / MC_R;
     c.heads = c.clusters % 4 == 0 ? 4 : (c.clusters % 2 == 0 ? 2 : 1);
-    if (const char *hd = diag_env("ARVAE_MIDC_HEADS")) { const int v = atoi(hd); if (v >= 1 && v <= 8 && c.clusters % v == 0) c.heads = v; }
     c.debug_drop = diag_env("ARVAE_MIDC_DROP_ARRIVAL") != nullptr;
-    c.debug_static = diag_env("ARVAE_MIDC_STATIC") != nullptr;
+    c.debug_static = 0;
     c.wait_ticks = midc_wait_ticks();
-    if (const char *ms = diag_env("ARVAE_MIDC_WAIT_MS")) c.wait_ticks = (unsigned long long)atoll(ms) * 100000ull;
     c.y_e0 = a.enc[0].y; c.y_e1 = a.enc[1].y; c.y_d0 = a.dec[0].y; c.y_d1 = a.dec[1].y; c.y_d2 = a.dec[2].y;
     c.g_e0 = a.enc[0].gpre; c.g_e1 = a.enc[1].gpre; c.g_d0 = a.dec[0].gpre; c.g_d1 = a.dec[1].gpre; c.g_d2 = a.dec[2].gpre;
 }
@@ -878,7 +872,6 @@ int mid_forward(const arvae_image_vae_t *m, int batch, const float *params, floa
         for (int i = 1; i < a.ne; ++i) { a.warm_ptr[nw] = a.enc[i].mf; a.warm_lines[nw++] = lines((int64_t)a.enc[i].k * a.enc[i].n); }
         a.warm_ptr[nw] = a.hf; a.warm_lines[nw++] = lines((int64_t)a.h * 2 * a.zdim);
         for (int i = 0; i < a.nd - (wide_d ? 1 : 0); ++i) { a.warm_ptr[nw] = a.dec[i].mf; a.warm_lines[nw++] = lines((int64_t)a.dec[i].k * a.dec[i].n); }
-        if (diag_env("ARVAE_MID_NO_WARM") != nullptr) nw = 0;
     }
     mid_allow_lds();
     if (!prep_done) {
@@ -978,7 +971,6 @@ int mid_backward(const arvae_image_vae_t *m, int batch, const float *params, flo
         for (int i = a.nd - 2 - (wide_d ? 1 : 0); i >= 0; --i) { a.warm_ptr[nw] = a.dec[i].mb; a.warm_lines[nw++] = lines((int64_t)a.dec[i].kb * a.dec[i].n); }
         a.warm_ptr[nw] = a.hb; a.warm_lines[nw++] = lines((int64_t)a.h * 2 * a.zdim);
         for (int i = a.ne - 1; i >= (wide_e ? 1 : 0); --i) { a.warm_ptr[nw] = a.enc[i].mb; a.warm_lines[nw++] = lines((int64_t)a.enc[i].kb * a.enc[i].n); }
-        if (diag_env("ARVAE_MID_NO_WARM") != nullptr) nw = 0;
     }
     mid_allow_lds();
     if (wide_d)
@@ -1021,8 +1013,7 @@ int mid_backward(const arvae_image_vae_t *m, int batch, const float *params, flo
 int mid_wide_wgrad(const arvae_image_vae_t *m, int batch, const float *params, float *prep_ws, float *wide_ws, const float *x0,
                    const float *g_last_pre, float *grads, hipStream_t s, int *took) {
     *took = 0;
-    static const bool off = diag_env("ARVAE_MID_NO_WIDE_WGRAD") != nullptr;      // diagnostic build: the grouped 32 x 32-tile launch
-    if (wide_ws == nullptr || off) return ARVAE_OK;
+    if (wide_ws == nullptr) return ARVAE_OK;
     MidPlan pl;
     mid_describe(m, params, prep_ws, pl, batch);
     if (!pl.wide_e && !pl.wide_d) return ARVAE_OK;

@@ -36,7 +36,8 @@ struct McConv {
 struct McArgs {
     int batch, zdim, clusters;
     unsigned long long wait_ticks;   // bound of a hand-off poll, in 10 ns ticks of the polling wave's own running time
-    int debug_static;           // diagnostic build only (ARVAE_MIDC_STATIC): places by blockIdx instead of tickets
+    int debug_static;           // always 0 (places by blockIdx instead of tickets: a retired experiment); left in so that the
+                                // clustered kernels' code stays the code that was measured
     int debug_drop;             // diagnostic build only (ARVAE_MIDC_DROP_ARRIVAL): one member never arrives at the first hand-off
     int heads;                  // ticket heads the places of a pass are dealt from (4, 2 or 1; divides `clusters`): midcluster.hip
     unsigned *counters;         // one arrival counter per cluster, 32 words apart; multiples of MC_S between phases; behind

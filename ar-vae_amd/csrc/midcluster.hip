@@ -186,7 +186,7 @@ __device__ __forceinline__ void mc_place(const McArgs &p, int b, int &cl, int &m
 // (mc_placed / mc_clear_heads), the step's prep launch clears everything.
 constexpr unsigned MC_E_FWD = ARVAE_STATUS_HANDOFF_FWD, MC_E_BWD = ARVAE_STATUS_HANDOFF_BWD, MC_E_TICKET = ARVAE_STATUS_HANDOFF_TICKET;     // arvae_hip.h: float-safe bit patterns
 __device__ __forceinline__ int mc_ticket(const McArgs &p) {
-    if (p.debug_static) return (int)blockIdx.x;          // diagnostic build, ARVAE_MIDC_STATIC: places by blockIdx (what tickets cost)
+    if (p.debug_static) return (int)blockIdx.x;          // (never set: McArgs.debug_static)
     __shared__ int place;
     if (threadIdx.x == 0) {
         const unsigned heads = (unsigned)p.heads, h = blockIdx.x % heads;

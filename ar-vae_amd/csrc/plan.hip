@@ -237,8 +237,7 @@ static int make_layout(const arvae_image_vae_t *m, int64_t n, int64_t n_cols, La
         arvae_link_t lk = l.link;
         lk.n = (int32_t)n;
         const bool fast = (conv32_fits(&lk) && wprep >= 0) || (conv_c1_fits(&lk) && !l.is_up);
-        static const bool off = diag_env("ARVAE_NO_RELU_BITS") != nullptr;      // diagnostic: gate with the float activations
-        return (fast && !off && l.act == ARVAE_ACT_RELU && !l.dropout) ? take(out_elems(l, n) / 32) : -1;
+        return (fast && l.act == ARVAE_ACT_RELU && !l.dropout) ? take(out_elems(l, n) / 32) : -1;
     };
     int n_prep = 0;
     auto own_prep = [&](const arvae_layer_t &l) -> int64_t {
@@ -587,7 +586,7 @@ extern "C" int arvae_image_vae_forward(const arvae_image_vae_t *m, int32_t batch
             if (L.dec_wprep[i] >= 0) { wts[np] = params + m->dec[i].w_off; preps[np++] = ws + L.dec_wprep[i]; }
         // (together with the latent block's matrix layouts when that block runs: one prep launch per step -- or none: when
         // the first encoder layer is the single-channel convolution, the prep rides in ITS grid, conv_c1.hip)
-        if (np > 0 && mid && diag_env("ARVAE_SPLIT_PREP") == nullptr) {
+        if (np > 0 && mid) {
             MidPrepArgs margs;
             mid_prep_args(m, params, ws + L.mid_prep, &margs, batch);
             const arvae_layer_t &l0 = m->enc[0];

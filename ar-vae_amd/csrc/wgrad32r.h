@@ -143,17 +143,6 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
         WGR_STAMP(1, 1);
         __syncthreads();                                         // step k0 is in LDS
         // step k is being consumed: refill its register set with step k + DEPTH, commit step k + 1
-#if defined(WGR_NO_PRODUCE)                                     /* ablation build: barriers only */
-#define ARVAE_WGR_PRODUCE(D)                                                          \
-        if (k + D >= k1) break;                                                       \
-        __syncthreads();
-#elif defined(WGR_NO_COMMIT)                                    /* ablation build: loads, no split / LDS writes */
-#define ARVAE_WGR_PRODUCE(D)                                                          \
-        if (k + D >= k1) break;                                                       \
-        issue(std::integral_constant<int, D>{}, k + D + WGR_DEPTH);                   \
-        asm volatile("" ::"v"(hv[(D + 1) % WGR_DEPTH][0]), "v"(hv[(D + 1) % WGR_DEPTH][3]), "v"(lv[(D + 1) % WGR_DEPTH])); \
-        __syncthreads();
-#else
 #define ARVAE_WGR_PRODUCE(D)                                                          \
         if (k + D >= k1) break;                                                       \
         WGR_STAMP(1, 2 + 2 * (k + D - k0));                                           \
@@ -161,7 +150,6 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
         commit(std::integral_constant<int, (D + 1) % WGR_DEPTH>{}, k + D + 1);        \
         WGR_STAMP(1, 3 + 2 * (k + D - k0));                                           \
         __syncthreads();
-#endif
         for (int k = k0;; k += WGR_DEPTH) {
             ARVAE_WGR_PRODUCE(0)
             ARVAE_WGR_PRODUCE(1)
@@ -217,9 +205,6 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
         };
         auto read_block = [&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
-#ifdef WGR_NO_READS                                             // ablation build: MFMAs on whatever the registers hold
-            return;
-#endif
 #pragma unroll
             for (int t = 0; t < 2; ++t) b2[b][t] = lds_tr_f16x8(lbuf + t * LPLANE + loff[b][0], lbuf + t * LPLANE + loff[b][1]);
             const unsigned *hb = b == 0 ? hrow0 : hrow1;
@@ -246,11 +231,6 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
         };
         auto mfma_block = [&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
-#ifdef WGR_NO_MFMA                                              // ablation build: reads stay, products go
-#pragma unroll
-            for (int kx = 0; kx < 4; ++kx)
-                asm volatile("" ::"v"(a2[b][kx][0]), "v"(a2[b][kx][1]), "v"(b2[b][0]), "v"(b2[b][1]));
-#else
             // (a term, b term) of the three partial products, smallest first
 #define ARVAE_WGR_PRODUCT(TA, TB)                                                     \
             _Pragma("unroll") for (int kx = 0; kx < 4; ++kx) MFMA_H(acc[kx], a2[b][kx][TA], b2[b][TB]);
@@ -258,7 +238,6 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
             ARVAE_WGR_PRODUCT(0, 1)
             ARVAE_WGR_PRODUCT(0, 0)
 #undef ARVAE_WGR_PRODUCT
-#endif
         };
         const float inv = amax_scale(al_l).inv * amax_scale(al_h).inv;     // accumulators -> fp32 partial sums (exact)
         WGR_STAMP(0, 0);
@@ -279,9 +258,7 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
             mask_b(std::integral_constant<int, 0>{}, k);
             read_block(std::integral_constant<int, 1>{});
             mfma_block(std::integral_constant<int, 0>{});
-#if !defined(WGR_NO_MFMA) && !defined(WGR_NO_READS)
             ARVAE_WGR_INTERLEAVE
-#endif
             __builtin_amdgcn_sched_barrier(0);
             WGR_STAMP(0, 2 + 2 * (k - k0));
             __syncthreads();                                     // every read of step k has landed; step k + 1 is in LDS
@@ -291,9 +268,7 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
             __builtin_amdgcn_sched_barrier(0);
             read_block(std::integral_constant<int, 0>{});        // (past the last step: harmless reads of stale rows)
             mfma_block(std::integral_constant<int, 1>{});
-#if !defined(WGR_NO_MFMA) && !defined(WGR_NO_READS)
             ARVAE_WGR_INTERLEAVE
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
 #undef ARVAE_WGR_INTERLEAVE

@@ -21,7 +21,7 @@ cnt = 256 * 2 * 64 * 2
 buf = (ctypes.c_ulonglong * cnt)()
 assert fn(buf, cnt) == 0
 st = np.array(buf, dtype=np.uint64).reshape(256, 2, 64, 2).astype(np.int64)
-steps = int(os.environ.get('ARVAE_WGR_SPW', n * lo_sz * lo_sz // 32 // 256))
+steps = n * lo_sz * lo_sz // 32 // 256                         # steps per workgroup on 256 CUs (conv32.hip stream_geometry)
 nwg = min(256, n * lo_sz * lo_sz // 32 // steps)
 st = st[:nwg]
 c, w = st[:, 0, :, 0], st[:, 0, :, 1]
