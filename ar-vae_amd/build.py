@@ -69,7 +69,7 @@ def _build(force, verbose, lib_path, objdir_name, extra_flags):
         if verbose and out.strip():
             print(out)
     if force or procs or _stale(lib_path, objs):
-        cmd = [hipcc, f'--offload-arch={ARCH}', '-shared', '-fPIC', '-o', lib_path] + objs
+        cmd = [hipcc, f'--offload-arch={ARCH}', '-shared', '-fPIC', '-Wl,--no-undefined', '-o', lib_path] + objs
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.run(cmd, check=True)

@@ -29,6 +29,7 @@
 #include "diag.h"
 #include "common.h"
 #include "conv32_common.h"
+#include "conv32.h"
 #include "reduce.h"
 #include "midprep.h"
 #include "prep32.h"
@@ -1465,7 +1466,7 @@ static int conv32_wgrad_stream(const arvae_link_t *l, const Operand &lo, const O
                        : launch_stream<8>(l, lo.v, hi.v, slab, bias_mode, amax_lo, amax_hi, s);
 }
 
-int conv32_wgrad_groups(const arvae_link_t *l) {
+static int conv32_wgrad_groups(const arvae_link_t *l) {
     if (conv32_wgrad_stream_fits(l)) return conv32_wgrad_stream_groups(l);
     // the patch-staged kernel (4x4 layers): 64-pixel tiles, one persistent workgroup per CU, one 64 KB partial each
     return grid_for_tiles(tiles_for<4, 64>(l->n));

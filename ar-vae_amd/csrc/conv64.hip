@@ -14,6 +14,7 @@
 #include "common.h"
 #include "x3tile.h"
 #include "conv32_common.h"
+#include "conv64.h"
 
 namespace arvae {
 
@@ -546,13 +547,6 @@ __global__ __launch_bounds__(256) void conv64_weight_prep_kernel(const float *__
 
 // The re-ordered copy lives in the CALLER's workspace (arvae_link_ws_floats): every launch re-creates it on the caller's
 // stream right before the convolution.
-// (conv64s.hip: the row-staged kernel of the 64 <-> 64 channel layers and its split weights)
-int64_t conv64s_ws_floats();
-bool conv64s_fits(const arvae_link_t *l, bool up);
-int conv64s_run(const Operand &src, int n, int sh, int sw, int oh, int ow, int q, int sgn, int off, const float *wt, bool transposed,
-                const float *bias, int act, const uint8_t *mask, float *out, float *ws, hipStream_t s, const char *what, const GateOp *gate,
-                const unsigned *amax_in, unsigned *amax_out, bool prepped);
-
 int64_t conv64_ws_floats(const arvae_link_t *l) {
     const int64_t packed = ((int64_t)l->kh * l->kw * l->chi * l->clo + 3) / 4 * 4 + 4;     // (+ the weights' maximum, conv_rows_h2_kernel)
     const bool staged = conv64s_fits(l, false) || conv64s_fits(l, true);
@@ -1197,8 +1191,6 @@ int64_t conv64_wgrad_ws_floats(const arvae_link_t *l) {
     const int64_t bias_partials = ((l->n + ipw_pairs - 1) / ipw_pairs) * 64;                  // (its bias sums riding along)
     return (taps_kernel > rows_kernel ? taps_kernel : rows_kernel) + bias_partials + 2 * AMAX_N;     // + the two operands' AMAX arrays
 }
-
-int conv64_operand_amax(const Operand &x, int64_t count, unsigned *out, hipStream_t s);      // conv64s.hip
 
 int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *dwt, float *ws, hipStream_t s,
                  const unsigned *amax_lo, const unsigned *amax_hi, float *dbias, int bias_side, bool *bias_done) {

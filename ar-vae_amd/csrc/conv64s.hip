@@ -31,6 +31,7 @@
 #include "diag.h"
 #include "common.h"
 #include "conv32_common.h"
+#include "conv64.h"
 
 #ifdef C64S_STAMPS
 // diagnostic build only (tools/stamp_c64s.py): phase timeline of the first 64 workgroups, 100 MHz wall clock

@@ -15,6 +15,7 @@
 #include "prep32.h"
 #include "wgrad_c1s.h"
 #include "vae_finish.h"
+#include "conv_c1.h"
 
 namespace arvae {
 

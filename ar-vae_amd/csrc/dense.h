@@ -87,6 +87,11 @@ int dense_wgrad_long_flush(LongWgradQueue *q, hipStream_t s);
 bool dense_wgrad_defer(DenseWgradBatch *b, const arvae_link_t *l, const Operand &g, const float *x, float *dw, float *dbias);
 int dense_wgrad_flush(DenseWgradBatch *b, hipStream_t s);
 struct SlabReduceBatch;
+struct SlabJob;
 int dense_wgrad_slab_flush(DenseWgradBatch *b, SlabReduceBatch *r, hipStream_t s);      // both closing queues of a backward pass, one launch
+// the queued Linear weight gradients and the single-channel layer's weight-gradient partials (conv_c1.h) in one launch
+bool dense_wgrad_c1_fits(const DenseWgradBatch *b);
+int dense_wgrad_flush_with_c1(DenseWgradBatch *b, const arvae_link_t *l, const Operand &lo, const Operand &img, float *dwt, float *dbias,
+                              int bias_mode, float *slab, hipStream_t s, SlabJob *job);
 
 }  // namespace arvae

@@ -17,6 +17,7 @@
 #include "reduce.h"
 #include "x3tile.h"
 #include "wgrad_c1s.h"
+#include "conv_c1.h"
 
 namespace arvae {
 
@@ -1456,7 +1457,6 @@ int dense_wgrad_flush(DenseWgradBatch *b, hipStream_t s) {
 }
 
 // the queued Linear weight gradients and the single-channel layer's weight-gradient partials (conv_c1.hip) in one launch
-int wgrad_c1_groups(const arvae_link_t *l);
 bool dense_wgrad_c1_fits(const DenseWgradBatch *b) {
     static const bool off = diag_env("ARVAE_NO_PAIR_TAIL") != nullptr;
     return !off && b != nullptr && b->count > 0;

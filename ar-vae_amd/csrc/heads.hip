@@ -8,6 +8,7 @@
 #include "diag.h"
 #include "common.h"
 #include "rng.h"
+#include "heads.h"
 
 namespace arvae {
 

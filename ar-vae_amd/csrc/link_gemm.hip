@@ -14,62 +14,17 @@
 // 32x32x2 MFMA wants (lane = (row|col) + 32 * k-parity) with conflict-free ds_read_b32.
 #include "common.h"
 #include "conv32_common.h"
+#include "dense.h"
+#include "conv32.h"
+#include "conv_c1.h"
+#include "conv64.h"
+#include "link.h"
 
 namespace arvae {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
-
-// batch-sized nn.Linear kernels (dense.hip)
-bool dense_fits(const arvae_link_t *l);
-int dense_fwd(const arvae_link_t *l, const float *x, const float *w, const float *bias, int act, float *y, hipStream_t s);
-int dense_dgrad(const arvae_link_t *l, const Operand &g, const float *w, const float *gate, float *dx, hipStream_t s);
-int64_t dense_wgrad_ws_floats(const arvae_link_t *l);
-int dense_wgrad(const arvae_link_t *l, const Operand &g, const float *x, float *dw, float *dbias, float *ws, hipStream_t s);
-
-// 1-channel 64x64 image links (conv_c1.hip)
-bool conv_c1_fits(const arvae_link_t *l);
-bool conv_c1w_fits(const arvae_link_t *l);
-int64_t conv_c1w_wgrad_ws_floats(const arvae_link_t *l);
-int conv_c1w_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &img, float *dwt, float *dbias, int bias_mode,
-                   float *slab, hipStream_t s);
-int conv_c1_down(const arvae_link_t *l, const Operand &img, const float *wt, const float *bias, int relu,
-                 const float *gate, const uint16_t *gate_bits, uint16_t *bits_out, float *out, hipStream_t s, unsigned *amax_out);
-int conv_c1_up(const arvae_link_t *l, const float *lo, const float *wt, const float *bias, float *out, hipStream_t s);
-int64_t conv_c1_wgrad_ws_floats(const arvae_link_t *l);
-int conv_c1_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &img, float *dwt, float *dbias, int bias_mode,
-                  float *slab, hipStream_t s);
-
-// stride-1 wide-channel convolutions on the split-bf16 MFMA (conv64.hip)
-bool conv64_fits(const arvae_link_t *l, bool up);
-int64_t conv64_ws_floats(const arvae_link_t *l);
-int conv64_down(const arvae_link_t *l, const Operand &hi, const float *wt, const float *bias, int act, const uint8_t *mask,
-                float *lo, float *ws, hipStream_t s, const GateOp *gate, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr,
-                float *prepped = nullptr);
-int conv64_up(const arvae_link_t *l, const Operand &lo, const float *wt, const float *bias, int act, const uint8_t *mask,
-              float *hi, float *ws, hipStream_t s, const GateOp *gate, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr,
-              float *prepped = nullptr);
-bool conv64_wgrad_fits(const arvae_link_t *l);
-int64_t conv64_wgrad_ws_floats(const arvae_link_t *l);
-int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *dwt, float *ws, hipStream_t s,
-                 const unsigned *amax_lo, const unsigned *amax_hi, float *dbias, int bias_side, bool *bias_done);
-
-// specialised 32-channel k4/s2/p1 kernels (conv32.hip)
-bool conv32_fits(const arvae_link_t *l);
-// (operands come with AMAX arrays and prepared weights: conv32_common.h; a per-layer caller has neither and makes them in `ws`)
-int conv32_down(const arvae_link_t *l, const Operand &hi, const float *bias, int relu, const float *gate, const uint16_t *gate_bits,
-                uint16_t *bits_out, float *out, hipStream_t s, const float *wprep, const unsigned *amax_in, unsigned *amax_out);
-int conv32_up(const arvae_link_t *l, const Operand &lo, const float *bias, int relu, const float *gate, const uint16_t *gate_bits,
-              uint16_t *bits_out, float *out, hipStream_t s, const float *wprep, const unsigned *amax_in, unsigned *amax_out);
-int64_t conv32_wgrad_ws_floats(const arvae_link_t *l);
-int conv32_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *dwt, float *dbias, int bias_mode,
-                 float *slab, hipStream_t s, const unsigned *amax_lo, const unsigned *amax_hi);
-int64_t conv32_prep_floats();
-int64_t conv32_scratch_floats();
-int conv32_weight_prep(const float *const *wts, float *const *preps, int n_layers, hipStream_t s);
-int conv32_amax(const float *x, int64_t count, unsigned *out, hipStream_t s);
-constexpr int64_t CONV32_AMAX_FLOATS = 1024;          // AMAX_N (conv32_common.h)
 
 struct Geom {
     int n, hh, hw, chi, lh, lw, clo, kh, kw, stride, pad;
@@ -1029,8 +984,8 @@ extern "C" int64_t arvae_link_wgrad_ws_floats(const arvae_link_t *link) {
     if (blocks * link->chi > need) need = blocks * link->chi;
     if (dense_fits(link) && dense_wgrad_ws_floats(link) > need) need = dense_wgrad_ws_floats(link);
     if (conv64_wgrad_fits(link) && conv64_wgrad_ws_floats(link) > need) need = conv64_wgrad_ws_floats(link);
-    if (conv32_fits(link) && conv32_wgrad_ws_floats(link) + 2 * CONV32_AMAX_FLOATS > need)        // slabs + the operands' AMAX arrays
-        need = conv32_wgrad_ws_floats(link) + 2 * CONV32_AMAX_FLOATS;
+    if (conv32_fits(link) && conv32_wgrad_ws_floats(link) + 2 * AMAX_N > need)        // slabs + the operands' AMAX arrays
+        need = conv32_wgrad_ws_floats(link) + 2 * AMAX_N;
     if (conv_c1_fits(link) && conv_c1_wgrad_ws_floats(link) > need) need = conv_c1_wgrad_ws_floats(link);
     if (conv_c1w_fits(link) && conv_c1w_wgrad_ws_floats(link) > need) need = conv_c1w_wgrad_ws_floats(link);
     return need;
@@ -1055,8 +1010,8 @@ extern "C" int arvae_link_wgrad(const arvae_link_t *link, const arvae_operand_t 
     if (wgrad_fast(link, lo, hi)) {
         unsigned *am = reinterpret_cast<unsigned *>(ws + conv32_wgrad_ws_floats(link));
         if (int rc = conv32_amax(lo->v, (int64_t)link->n * link->lh * link->lw * link->clo, am, st)) return rc;
-        if (int rc = conv32_amax(hi->v, (int64_t)link->n * link->hh * link->hw * link->chi, am + CONV32_AMAX_FLOATS, st)) return rc;
-        return conv32_wgrad(link, make_operand(lo), make_operand(hi), dwt, dbias, bias_side, ws, st, am, am + CONV32_AMAX_FLOATS);
+        if (int rc = conv32_amax(hi->v, (int64_t)link->n * link->hh * link->hw * link->chi, am + AMAX_N, st)) return rc;
+        return conv32_wgrad(link, make_operand(lo), make_operand(hi), dwt, dbias, bias_side, ws, st, am, am + AMAX_N);
     }
     p.lo = make_operand(lo);
     p.hi = make_operand(hi);

@@ -6,6 +6,7 @@
 #include "attributes.h"
 #include "regloss.h"
 #include "vae_finish.h"
+#include "losses.h"
 
 namespace arvae {
 
@@ -465,7 +466,7 @@ VaeFinishArgs vae_finish_args(const float *rec_partial, int nb, int64_t batch, i
     return p;
 }
 
-int vae_finish_launch(const VaeFinishArgs &p, hipStream_t s) {
+static int vae_finish_launch(const VaeFinishArgs &p, hipStream_t s) {
     ARVAE_LAUNCH(vae_finish_kernel, dim3(1), dim3(1024), 0, s, p);
     return check_launch("image_vae_forward(finish)");
 }

@@ -20,10 +20,10 @@
 #include "midprep.h"
 #include "midcluster.h"
 #include "conv32_common.h"
+#include "conv32.h"
+#include "midblock.h"
 
 namespace arvae {
-
-int conv32_amax(const float *x, int64_t count, unsigned *out, hipStream_t s);      // conv32.hip
 
 
 constexpr int MID_T = 512;           // threads per workgroup

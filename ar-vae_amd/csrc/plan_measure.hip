@@ -14,28 +14,11 @@
 #include "regloss.h"
 #include "gru_mask.h"
 #include "attributes.h"
+#include "rng.h"
+#include "losses.h"
+#include "sequence.h"
 
 namespace arvae {
-
-// loss-term pieces (losses.hip)
-int token_recon_partials(const float *weights, const int64_t *score, int batch, int beats, int tpb, int32_t vocab, float *ws,
-                         float *dweights, hipStream_t s, int *nb_out, const AttrArgs *attr);
-int token_recon_blocks(int64_t rows);
-bool embed_fwd_with_beat(const int64_t *idx, const float *table, int32_t batch, int32_t steps, int32_t dim, int32_t vocab, int32_t time_major,
-                         float *out, const BeatInput &beat, hipStream_t s, int *rc);
-// arvae_tick_gi_fwd that also copies the tokens it reads (sequence.hip)
-int tick_gi_fwd_copy(const float *g_small, const int64_t *tokens, const float *bias, int32_t batch, int32_t beats, int32_t ticks_per_beat,
-                     int32_t vocab, int32_t cols, float *gi, int64_t *copy_to, hipStream_t s);
-// several draws as one launch (rng.hip)
-int philox_draws(int n_draws, const int *kind, void *const *out, const int64_t *count, const float *keep_prob, const uint32_t *offset,
-                 uint64_t seed, uint32_t step, const uint32_t *dev_step, hipStream_t s);
-int reg_partials(const float *z_rows, const float *lab_rows, int64_t n_rows, const float *z_cols, const float *lab_cols,
-                 int64_t n_cols, int64_t ldz, int64_t ldl, const RegDims &rd, int32_t r, float delta, float *ws,
-                 hipStream_t s, const struct VaeFinishArgs *park = nullptr, struct VaeFinishArgs *park_dst = nullptr);
-int vae_finish(const float *rec_partial, int nb, int64_t batch, int64_t pix, const float *mu, const float *sigma,
-               int64_t zdim, float beta, const float *cap, const float *reg_ws, int64_t n_cols, int64_t ldz,
-               const int32_t *dims, int32_t r, float gamma, float delta, float reg_scale, float *dz, float *rec_out,
-               float *kld_out, float *reg_out, float *scalars, hipStream_t s, int64_t rec_rows = 0);
 
 static inline int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
 

@@ -51,4 +51,8 @@ __device__ __forceinline__ float rng_normal(const RngStream &s, uint64_t index) 
     return r * cosf(6.283185307179586f * rng_unit(b.y));
 }
 
+// several draws that share seed, step and device step as one launch (rng.hip): kind 0 standard normals (float), 1 keep-mask bytes
+int philox_draws(int n_draws, const int *kind, void *const *out, const int64_t *count, const float *keep_prob, const uint32_t *offset,
+                 uint64_t seed, uint32_t step, const uint32_t *dev_step, hipStream_t s);
+
 }  // namespace arvae

@@ -7,6 +7,7 @@
 //     r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r * gh_n);  h' = (1-z)*n + z*h
 #include "common.h"
 #include "attributes.h"
+#include "sequence.h"
 
 namespace arvae {
 

@@ -251,3 +251,29 @@ def test_measure_executor_descriptor_without_gpu(lib):
     # torch's parameters() order does not put the pairs side by side: the trainer then keeps the per-layer path
     other = FlatAdam(model.parameters(), lr=1e-4)
     assert 'adjacent' in FusedMeasureVAE.supports(model, other, ())
+
+
+def test_image_executor_workspace_layout_without_gpu(lib):
+    """the workspace the whole-model image executor lays out (csrc/plan.hip make_layout) for the two image models, from the
+    descriptor FusedImageVAE builds over a FlatAdam arena on the CPU: every buffer's offset -- and with it every alignment the
+    kernels see -- follows from the order and the sizes of the layout's takes, and the total pins them.  The figures are those of
+    a model without regularised dimensions; they do not depend on n_cols or on the device.  The regulariser's slot is the one
+    part that grows with n_reg: arvae_reg_loss_ws_floats(batch, max(n_reg, 1)) = 2 * batch * max(n_reg, 1) floats."""
+    from arvae_amd.fused import FusedImageVAE
+    from arvae_amd.image_vae import DspritesVAE, MnistVAE
+    from arvae_amd.optim import FlatAdam
+    expected = {DspritesVAE: {8: 8047500, 64: 37029948, 500: 157993284, 512: 161738172},
+                MnistVAE: {8: 10537440, 1000: 402855968, 1024: 412441040}}
+    for cls, sizes in expected.items():
+        torch.manual_seed(0)
+        model = cls()
+        for reg_dims in ((), (1,), (1, 2, 3, 4, 5), (1, 2, 3, 4, 5, 6)):
+            fused = FusedImageVAE(model, FlatAdam(model.parameters(), lr=1e-4), reg_dims, 4.0, 10.0, 1.0, 'bernoulli')
+            d = fused.descriptor()
+            r = max(len(reg_dims), 1)
+            for batch, floats in sizes.items():
+                assert (2 * batch) % 4 == 0                                       # (the slot is a whole number of 4-float units)
+                for n_cols in (0, -2, 4 * batch):
+                    got = lib.arvae_image_vae_ws_floats(ctypes.byref(d), batch, n_cols)
+                    assert got == floats + 2 * batch * (r - 1), (cls.__name__, batch, reg_dims, n_cols)
+        assert lib.arvae_image_vae_ws_floats(ctypes.byref(d), 0, 0) == -1 and lib.arvae_image_vae_ws_floats(None, 8, 0) == -1
