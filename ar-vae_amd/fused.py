@@ -59,18 +59,55 @@ class DeviceStatusError(RuntimeError):
         self.skipped = int(skipped)
 
 
-class FusedImageVAE:
-    """Descriptor + workspace cache binding a MnistVAE/DspritesVAE to a FlatAdam arena."""
+class _ArenaBound:
+    """What both executors' bindings share (FusedImageVAE here, fused_measure.FusedMeasureVAE): a model bound to a FlatAdam
+    arena, its cached descriptor and the workspace it lends to the pass in flight.  A binding adds descriptor() and
+    _ws_floats(batch), the library call that reports the workspace size in floats."""
 
-    def __init__(self, model, optimizer, reg_dims, beta, gamma, delta, dec_dist):
+    def __init__(self, model, optimizer, reg_dims, beta, gamma, delta):
         self.model, self.optimizer = model, optimizer
         self.reg_dims = tuple(int(d) for d in reg_dims)
         self.beta, self.gamma, self.delta = float(beta), float(gamma), float(delta)
-        self.dist = ops.RECON_DIST[dec_dist]
         self._desc = None
         self._arena_ptr = None
         self._ws = {}
         self._ws_owner = None
+
+    def _offset(self, param):
+        opt = self.optimizer
+        for p, off in zip(opt.params, opt._offsets):
+            if p is param:
+                return off
+        raise KeyError('parameter is not managed by the optimizer arena')
+
+    def workspace(self, batch, device, ctx=None):
+        """The activation workspace of one forward pass.  One batch-sized buffer is cached and lent to the pass that is in
+        flight; a forward that starts while an earlier pass still waits for its backward (two losses summed, a validation
+        forward in between, another batch size) gets a buffer of its own, so no pass can overwrite another's activations.
+        The buffer travels on the autograd ctx: backward reads exactly what its forward wrote."""
+        key = (batch, str(device))
+        owner = self._ws_owner() if self._ws_owner is not None else None
+        busy = owner is not None and not getattr(owner, 'ws_released', True)
+        ws = self._ws.get(key)
+        if ws is None or busy:
+            n = self._ws_floats(batch)
+            fresh = torch.empty(n, device=device, dtype=torch.float32)
+            if busy:
+                return fresh                          # not cached: it lives and dies with this pass
+            ws = fresh
+            self._ws = {key: ws}                      # keep one (batch-sized) workspace alive
+        if ctx is not None:
+            ctx.ws_released = False
+            self._ws_owner = weakref.ref(ctx)
+        return ws
+
+
+class FusedImageVAE(_ArenaBound):
+    """Descriptor + workspace cache binding a MnistVAE/DspritesVAE to a FlatAdam arena."""
+
+    def __init__(self, model, optimizer, reg_dims, beta, gamma, delta, dec_dist):
+        super().__init__(model, optimizer, reg_dims, beta, gamma, delta)
+        self.dist = ops.RECON_DIST[dec_dist]
         self._overlap = None
         self._buckets = None
         self.no_cluster = False          # set once a hand-off has given up: the latent block stays on the row kernels
@@ -132,13 +169,6 @@ class FusedImageVAE:
         self._buckets = (dec, lin, rest)
         return self._buckets
 
-    def _offset(self, param):
-        opt = self.optimizer
-        for p, off in zip(opt.params, opt._offsets):
-            if p is param:
-                return off
-        raise KeyError('parameter is not managed by the optimizer arena')
-
     def descriptor(self):
         arena = self.optimizer.ensure_arena()
         if self._desc is not None and self._arena_ptr == arena.data_ptr():
@@ -183,28 +213,11 @@ class FusedImageVAE:
         self._desc, self._arena_ptr = d, arena.data_ptr()
         return d
 
-    def workspace(self, batch, device, ctx=None):
-        """The activation workspace of one forward pass.  One batch-sized buffer is cached and lent to the pass that is in
-        flight; a forward that starts while an earlier pass still waits for its backward (two losses summed, a validation
-        forward in between, another batch size) gets a buffer of its own, so no pass can overwrite another's activations.
-        The buffer travels on the autograd ctx: backward reads exactly what its forward wrote."""
-        key = (batch, str(device))
-        owner = self._ws_owner() if self._ws_owner is not None else None
-        busy = owner is not None and not getattr(owner, 'ws_released', True)
-        ws = self._ws.get(key)
-        if ws is None or busy:
-            n = _lib.load().arvae_image_vae_ws_floats(ctypes.byref(self.descriptor()), batch, 0)
-            if n < 0:
-                _lib.check(-1, 'image_vae_ws_floats')
-            fresh = torch.empty(n, device=device, dtype=torch.float32)
-            if busy:
-                return fresh                          # not cached: it lives and dies with this pass
-            ws = fresh
-            self._ws = {key: ws}                      # keep one (batch-sized) workspace alive
-        if ctx is not None:
-            ctx.ws_released = False
-            self._ws_owner = weakref.ref(ctx)
-        return ws
+    def _ws_floats(self, batch):
+        n = _lib.load().arvae_image_vae_ws_floats(ctypes.byref(self.descriptor()), batch, 0)
+        if n < 0:
+            _lib.check(-1, 'image_vae_ws_floats')
+        return n
 
     def run(self, x, labels, eps, masks, capacity, external_reg=False, reg_scale=1.0, dp=None, capacity_nonzero=False,
             draw_eps=False, defer_finish=False):

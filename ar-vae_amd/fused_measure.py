@@ -8,7 +8,6 @@ reference's class API (MeasureVAE.forward returns the weights), data parallelism
 for; tests/test_measure_executor.py holds the two paths against each other.
 """
 import ctypes
-import weakref
 
 import torch
 from torch.autograd import Function
@@ -16,21 +15,14 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import MeasureTables, MeasureVaeDesc
+from .fused import ACC, DIST, KL, LOSS, NSCALARS, RECON, REG, _ArenaBound  # noqa: F401  (the pass's scalar slots: one list)
 
-LOSS, RECON, DIST, REG, ACC, KL, NSCALARS = 0, 1, 2, 3, 4, 5, 8
 
-
-class FusedMeasureVAE:
-    """Descriptor + workspace cache binding a MeasureVAE to a FlatAdam arena."""
+class FusedMeasureVAE(_ArenaBound):
+    """Descriptor + workspace cache binding a MeasureVAE to a FlatAdam arena (_offset and workspace(): fused._ArenaBound)."""
 
     def __init__(self, model, optimizer, reg_dims, beta, gamma, delta):
-        self.model, self.optimizer = model, optimizer
-        self.reg_dims = tuple(int(d) for d in reg_dims)
-        self.beta, self.gamma, self.delta = float(beta), float(gamma), float(delta)
-        self._desc = None
-        self._arena_ptr = None
-        self._ws = {}
-        self._ws_owner = None
+        super().__init__(model, optimizer, reg_dims, beta, gamma, delta)
         self._tables = None
 
     # -- can the executor run this model? -------------------------------------------------------------------------
@@ -71,13 +63,6 @@ class FusedMeasureVAE:
         m = self.model
         return (m.num_notes + 1) * 1024 + (m.num_ticks_per_measure * batch + 15) // 16 * 8 <= 65536
 
-    def _offset(self, param):
-        opt = self.optimizer
-        for p, off in zip(opt.params, opt._offsets):
-            if p is param:
-                return off
-        raise KeyError('parameter is not managed by the optimizer arena')
-
     def descriptor(self):
         arena = self.optimizer.ensure_arena()
         if self._desc is not None and self._arena_ptr == arena.data_ptr():
@@ -115,26 +100,11 @@ class FusedMeasureVAE:
         self._desc, self._arena_ptr = d, arena.data_ptr()
         return d
 
-    def workspace(self, batch, device, ctx=None):
-        """The activation workspace of one forward pass: one batch-sized buffer is cached and lent to the pass in flight; a
-        forward that starts while an earlier pass still waits for its backward gets a buffer of its own (fused.FusedImageVAE)."""
-        key = (batch, str(device))
-        owner = self._ws_owner() if self._ws_owner is not None else None
-        busy = owner is not None and not getattr(owner, 'ws_released', True)
-        ws = self._ws.get(key)
-        if ws is None or busy:
-            n = _lib.load().arvae_measure_vae_ws_floats(ctypes.byref(self.descriptor()), batch)
-            if n < 0:
-                _lib.check(-1, 'measure_vae_ws_floats')
-            fresh = torch.empty(n, device=device, dtype=torch.float32)
-            if busy:
-                return fresh
-            ws = fresh
-            self._ws = {key: ws}
-        if ctx is not None:
-            ctx.ws_released = False
-            self._ws_owner = weakref.ref(ctx)
-        return ws
+    def _ws_floats(self, batch):
+        n = _lib.load().arvae_measure_vae_ws_floats(ctypes.byref(self.descriptor()), batch)
+        if n < 0:
+            _lib.check(-1, 'measure_vae_ws_floats')
+        return n
 
     def tables(self, trainer, device):
         """arvae_measure_tables_t over the trainer's per-vocabulary attribute tables (kept alive here)"""

@@ -239,6 +239,16 @@ def test_measure_executor_descriptor_without_gpu(lib):
     assert (d.vocab, d.emb, d.enc_hidden, d.dec_hidden, d.zdim, d.steps, d.beats, d.ticks_per_beat, d.n_reg) == (35, 10, 128, 128, 32, 24, 4, 6, 4)
     ws256, ws8 = lib.arvae_measure_vae_ws_floats(ctypes.byref(d), 256), lib.arvae_measure_vae_ws_floats(ctypes.byref(d), 8)
     assert ws256 > ws8 > 0 and ws256 % 4 == 0 and ws256 * 4 < 2 ** 31          # (some 400 MB at the benchmark batch)
+    # the layout csrc/plan_measure.hip carves (the order and the sizes of its takes fix every offset; the total pins them) depends on
+    # the descriptor's sizes and n_reg alone: the shapes tests/test_measure_executor.py steps through, and the benchmark's at B = 8
+    pinned = {(128, 32, 256): (109364252, 109365788), (128, 32, 21): (8001980, 8002104), (128, 32, 8): (3647212, 3647260),
+              (64, 16, 5): (1274060, 1274088), (64, 32, 37): (6679324, 6679544)}
+    for (hid, zdim, b), floats in pinned.items():
+        for n_reg, want in zip((0, 4), floats):
+            d.enc_hidden, d.dec_hidden, d.zdim, d.n_reg = hid, hid, zdim, n_reg
+            assert lib.arvae_measure_vae_ws_floats(ctypes.byref(d), b) == want, (hid, zdim, b, n_reg)
+    d.enc_hidden, d.dec_hidden, d.zdim, d.n_reg = 128, 128, 32, 4
+    assert lib.arvae_measure_vae_ws_floats(ctypes.byref(d), 256) == ws256
     assert lib.arvae_measure_vae_ws_floats(ctypes.byref(d), 0) == -1 and lib.arvae_measure_vae_ws_floats(None, 8) == -1
     assert lib.arvae_measure_vae_ws_floats(ctypes.byref(d), 4096) == -1 and b'segment sums' in lib.arvae_last_error_string()
     assert lib.arvae_measure_vae_forward(ctypes.byref(d), 8, None, None, None, None, None, 1, None, None, None, None, None, None, None, None,
