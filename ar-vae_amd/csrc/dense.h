@@ -70,6 +70,9 @@ int wide_wgrad(const WideWgradJob *jobs, int count, hipStream_t s);
 int wide_gemm_slices(int M, int N, int K);
 bool wide_gemm_fits(const WideGemm &g, int slices);
 int wide_gemm(WideGemm g, int slices, bool partial, hipStream_t s);
+// out[count] = the sum of `slices` partial results of a split wide_gemm, in slice order (the per-layer entry point; the latent
+// block's kernels sum them in their prologue)
+int wide_partial_sum(const float *ws, int64_t slice_floats, int slices, float *out, hipStream_t s);
 
 bool dense_fits(const arvae_link_t *l);
 int dense_fwd(const arvae_link_t *l, const float *x, const float *w, const float *bias, int act, float *y, hipStream_t s);

@@ -1256,6 +1256,13 @@ int dense_wgrad_slab_flush(DenseWgradBatch *b, SlabReduceBatch *r, hipStream_t s
     return check_launch("pair(dense_wgrad_batch + slab_reduce_batch)");
 }
 
+int wide_partial_sum(const float *ws, int64_t slice_floats, int slices, float *out, hipStream_t s) {
+    if (hipMemsetAsync(out, 0, sizeof(float) * slice_floats, s) != hipSuccess) return fail(ARVAE_E_LAUNCH, "wide_partial_sum: memset");
+    ARVAE_LAUNCH(dense_split_reduce_kernel, dim3((unsigned)((slice_floats * 4 + 255) / 256)), dim3(256), 0, s, ws, slice_floats, slices,
+                 slice_floats, 0, out, static_cast<float *>(nullptr));
+    return check_launch("wide_partial_sum");
+}
+
 bool dense_fits(const arvae_link_t *l) {
     return l->hh == 1 && l->hw == 1 && l->lh == 1 && l->lw == 1 && l->kh == 1 && l->kw == 1;
 }

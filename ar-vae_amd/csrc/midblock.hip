@@ -1048,6 +1048,97 @@ int mid_wide_wgrad(const arvae_image_vae_t *m, int batch, const float *params, f
 
 }  // namespace arvae
 
+// ---- the wide layers' tile GEMMs as per-layer calls ---------------------------------------------------------------------
+// What mid_forward / mid_backward / mid_wide_wgrad launch for a wide Linear layer, one product at a time and with nothing of the
+// latent block around it: the weight is split into its bf16 planes by mid_prep_kernel, the operand the row kernels would leave
+// pre-split is split the same way, and the product runs in the form the block uses for that side of the layer -- the long
+// reduction (the 2888 side) as fp32 A with a split reduction, the short one as planes A in one pass.  For tests and profiling
+// of wide_gemm_x3_kernel / wide_wgrad_x3_kernel against a reference of the same product.
+using namespace arvae;
+
+static int64_t wide_w_plane_floats(const arvae_link_t *l) {
+    const int64_t n_pad = (l->clo + 31) / 32 * 32, kb_pad = (l->chi + 31) / 32 * 32;
+    return (3 * n_pad * kb_pad / 2 + 3) / 4 * 4;
+}
+
+extern "C" int64_t arvae_wide_dense_ws_floats(const arvae_link_t *l) {
+    if (l == nullptr || l->n <= 0) return 0;
+    const int64_t narrow = l->chi < l->clo ? l->chi : l->clo;
+    // weight planes | permuted bias | the narrow operand's planes | partial sums of a split reduction
+    return wide_w_plane_floats(l) + (l->clo + 3) / 4 * 4 + mid_wide_plane_floats(l->n, narrow) + (int64_t)WIDE_MAX_SLICES * l->n * narrow;
+}
+
+// mode 0: out[n][clo] = x . W'^T + bias    mode 1: out[n][chi] = g . W'    mode 2: dw += g^T x, dbias += column sums of g
+//   (x [n][chi], g [n][clo], out: channels-last memory order under the link's permutations; w [clo][chi] and dw in feature order)
+extern "C" int arvae_wide_dense(const arvae_link_t *l, int32_t mode, const float *x, const float *g, const float *w, const float *bias,
+                                float *out, float *dw, float *dbias, float *ws, arvae_stream_t stream) {
+    ARVAE_REQUIRE(l != nullptr && dense_fits(l) && l->n > 0, "wide_dense: a Linear link with a batch");
+    ARVAE_REQUIRE(mode >= 0 && mode <= 2 && w != nullptr && ws != nullptr && (mode == 1 || x != nullptr) && (mode == 0 || g != nullptr) &&
+                  (mode == 2 ? dw != nullptr : out != nullptr), "wide_dense: null pointer / bad mode");
+    const int rows = l->n, k = l->chi, n = l->clo, narrow = k < n ? k : n;
+    ARVAE_REQUIRE(k % 4 == 0 && n % 4 == 0 && narrow % RG_R == 0 && (k >= MID_WIDE_MIN || n >= MID_WIDE_MIN),
+                  "wide_dense: one side at least %d wide, the other a multiple of %d", MID_WIDE_MIN, RG_R);
+    hipStream_t s = as_stream(stream);
+    const int n_pad = (n + 31) / 32 * 32, kb_pad = (k + 31) / 32 * 32;
+    unsigned short *w_planes = reinterpret_cast<unsigned short *>(ws);
+    float *pbias = ws + wide_w_plane_floats(l);
+    unsigned short *a_planes = reinterpret_cast<unsigned short *>(pbias + (n + 3) / 4 * 4);
+    float *partial = reinterpret_cast<float *>(a_planes) + mid_wide_plane_floats(rows, narrow);
+    // which activation is the narrow one (the one the block's row kernels leave as planes)
+    const bool k_long = k > n;
+    const float *narrow_src = mode == 0 ? (k_long ? nullptr : x) : mode == 1 ? (k_long ? g : nullptr) : (k_long ? g : x);
+    MidPrepArgs pa{};
+    auto add = [&](const MidPrepJob &j, int64_t pairs) {
+        int b = (int)((pairs + 1023) / 1024);
+        b = b > 256 ? 256 : (b < 1 ? 1 : b);
+        pa.job[pa.count] = j;
+        pa.blk_end[pa.count] = (pa.count ? pa.blk_end[pa.count - 1] : 0) + b;
+        ++pa.count;
+    };
+    if (mode != 2) {
+        MidPrepJob j{};
+        j.w = w; j.b = mode == 0 ? bias : nullptr; j.bias = (mode == 0 && bias != nullptr) ? pbias : nullptr;
+        j.k = k; j.n = n; j.kb = (k + 3) / 4 * 4;
+        j.kp = Perm{l->hi_perm_c, l->hi_perm_hw}; j.np = Perm{l->lo_perm_c, l->lo_perm_hw};
+        j.planes = w_planes; j.n_pad = n_pad; j.kb_pad = kb_pad;
+        add(j, (int64_t)n_pad * kb_pad / 2);
+    }
+    if (narrow_src != nullptr) {                                 // [rows][narrow] -> planes [3][narrow / 32][rows][32]
+        MidPrepJob j{};
+        j.w = narrow_src; j.k = narrow; j.n = rows; j.kb = narrow;
+        j.planes = a_planes; j.n_pad = rows; j.kb_pad = narrow;
+        add(j, (int64_t)rows * narrow / 2);
+    }
+    ARVAE_LAUNCH(mid_prep_kernel, dim3(mid_prep_blocks(pa)), dim3(256), 0, s, pa);
+    if (int rc = check_launch("mid_prep_kernel")) return rc;
+    if (mode == 2) {
+        WideWgradJob j{};
+        if (k_long) { j.a = a_planes; j.lda = rows; j.a_pstride = (int64_t)rows * n; j.a_planes = 1; j.b = x; j.ldb = k; }
+        else { j.a = g; j.lda = n; j.b = a_planes; j.ldb = rows; j.b_pstride = (int64_t)rows * k; j.b_planes = 1; }
+        j.P = n; j.Q = k; j.R = rows;
+        j.dw = dw; j.ldw = k; j.dbias = dbias;
+        j.p_perm = Perm{l->lo_perm_c, l->lo_perm_hw}; j.q_perm = Perm{l->hi_perm_c, l->hi_perm_hw};
+        ARVAE_REQUIRE(wide_wgrad_fits(j), "wide_dense: the weight gradient does not fit the tile kernel (alignment / size)");
+        return wide_wgrad(&j, 1, s);
+    }
+    WideGemm q{};
+    q.b = w_planes; q.ldb = n_pad; q.b_pstride = (int64_t)n_pad * kb_pad; q.b_planes = 1; q.b_krows = mode;
+    q.M = rows; q.N = mode == 0 ? n : k; q.K = mode == 0 ? k : n;
+    q.ldo = q.N;
+    if (narrow_src != nullptr) {                                 // planes A, one pass (mid_forward's F2, mid_backward's B2)
+        q.a = a_planes; q.lda = rows; q.a_pstride = (int64_t)rows * narrow; q.a_planes = 1;
+        q.out = out; q.bias = (mode == 0 && bias != nullptr) ? pbias : nullptr; q.act = ARVAE_ACT_NONE;
+        return wide_gemm(q, 1, false, s);
+    }
+    // fp32 A, split reduction (F1 / B1): the partial sums are added here instead of in the row kernel's prologue; no bias
+    ARVAE_REQUIRE(bias == nullptr, "wide_dense: the split-reduction form leaves the bias to its consumer");
+    q.a = mode == 0 ? x : g; q.lda = q.K;
+    q.out = partial; q.slice_floats = (int64_t)rows * q.N;
+    const int slices = wide_gemm_slices(rows, q.N, q.K);
+    if (int rc = wide_gemm(q, slices, true, s)) return rc;
+    return wide_partial_sum(partial, q.slice_floats, slices, out, s);
+}
+
 #ifdef MID_STAMPS
 extern "C" int arvae_debug_mid_stamps(unsigned long long *out, int count) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_mid_stamps), sizeof(unsigned long long) * count);

@@ -182,6 +182,19 @@ def channel_sum(op, rows, channels, perm, out):
     return out
 
 
+def wide_dense(link: Link, n, mode, w, x=None, g=None, bias=None, dw=None, dbias=None):
+    """One product of a wide Linear layer on the latent block's three-term bf16 tile kernels (csrc/dense.hip wide_gemm_x3_kernel /
+    wide_wgrad_x3_kernel), outside the whole-model executor.  mode 0: x W^T (+ bias), 1: g W, 2: dw += g^T x, dbias += sums of g."""
+    lib = _lib.load()
+    d = link.desc(n)
+    ws = torch.empty(lib.arvae_wide_dense_ws_floats(ctypes.byref(d)), device=w.device, dtype=torch.float32)
+    out = None if mode == 2 else torch.empty((n, link.clo if mode == 0 else link.chi), device=w.device, dtype=torch.float32)
+    with _timed('wide_dense', 2.0 * n * link.chi * link.clo, 0.0):
+        _lib.check(lib.arvae_wide_dense(ctypes.byref(d), mode, _ptr(x), _ptr(g), _ptr(w), _ptr(bias), _ptr(out), _ptr(dw), _ptr(dbias),
+                                        _ptr(ws), _stream()), 'wide_dense')
+    return dw if mode == 2 else out
+
+
 LONG_BATCH_ROWS = 2048      # csrc/dense.h DENSE_SPLIT_MIN_ROWS: Linear layers over this many rows run on the rows-GEMM kernels
 
 

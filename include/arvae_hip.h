@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 12  /* 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 13  /* 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -143,6 +143,16 @@ int arvae_dense_wgrad_batch(const arvae_dense_wgrad_job_t *jobs, int32_t njobs, 
 
 /* out[i] = value of the operand with act'(y) and the keep-mask folded in: a plain copy of a gradient operand. */
 int arvae_operand_apply(const arvae_operand_t *g, int64_t count, float *out, arvae_stream_t stream);
+
+/* One product of a WIDE nn.Linear layer (one side >= 1024 features, the other a multiple of 32; link->n rows) on the three-term
+ * bf16 tile kernels the whole-model executor's latent block uses for it, with nothing of the block around it (tests, profiling):
+ *   mode 0: out[n][clo] = x . W^T (+ bias)    mode 1: out[n][chi] = g . W    mode 2: dw += g^T x, dbias += column sums of g (or NULL)
+ * x [n][chi], g [n][clo], out in channels-last memory order under the link's permutations; w [clo][chi], dw in feature order.
+ * The product whose reduction runs over the wide side is a split reduction whose consumer adds the bias: bias must be NULL there.
+ * ws: arvae_wide_dense_ws_floats() floats, 16-byte aligned. */
+int64_t arvae_wide_dense_ws_floats(const arvae_link_t *link);
+int arvae_wide_dense(const arvae_link_t *link, int32_t mode, const float *x, const float *g, const float *w, const float *bias,
+                     float *out, float *dw, float *dbias, float *ws, arvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Latent head.  Replaces z_dist = Normal(mu, exp(log_std)); z = z_dist.rsample()

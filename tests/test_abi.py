@@ -108,6 +108,8 @@ def test_argument_validation_without_gpu(lib):
     assert lib.arvae_embed_bwd_ws_floats(256, 24, 10, 35) == (256 * 24 // 64) * 35 * 10
     assert lib.arvae_dense_wgrad_batch((DenseWgradJob * 1)(), 1, None) == -1
     assert lib.arvae_operand_apply(None, 4, None, None) == -1
+    assert lib.arvae_wide_dense(None, 0, None, None, None, None, None, None, None, None, None) == -1
+    assert lib.arvae_wide_dense_ws_floats(None) == 0
 
 
 def test_cpu_tensors_are_refused():
