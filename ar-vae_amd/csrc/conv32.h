@@ -1,5 +1,5 @@
 // Host entry points of the specialised 32-channel k4 / s2 / p1 conv kernels (conv32.hip).  Operands are plain fp32 tensors that
-// come with the AMAX array of their values and the layer's prepared weights (conv32_common.h); a per-layer caller that has
+// come with the AMAX array of their values and the layer's prepared weights (amax.h, conv32_common.h); a per-layer caller that has
 // neither makes them in its workspace (conv32_scratch_floats, conv32_weight_prep, conv32_amax).
 #pragma once
 #include "common.h"

@@ -3,7 +3,7 @@
 // carry 85 % of the training step's FLOPs.  Same math and C-ABI as the
 // generic gather-GEMM (link_gemm.hip); arvae_link_down/up/wgrad dispatch here when the geometry fits.
 //
-// The kernels run the fp16 MFMA on scaled two-term operands (conv32_common.h): every fp32 operand is scaled by its tensor's
+// The kernels run the fp16 MFMA on scaled two-term operands (splitmath.h): every fp32 operand is scaled by its tensor's
 // power-of-two scale and split into two fp16 terms when it enters LDS (weights: once per step, prep32.h) and every multiply-add
 // is three partial products on v_mfma_f32_32x32x16_f16 with fp32 accumulation: the result is within one fp32 rounding of an
 // fp32 FMA chain's at a fifth of the fp32 MFMA's cycles, and the fp16 MFMA leaves the vector ALU free for the splitting.
@@ -103,7 +103,7 @@ struct PatchLoader {
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) issue_slot(it);
     }
-    // Split commit: every fp32 value x becomes the fp16 pair (h, l) of s x (split_pair_h2); two planes of PLANE_DW dwords, a
+    // Split commit: every fp32 value x becomes the fp16 pair (h, l) of s x (split2); two planes of PLANE_DW dwords, a
     // pixel is PITCH dwords per plane (32 channels x 2 bytes + pad), channel pair (2i, 2i+1) shares a dword, even channel in the
     // low half.  BIAS_SUM: also accumulate the pixels this tile owns (not the halo) per channel chunk q = threadIdx.x & 7.
     static constexpr int PLANE_DW = T::TI * PR * PC * PSB;
@@ -121,8 +121,8 @@ struct PatchLoader {
             if (idx < SLOTS) {
                 const int q = idx & 7, pix = idx >> 3;
                 uint2 hv, lv;
-                split_pair_h2(v.x, v.y, sc, hv.x, lv.x);
-                split_pair_h2(v.z, v.w, sc, hv.y, lv.y);
+                split2(v.x, v.y, sc, hv.x, lv.x);
+                split2(v.z, v.w, sc, hv.y, lv.y);
                 *reinterpret_cast<uint2 *>(planes + pix * PITCH + q * 2) = hv;
                 *reinterpret_cast<uint2 *>(planes + PLANE_P + pix * PITCH + q * 2) = lv;
                 if (BIAS_SUM) {
@@ -143,8 +143,8 @@ struct PatchLoader {
             if (idx < SLOTS) {
                 const int q = idx & 7, pix = idx >> 3;
                 uint2 hv, lv;
-                split_pair_h2(r[it].x, r[it].y, sc, hv.x, lv.x);
-                split_pair_h2(r[it].z, r[it].w, sc, hv.y, lv.y);
+                split2(r[it].x, r[it].y, sc, hv.x, lv.x);
+                split2(r[it].z, r[it].w, sc, hv.y, lv.y);
                 unsigned *d = buf + pix * PSB2 + q * 2;
                 *reinterpret_cast<uint2 *>(d) = hv;
                 *reinterpret_cast<uint2 *>(d + 16) = lv;
@@ -231,10 +231,6 @@ __device__ __forceinline__ void load_bias4(const float *bias, int half, float4 (
 #pragma unroll
     for (int g = 0; g < 4; ++g)
         b4[g] = bias != nullptr ? *reinterpret_cast<const float4 *>(bias + 8 * g + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-__device__ __forceinline__ f16x8 lds_f16x8(const unsigned *p) {
-    return __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4v *>(p));
 }
 
 __global__ __launch_bounds__(256) void conv32_weight_prep_kernel(PrepArgs p) { conv32_prep_block(p, blockIdx.x); }
@@ -335,7 +331,7 @@ __device__ __forceinline__ void down32s_body(const float *__restrict__ hi, Ep32 
         for (int kx = 0; kx < 4; ++kx)
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
-                const f16x8 ah = lds_f16x8(ldsw + aoff + kx * PSB2 + cc * 8), al = lds_f16x8(ldsw + aoff + kx * PSB2 + cc * 8 + 16);
+                const f16x8 ah = lds_x8<f16x8>(ldsw + aoff + kx * PSB2 + cc * 8), al = lds_x8<f16x8>(ldsw + aoff + kx * PSB2 + cc * 8 + 16);
                 MFMA_H(acc, w2[kx][cc][1], ah);                  // smallest partial products first
                 MFMA_H(acc, w2[kx][cc][0], al);
                 MFMA_H(acc, w2[kx][cc][0], ah);
@@ -370,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void down32s_kernel(const float *__restrict
 // behind the wave's previous MFMA.  Gate values are fetched one tile ahead into registers.
 
 // ================================================================================================
-// Up on the fp16 MFMA with scaled two-term operands (conv32_common.h): 3 x 32 cycles per 16 channels.  64 weights x 2 terms
+// Up on the fp16 MFMA with scaled two-term operands (splitmath.h): 3 x 32 cycles per 16 channels.  64 weights x 2 terms
 // live in 64 registers (prepared per step, prep32.h); staggered epilogue and gating as described above.
 constexpr int UP_ISSUE_STEPS = 4;
 template <int LO, int MODE, int PX = 128>
@@ -479,7 +475,7 @@ __device__ __forceinline__ void up32x_body(const float *__restrict__ lo, Ep32 ep
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int t = 0; t < 2; ++t) a[0][mt][t] = lds_f16x8(ldsw + t * PLANE + aoff[mt]);
+            for (int t = 0; t < 2; ++t) a[0][mt][t] = lds_x8<f16x8>(ldsw + t * PLANE + aoff[mt]);
         static_for<0, 8>([&](auto sc_) __attribute__((always_inline)) {
             constexpr int step = decltype(sc_)::value, ty = step >> 2, tx = (step >> 1) & 1, c = step & 1;
             constexpr int cur = step & 1, nxt = cur ^ 1;
@@ -519,7 +515,7 @@ __device__ __forceinline__ void up32x_body(const float *__restrict__ lo, Ep32 ep
                 if constexpr (nstep < 8) {                       // this sub-step's share of the next step's operand reads
                     static_for<2 * sub, 2 * sub + 2>([&](auto rc_) __attribute__((always_inline)) {
                         constexpr int ri = decltype(rc_)::value, rmt = ri / 2, rt = ri % 2;
-                        a[nxt][rmt][rt] = lds_f16x8(ldsw + rt * PLANE + aoff[rmt] + ntoff);
+                        a[nxt][rmt][rt] = lds_x8<f16x8>(ldsw + rt * PLANE + aoff[rmt] + ntoff);
                     });
                 }
                 (void)nxt;
@@ -734,8 +730,8 @@ __device__ __forceinline__ void up32p_body(const float *__restrict__ lo, Ep32 ep
                         const unsigned bits = base != OOB ? gb[mt] >> (4 * g) : 0u;
                         const float v0 = (bits & 1u) ? a.x : 0.f, v1 = (bits & 2u) ? a.y : 0.f, v2 = (bits & 4u) ? a.z : 0.f, v3 = (bits & 8u) ? a.w : 0.f;
                         uint2 hv, lv;
-                        split_pair_h2(v0, v1, 0x1p-23f, hv.x, lv.x);
-                        split_pair_h2(v2, v3, 0x1p-23f, hv.y, lv.y);
+                        split2(v0, v1, 0x1p-23f, hv.x, lv.x);
+                        split2(v2, v3, 0x1p-23f, hv.y, lv.y);
                         const int vd = (4 * g + 2 * half) ^ c1_sw;                     // (an even XOR keeps the dword pair together)
                         *reinterpret_cast<uint2 *>(c1_v + rc * C1W_VP + vd) = hv;
                         *reinterpret_cast<uint2 *>(c1_v + 32 * C1W_VP + rc * C1W_VP + vd) = lv;
@@ -751,8 +747,8 @@ __device__ __forceinline__ void up32p_body(const float *__restrict__ lo, Ep32 ep
                             float4 t = c1_tap[mt][e];
                             if (X == 0) t = make_float4(0.f, t.x, t.y, t.z);
                             if (X == HI - 1) t.w = 0.f;
-                            split_pair_h2(t.x, t.y, C1W_SX, hp[2 * e], lp[2 * e]);
-                            split_pair_h2(t.z, t.w, C1W_SX, hp[2 * e + 1], lp[2 * e + 1]);
+                            split2(t.x, t.y, C1W_SX, hp[2 * e], lp[2 * e]);
+                            split2(t.z, t.w, C1W_SX, hp[2 * e + 1], lp[2 * e + 1]);
                         }
                         // (dword pairs: the XOR moves pairs, not quads)
                         *reinterpret_cast<uint2 *>(c1_x + rc * C1W_XP + ((4 * half) ^ c1_sw)) = make_uint2(hx.x, hx.y);
@@ -766,8 +762,8 @@ __device__ __forceinline__ void up32p_body(const float *__restrict__ lo, Ep32 ep
                     for (int b = 0; b < 2; ++b)
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
-                            a2[b][t] = lds_tr_f16x8(c1_v + t * 32 * C1W_VP + c1_voff[b][0], c1_v + t * 32 * C1W_VP + c1_voff[b][1]);
-                            b2[b][t] = lds_tr_f16x8(c1_x + t * 32 * C1W_XP + c1_xoff[b][0], c1_x + t * 32 * C1W_XP + c1_xoff[b][1]);
+                            a2[b][t] = lds_tr_x8<f16x8>(c1_v + t * 32 * C1W_VP + c1_voff[b][0], c1_v + t * 32 * C1W_VP + c1_voff[b][1]);
+                            b2[b][t] = lds_tr_x8<f16x8>(c1_x + t * 32 * C1W_XP + c1_xoff[b][0], c1_x + t * 32 * C1W_XP + c1_xoff[b][1]);
                         }
                     // (two accumulators: an MFMA into the result of the previous one waits for it)
                     MFMA_H(c1_acc, a2[0][1], b2[0][0]);          // smallest partial products first
@@ -873,8 +869,8 @@ __device__ __forceinline__ void up32p_body(const float *__restrict__ lo, Ep32 ep
             if (idx < SLOTS) {
                 const int q = idx & 7, pix = idx >> 3;
                 uint2 hv, lv;
-                split_pair_h2(v.x, v.y, sc_in, hv.x, lv.x);
-                split_pair_h2(v.z, v.w, sc_in, hv.y, lv.y);
+                split2(v.x, v.y, sc_in, hv.x, lv.x);
+                split2(v.z, v.w, sc_in, hv.y, lv.y);
                 *reinterpret_cast<uint2 *>(planes + pix * PSB + q * 2) = hv;
                 *reinterpret_cast<uint2 *>(planes + PLANE + pix * PSB + q * 2) = lv;
             }
@@ -922,7 +918,7 @@ __device__ __forceinline__ void up32p_body(const float *__restrict__ lo, Ep32 ep
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int t = 0; t < 2; ++t) a[0][mt][t] = lds_f16x8(ldsw + t * PLANE + aoff[mt]);
+            for (int t = 0; t < 2; ++t) a[0][mt][t] = lds_x8<f16x8>(ldsw + t * PLANE + aoff[mt]);
         static_for<0, 8>([&](auto sc_) __attribute__((always_inline)) {
             constexpr int step = decltype(sc_)::value, ty = step >> 2, tx = (step >> 1) & 1, c = step & 1;
             constexpr int cu = step & 1, nxt = cu ^ 1;
@@ -941,7 +937,7 @@ __device__ __forceinline__ void up32p_body(const float *__restrict__ lo, Ep32 ep
                 if constexpr (nstep < 8) {
                     static_for<2 * sub, 2 * sub + 2>([&](auto rc_) __attribute__((always_inline)) {
                         constexpr int ri = decltype(rc_)::value, rmt = ri / 2, rt = ri % 2;
-                        a[nxt][rmt][rt] = lds_f16x8(ldsw + rt * PLANE + aoff[rmt] + ntoff);
+                        a[nxt][rmt][rt] = lds_x8<f16x8>(ldsw + rt * PLANE + aoff[rmt] + ntoff);
                     });
                 }
                 (void)nxt;
@@ -1073,8 +1069,8 @@ __device__ __forceinline__ void wgrad32x_body(const float *__restrict__ lo, cons
         for (int it = 0; it < 2; ++it) {
             const int idx = threadIdx.x + it * 256, pix = idx >> 3, q = idx & 7;
             uint2 hv, lv;
-            split_pair_h2(lr[it].x, lr[it].y, sc_lo.s, hv.x, lv.x);
-            split_pair_h2(lr[it].z, lr[it].w, sc_lo.s, hv.y, lv.y);
+            split2(lr[it].x, lr[it].y, sc_lo.s, hv.x, lv.x);
+            split2(lr[it].z, lr[it].w, sc_lo.s, hv.y, lv.y);
             *reinterpret_cast<uint2 *>(lo_w + pix * WG_PSB_L + q * 2) = hv;
             *reinterpret_cast<uint2 *>(lo_w + LPLANE + pix * WG_PSB_L + q * 2) = lv;
             if (BIAS == 1) { bias4.x += lr[it].x; bias4.y += lr[it].y; bias4.z += lr[it].z; bias4.w += lr[it].w; }
@@ -1090,7 +1086,7 @@ __device__ __forceinline__ void wgrad32x_body(const float *__restrict__ lo, cons
             constexpr int b = decltype(bc)::value;
             f16x8 b2[2];                                         // lo values: B operand, column = clo
 #pragma unroll
-            for (int t = 0; t < 2; ++t) b2[t] = lds_tr_f16x8(lo_w + t * LPLANE + loff[b][0], lo_w + t * LPLANE + loff[b][1]);
+            for (int t = 0; t < 2; ++t) b2[t] = lds_tr_x8<f16x8>(lo_w + t * LPLANE + loff[b][0], lo_w + t * LPLANE + loff[b][1]);
             pl.template issue_step<KB, b>();
             if constexpr (b < 2) lr[b] = buf_load4(rs_lo, lo_base + b * 4096);
 #pragma unroll
@@ -1098,7 +1094,7 @@ __device__ __forceinline__ void wgrad32x_body(const float *__restrict__ lo, cons
                 f16x8 a2[2];                                     // hi values at tap (ky = wave, kx): A operand, row = chi
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
-                    a2[t] = lds_tr_f16x8(ldsw + t * PLANE + hoff[b][0] + kx * WG_PSB_H, ldsw + t * PLANE + hoff[b][1] + kx * WG_PSB_H);
+                    a2[t] = lds_tr_x8<f16x8>(ldsw + t * PLANE + hoff[b][0] + kx * WG_PSB_H, ldsw + t * PLANE + hoff[b][1] + kx * WG_PSB_H);
                 MFMA_H(acc[kx], a2[1], b2[0]);                   // smallest partial products first
                 MFMA_H(acc[kx], a2[0], b2[1]);
                 MFMA_H(acc[kx], a2[0], b2[0]);
@@ -1274,7 +1270,7 @@ static void conv32_down_ksplit(const arvae_link_t *l, const float *hi, const Ep3
     else launch_down_p_mode<8>(hi, ep, mode, l->n, s);
 }
 
-// The operands of every entry point below: plain fp32 tensors that come with the AMAX array of their values (conv32_common.h;
+// The operands of every entry point below: plain fp32 tensors that come with the AMAX array of their values (amax.h;
 // conv32_amax makes one for a tensor that has none), the layer's prepared weights (conv32_weight_prep), and -- when somebody
 // will multiply the result on the matrix pipe -- the AMAX array the result's maxima go to.
 // gate (float activation) or gate_bits (relu_bits16) select a gated epilogue; with relu, bits_out (may be null) receives

@@ -9,7 +9,7 @@ namespace arvae {
 bool conv64_fits(const arvae_link_t *l, bool up);
 int64_t conv64_ws_floats(const arvae_link_t *l);
 // lo = act(conv(hi) + bias) * mask (Conv2d forward / ConvTranspose2d data gradient) and hi = act(convT(lo) + bias) * mask.
-// amax_in / amax_out: AMAX arrays (conv32_common.h) of a plain source / of the result, or null; prepped: the layer's split
+// amax_in / amax_out: AMAX arrays (amax.h) of a plain source / of the result, or null; prepped: the layer's split
 // weights (conv64s_prep_batch on this stream, this step), or null
 int conv64_down(const arvae_link_t *l, const Operand &hi, const float *wt, const float *bias, int act, const uint8_t *mask,
                 float *lo, float *ws, hipStream_t s, const GateOp *gate, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr,

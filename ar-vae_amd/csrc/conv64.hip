@@ -1,5 +1,5 @@
 // Stride-1 convolutions between wide layers (the Morpho-MNIST 64 <-> 64 channel k4 layers, imagevae/mnist_vae.py) as
-// implicit GEMMs on the split-bf16 MFMA (x3tile.h): rows = output pixels, columns = output channels, reduction =
+// implicit GEMMs on the split-bf16 MFMA (splitmath.h): rows = output pixels, columns = output channels, reduction =
 // (tap, source channel).  The A tile is GATHERED: a thread owns two (pixel, 4-channel) slots, works out its pixel's
 // coordinates once, and per 32-channel chunk adds the tap's offset -- a coalesced 16-byte load per slot, zero where the
 // tap falls outside the source (padding).  The weights are re-ordered to [out channel][tap][source channel] by a small
@@ -13,13 +13,13 @@
 #include "diag.h"
 #include "common.h"
 #include "x3tile.h"
-#include "conv32_common.h"
+#include "amax.h"
+#include "conv32_common.h"       // raw buffer access
 #include "conv64.h"
 
 namespace arvae {
 
 constexpr int C64_TP = 64, C64_TQ = 64;
-typedef float f32x16c __attribute__((ext_vector_type(16)));
 
 struct ConvRows {
     Operand src;                 // [n][sh][sw][cs] channels-last
@@ -32,7 +32,7 @@ struct ConvRows {
     int act;
     float *out;                  // [n][oh][ow][q]
     GateOp gate;                 // data-gradient launches: result *= act'(gate.y) * 2 gate.mask at the output location
-    unsigned *amax_out;          // AMAX array of the output (conv32_common.h) or null: zeroed by the weight-prep launch in front, every
+    unsigned *amax_out;          // AMAX array of the output (amax.h) or null: zeroed by the weight-prep launch in front, every
                                  // wave folds its maximum into entry (workgroup % AMAX_N) with an integer atomic max (bit patterns of
                                  // non-negative floats order like the floats: exact, order-independent)
     const unsigned *amax_in;     // conv_rows_h2_kernel: AMAX array of the (plain) source
@@ -41,7 +41,7 @@ struct ConvRows {
 
 // 16 bytes through a buffer resource at per-lane offset + scalar offset (the scalar part is not range-checked)
 __device__ __forceinline__ float4 buf_load4s(__amdgpu_buffer_rsrc_t r, unsigned off, int soff) {
-    const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, soff, 0));
+    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, soff, 0));
     return make_float4(v.x, v.y, v.z, v.w);
 }
 // value of a gradient operand (activation derivative of the saved output, keep-mask) for 4 consecutive channels
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_rows_x3_kernel(ConvRows g) {
             vb[i] = qok[i] ? w : float4{0.f, 0.f, 0.f, 0.f};
         }
     };
-    f32x16c acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     load(0);
@@ -134,8 +134,8 @@ __global__ __launch_bounds__(256) void conv_rows_x3_kernel(ConvRows g) {
         if (chunk + 1 < chunks) load(chunk + 1);
 #pragma unroll
         for (int s = 0; s < RG_R / 16; ++s) {
-            const rg_bf16x8 ah = PlaneA::operand(As, abase, 0, s), am = PlaneA::operand(As, abase, 1, s), al = PlaneA::operand(As, abase, 2, s);
-            const rg_bf16x8 bh = PlaneB::operand(Bs, bbase, 0, s), bm = PlaneB::operand(Bs, bbase, 1, s), bl = PlaneB::operand(Bs, bbase, 2, s);
+            const bf16x8 ah = PlaneA::operand(As, abase, 0, s), am = PlaneA::operand(As, abase, 1, s), al = PlaneA::operand(As, abase, 2, s);
+            const bf16x8 bh = PlaneB::operand(Bs, bbase, 0, s), bm = PlaneB::operand(Bs, bbase, 1, s), bl = PlaneB::operand(Bs, bbase, 2, s);
             X3_MFMA6(acc, ah, am, al, bh, bm, bl);
         }
     }
@@ -187,25 +187,20 @@ __global__ __launch_bounds__(256) void conv_rows_x3_kernel(ConvRows g) {
     }
 }
 
-// The same product on the fp16 MFMA with scaled two-term operands (conv32_common.h: three partial products, two LDS planes per
+// The same product on the fp16 MFMA with scaled two-term operands (splitmath.h: three partial products, two LDS planes per
 // operand, the scales from the source's AMAX array and the weights' maximum): for PLAIN sources that come with their maxima -- the
 // 8 -> 64 products of the Morpho-MNIST step, which ran six bf16 products per multiply-add here through most of round 4.
 template <int TP> struct H2PlaneRows {          // [TP][RG_XP] fp16, reduction index contiguous; planes h | l
     static constexpr int PLANE = TP * RG_XP;
     __device__ static __forceinline__ void commit(unsigned short *lds, int idx, const float4 &v, float sc) {
-        unsigned h0, l0, h1, l1;
-        split_pair_h2(v.x, v.y, sc, h0, l0);
-        split_pair_h2(v.z, v.w, sc, h1, l1);
-        unsigned short *d = lds + (idx / (RG_R / 4)) * RG_XP + 4 * (idx % (RG_R / 4));
-        *reinterpret_cast<uint2 *>(d) = uint2{h0, h1};
-        *reinterpret_cast<uint2 *>(d + PLANE) = uint2{l0, l1};
+        store_split2_x4(lds + (idx / (RG_R / 4)) * RG_XP + 4 * (idx % (RG_R / 4)), PLANE, v, sc);
     }
     __device__ static __forceinline__ int lane_base(int w) {
         const int lane = threadIdx.x & 63;
         return (32 * w + (lane & 31)) * RG_XP + 8 * (lane >> 5);
     }
     __device__ static __forceinline__ f16x8 operand(const unsigned short *lds, int base, int t, int s) {
-        return __builtin_bit_cast(f16x8, *reinterpret_cast<const rg_i32x4 *>(lds + t * PLANE + base + 16 * s));
+        return lds_x8<f16x8>(lds + t * PLANE + base + 16 * s);
     }
 };
 
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(256) void conv_rows_h2_kernel(ConvRows g) {
             vb[i] = qok[i] ? w : float4{0.f, 0.f, 0.f, 0.f};
         }
     };
-    f32x16c acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     load(0);
@@ -339,7 +334,7 @@ __global__ __launch_bounds__(256) void conv_rows_h2_kernel(ConvRows g) {
 //   * the wave's 32 x 128 weight slice lives in registers (two terms, 64 VGPRs) for the whole launch;
 //   * a tile is 64 consecutive output pixels of an image in row-major order (94 % of the MFMA rows at 22 x 22), workgroups walk
 //     tiles persistently, four workgroups per CU hide each other's staging round trip.
-// Arithmetic: scaled two-term fp16, three products (conv32_common.h); plain sources that come with their maxima.
+// Arithmetic: scaled two-term fp16, three products (splitmath.h); plain sources that come with their maxima.
 #ifdef S8_STAMPS
 __device__ unsigned long long g_s8_stamps[8];
 #define S8STAMP(k) { const unsigned long long now_ = __builtin_readcyclecounter(); s8ph[k] += now_ - s8tc; s8tc = now_; }
@@ -347,14 +342,6 @@ __device__ unsigned long long g_s8_stamps[8];
 #define S8STAMP(k)
 #endif
 constexpr int S8_PIX = 255;                                      // staged source pixels per tile (one per thread; 255 = the zero pixel)
-__device__ __forceinline__ void s8_split8(const float (&x)[8], float sc, f16x8 &hi, f16x8 &lo) {
-    uint4 h, l;
-    split_pair_h2(x[0], x[1], sc, h.x, l.x);
-    split_pair_h2(x[2], x[3], sc, h.y, l.y);
-    split_pair_h2(x[4], x[5], sc, h.z, l.z);
-    split_pair_h2(x[6], x[7], sc, h.w, l.w);
-    hi = __builtin_bit_cast(f16x8, h); lo = __builtin_bit_cast(f16x8, l);
-}
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_s8_h2_kernel(ConvRows g, int tiles_per_img, int n_tiles) {
     __shared__ uint4 src_h[S8_PIX + 1], src_l[S8_PIX + 1];
     __shared__ __attribute__((aligned(16))) float otile[64][68];   // the tile's results, so that the epilogue is 16-byte loads and stores
@@ -373,7 +360,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const float4 a = *reinterpret_cast<const float4 *>(wsrc), b = *reinterpret_cast<const float4 *>(wsrc + 4);
         const float z = q < g.q ? 1.f : 0.f;
         const float x[8] = {a.x * z, a.y * z, a.z * z, a.w * z, b.x * z, b.y * z, b.z * z, b.w * z};
-        s8_split8(x, sc_w.s, wh[s8], wl[s8]);
+        split2_8(x, sc_w.s, wh[s8], wl[s8]);
     }
     // epilogue slot of this thread: pixel (threadIdx.x / 16) + 16 k of the tile, channels 4 (threadIdx.x % 16) ..
     const int e_px = threadIdx.x >> 4, e_c = 4 * (threadIdx.x & 15);
@@ -429,7 +416,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         if ((int)threadIdx.x < nrows * g.sw) {
             const float v[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
             f16x8 h, l;
-            s8_split8(v, sc_a.s, h, l);
+            split2_8(v, sc_a.s, h, l);
             src_h[threadIdx.x] = __builtin_bit_cast(uint4, h);
             src_l[threadIdx.x] = __builtin_bit_cast(uint4, l);
         }
@@ -453,7 +440,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const int P = P0 + 32 * wp + rc;
         const bool pok = P < opix;
         const int y = P / g.ow, x = P - y * g.ow;
-        f32x16c acc;
+        f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         // a k-step's two operand reads are requested one step ahead of its MFMAs (pinned: left to the scheduler every read was
@@ -693,7 +680,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(ConvWgrad g) {
             vb[i] = load_src4<PLAIN_HI>(g.hi, (((int64_t)img * g.hh + hy) * g.hw + hx) * g.chi + c4[i], ok);
         }
     };
-    f32x16c acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     load(pbeg);
@@ -709,8 +696,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(ConvWgrad g) {
         if (pix0 + RG_R < pend) load(pix0 + RG_R);
 #pragma unroll
         for (int s = 0; s < RG_R / 16; ++s) {
-            const rg_bf16x8 ah = Plane::operand(As, abase, 0, s), am = Plane::operand(As, abase, 1, s), al = Plane::operand(As, abase, 2, s);
-            const rg_bf16x8 bh = Plane::operand(Bs, bbase, 0, s), bm = Plane::operand(Bs, bbase, 1, s), bl = Plane::operand(Bs, bbase, 2, s);
+            const bf16x8 ah = Plane::operand(As, abase, 0, s), am = Plane::operand(As, abase, 1, s), al = Plane::operand(As, abase, 2, s);
+            const bf16x8 bh = Plane::operand(Bs, bbase, 0, s), bm = Plane::operand(Bs, bbase, 1, s), bl = Plane::operand(Bs, bbase, 2, s);
             X3_MFMA6(acc, ah, am, al, bh, bm, bl);
         }
     }
@@ -769,22 +756,8 @@ constexpr int WR_HROWS = 36;                                   // hi row image: 
 constexpr int WR_RING = 5;
 constexpr int WR_APLANE = RG_R * RG_TRP, WR_HPLANE = WR_HROWS * RG_TRP;
 
-__device__ __forceinline__ rg_bf16x8 wr_tr_operand(const unsigned short *p) {
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    typedef __attribute__((address_space(3))) s16x4 *lds_ptr;
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p);
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(p + 4 * RG_TRP));
-    return __builtin_bit_cast(rg_bf16x8, (s16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ void wr_commit(unsigned short *d, int plane, const float4 &v) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    rg_split3(v.x, v.y, h0, m0, l0);
-    rg_split3(v.z, v.w, h1, m1, l1);
-    *reinterpret_cast<uint2 *>(d) = uint2{h0, h1};
-    *reinterpret_cast<uint2 *>(d + plane) = uint2{m0, m1};
-    *reinterpret_cast<uint2 *>(d + 2 * plane) = uint2{l0, l1};
-}
+// this lane's operand of a [.][RG_TRP] image through the transposing read: its two 4-row blocks are four rows apart
+__device__ __forceinline__ bf16x8 wr_operand(const unsigned short *p) { return lds_tr_x8<bf16x8>(p, p + 4 * RG_TRP); }
 
 template <bool PLAIN_LO, bool PLAIN_HI, int KW>
 __global__ __launch_bounds__(256) void conv_wgrad_rows_x3_kernel(ConvWgrad g, int img_per_wg) {
@@ -820,16 +793,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_x3_kernel(ConvWgrad g, in
     };
     auto commit_lo = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) wr_commit(lo_img + buf * 3 * WR_APLANE + lo_r[i] * RG_TRP + lo_c, WR_APLANE, vlo[i]);
+        for (int i = 0; i < 2; ++i) store_split3_x4(lo_img + buf * 3 * WR_APLANE + lo_r[i] * RG_TRP + lo_c, WR_APLANE, split3_x4(vlo[i]));
     };
     auto commit_hi = [&](int hy) {
         unsigned short *img = hi_ring + ((hy + 2 * WR_RING) % WR_RING) * 3 * WR_HPLANE;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            if (hi_r[i] < WR_HROWS) wr_commit(img + hi_r[i] * RG_TRP + hi_c, WR_HPLANE, vhi[i]);
+            if (hi_r[i] < WR_HROWS) store_split3_x4(img + hi_r[i] * RG_TRP + hi_c, WR_HPLANE, split3_x4(vhi[i]));
     };
 
-    f32x16c acc[2][KW];
+    f32x16 acc[2][KW];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -862,17 +835,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_x3_kernel(ConvWgrad g, in
                 const unsigned short *hb = hi_ring + ((hy + 2 * WR_RING) % WR_RING) * 3 * WR_HPLANE + tr_base;
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    rg_bf16x8 a3[2][3];
+                    bf16x8 a3[2][3];
 #pragma unroll
                     for (int t = 0; t < 3; ++t) {
-                        a3[0][t] = wr_tr_operand(ab + t * WR_APLANE + 16 * s * RG_TRP);
-                        a3[1][t] = wr_tr_operand(ab + t * WR_APLANE + 16 * s * RG_TRP + 32);
+                        a3[0][t] = wr_operand(ab + t * WR_APLANE + 16 * s * RG_TRP);
+                        a3[1][t] = wr_operand(ab + t * WR_APLANE + 16 * s * RG_TRP + 32);
                     }
 #pragma unroll
                     for (int kx = 0; kx < KW; ++kx) {
-                        rg_bf16x8 b3[3];
+                        bf16x8 b3[3];
 #pragma unroll
-                        for (int t = 0; t < 3; ++t) b3[t] = wr_tr_operand(hb + t * WR_HPLANE + (16 * s + kx) * RG_TRP);
+                        for (int t = 0; t < 3; ++t) b3[t] = wr_operand(hb + t * WR_HPLANE + (16 * s + kx) * RG_TRP);
                         X3_MFMA6(acc[0][kx], a3[0][0], a3[0][1], a3[0][2], b3[0], b3[1], b3[2]);
                         if (na > 1) { X3_MFMA6(acc[1][kx], a3[1][0], a3[1][1], a3[1][2], b3[0], b3[1], b3[2]); }
                     }
@@ -908,30 +881,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_x3_kernel(ConvWgrad g, in
 constexpr int WP_SLOTS = 48, WP_RING = 8, WP_HTRP = 48;
 constexpr int WP_APLANE = WP_SLOTS * RG_TRP, WP_HPLANE = WR_HROWS * WP_HTRP;
 
-__device__ __forceinline__ rg_bf16x8 wp_tr_operand(const unsigned short *p0, const unsigned short *p1) {
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    typedef __attribute__((address_space(3))) s16x4 *lds_ptr;
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p0);
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p1);
-    return __builtin_bit_cast(rg_bf16x8, (s16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
-// (on the fp16 MFMA with scaled two-term operands, conv32_common.h: three partial products, the operands' maxima in AMAX
+// (on the fp16 MFMA with scaled two-term operands, splitmath.h: three partial products, the operands' maxima in AMAX
 // arrays; 339 / 217 us per launch with six bf16 products through round 3)
-__device__ __forceinline__ void wp_commit_h2(unsigned short *d, int plane, const float4 &v, float sc) {
-    unsigned h0, l0, h1, l1;
-    split_pair_h2(v.x, v.y, sc, h0, l0);
-    split_pair_h2(v.z, v.w, sc, h1, l1);
-    *reinterpret_cast<uint2 *>(d) = uint2{h0, h1};
-    *reinterpret_cast<uint2 *>(d + plane) = uint2{l0, l1};
-}
-// acc += A . B for one 16-deep k-step: (l, h), (h, l), (h, h)
-#define H2_MFMA3(ACC, AH, AL, BH, BL)                                              \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, ACC, 0, 0, 0);            \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, ACC, 0, 0, 0);            \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, ACC, 0, 0, 0)
-
 // TWO workgroups per CU (72 KB of LDS and <= 128 + 128 registers each): with one, a SIMD held a single wave and every transposed
 // operand read stalled its MFMAs -- the launch ran at 13 % of the fp16 MFMA rate.  The lo pair image is single-buffered for that
 // (a second barrier per pair keeps the next pair's commit off the image still being read).
@@ -1015,7 +966,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pairs_h2_kernel(ConvWgrad g
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             if (lo_r[i] < g.lw)
-                wp_commit_h2(lo_img + (which * g.lw + lo_r[i]) * RG_TRP + lo_c, WP_APLANE, vlo[which][i], sc_l.s);
+                store_split2_x4(lo_img + (which * g.lw + lo_r[i]) * RG_TRP + lo_c, WP_APLANE, vlo[which][i], sc_l.s);
     };
     auto ring_of = [&](int hy) { return hi_ring + ((hy + 4 * WP_RING) & (WP_RING - 1)) * 2 * WP_HPLANE; };
     auto commit_hi = [&](int which, int hy) __attribute__((always_inline)) {
@@ -1028,10 +979,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pairs_h2_kernel(ConvWgrad g
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            if (hi_r[i] < WR_HROWS) wp_commit_h2(img + hi_r[i] * WP_HTRP + hi_c, WP_HPLANE, vhi[which][i], sc_h.s);
+            if (hi_r[i] < WR_HROWS) store_split2_x4(img + hi_r[i] * WP_HTRP + hi_c, WP_HPLANE, vhi[which][i], sc_h.s);
     };
 
-    f32x16c acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1100,15 +1051,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pairs_h2_kernel(ConvWgrad g
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
                         const unsigned short *ap = ab + t * WP_APLANE + 16 * s * RG_TRP;
-                        a2[0][t] = __builtin_bit_cast(f16x8, wp_tr_operand(ap, ap + 4 * RG_TRP));
-                        a2[1][t] = __builtin_bit_cast(f16x8, wp_tr_operand(ap + 32, ap + 32 + 4 * RG_TRP));
+                        a2[0][t] = lds_tr_x8<f16x8>(ap, ap + 4 * RG_TRP);
+                        a2[1][t] = lds_tr_x8<f16x8>(ap + 32, ap + 32 + 4 * RG_TRP);
                     }
                 };
                 auto load_b = [&](int buf, int s, int kx) __attribute__((always_inline)) {
                     const unsigned short *h0 = ((h_sel >> (2 * s)) & 1u) ? hbB : hbA, *h1 = ((h_sel >> (2 * s + 1)) & 1u) ? hbB : hbA;
 #pragma unroll
                     for (int t = 0; t < 2; ++t)
-                        b2[buf][t] = __builtin_bit_cast(f16x8, wp_tr_operand(h0 + t * WP_HPLANE + h_off[s][0] + kx * WP_HTRP, h1 + t * WP_HPLANE + h_off[s][1] + kx * WP_HTRP));
+                        b2[buf][t] = lds_tr_x8<f16x8>(h0 + t * WP_HPLANE + h_off[s][0] + kx * WP_HTRP, h1 + t * WP_HPLANE + h_off[s][1] + kx * WP_HTRP);
                 };
                 load_a(0);
                 load_b(0, 0, 0);

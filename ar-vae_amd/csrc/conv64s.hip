@@ -1,6 +1,6 @@
 // Stride-1 4x4 convolutions between 64-channel layers (the Morpho-MNIST 64 <-> 64 layers, imagevae/mnist_vae.py:16-47),
 // ROW-STAGED: the source rows an output row group meets are fetched from HBM, scaled, turned into two fp16 terms
-// (conv32_common.h: the arithmetic of the 32-channel kernels, three partial products per multiply-add) and written to
+// (splitmath.h: the arithmetic of the 32-channel kernels, three partial products per multiply-add) and written to
 // LDS exactly ONCE, and all 16 taps x 64 channels of the reduction are served from there.  conv_rows_x3_kernel (conv64.hip)
 // re-gathers its 64-pixel A tile from L2 for each of its 32 reduction chunks (~4 GB per launch at B = 1024, 16x re-read) and
 // runs load -> split -> LDS -> MFMA serially between two barriers per chunk (MFMA pipe ~30 % busy).
@@ -12,7 +12,7 @@
 // MT = 3 or 4 MFMA column tiles) and needs G + 3 source rows: <= 176 pixels x (2 x 64 fp16 + pad) = 50 KB, two buffers.
 //   * MFMA orientation as in conv32.hip: the WEIGHTS are the A operand (row = output channel), the pixels the B operand, so a
 //     lane ends up with consecutive channels of one pixel (16-byte stores).  32x32x16 fp16, three partial products per
-//     multiply-add, smallest first (fp32-accurate: conv32_common.h; six bf16 products through round 3: 357-378 us per
+//     multiply-add, smallest first (fp32-accurate: splitmath.h; six bf16 products through round 3: 357-378 us per
 //     64 -> 64 launch at two thirds of the MFMA issue rate).
 //   * wave = kernel row (K split four ways); a wave holds MT x 2 accumulator tiles (all 64 output channels of the group's
 //     pixels for its four taps) -- each pixel operand read from LDS feeds 6 MFMAs, each weight operand MT x 3.  The four partial sums meet through the tile's own (now free) LDS buffer, each wave finishing a quarter
@@ -20,7 +20,7 @@
 //   * weights: split once per launch by conv64s_weight_prep_kernel into the exact per-lane operand order,
 //     [ky][kx][16-channel chunk][column tile][term][lane] x 16 bytes (262 KB, L2 resident) + the inverse weight scale; a wave
 //     streams its 4 KB per reduction step straight into registers, two steps ahead.
-//   * the source tensor's maxima (AMAX array, conv32_common.h) come with it or are taken by operand_amax_kernel first; the
+//   * the source tensor's maxima (AMAX array, amax.h) come with it or are taken by operand_amax_kernel first; the
 //     result's are published by the epilogue.
 //   * pipeline as down32x_kernel: registers hold tile t+1 (loaded during tile t-1); during tile t's MFMAs each loader slot
 //     is split, written to the other buffer and refilled with tile t+2.  The activation derivative / keep-mask of a
@@ -30,7 +30,8 @@
 #include <mutex>
 #include "diag.h"
 #include "common.h"
-#include "conv32_common.h"
+#include "amax.h"
+#include "conv32_common.h"       // raw buffer access
 #include "conv64.h"
 
 #ifdef C64S_STAMPS
@@ -105,10 +106,10 @@ __device__ __forceinline__ void conv64s_prep_block(const float *__restrict__ wt,
         x[j] = q < q_count ? v : 0.f;
     }
     uint4 h, l;
-    split_pair_h2(x[0], x[1], sc.s, h.x, l.x);
-    split_pair_h2(x[2], x[3], sc.s, h.y, l.y);
-    split_pair_h2(x[4], x[5], sc.s, h.z, l.z);
-    split_pair_h2(x[6], x[7], sc.s, h.w, l.w);
+    split2(x[0], x[1], sc.s, h.x, l.x);
+    split2(x[2], x[3], sc.s, h.y, l.y);
+    split2(x[4], x[5], sc.s, h.z, l.z);
+    split2(x[6], x[7], sc.s, h.w, l.w);
     uint4 *d = out + ((tap * 4 + c16) * nt_count + nt) * 2 * 64 + lane;
     d[0] = h; d[64] = l;
 }
@@ -193,10 +194,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         return (unsigned)(pix0 + 16 * s - ts.lo) < (unsigned)ts.span ? (unsigned)(pix0 * 256 + q4 * 16) : OOBV;
     };
     auto slot_load = [&](int s, unsigned off, const TileSrc &ts) __attribute__((always_inline)) {
-        const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_v, (int)off, ts.soff + 4096 * s, 0));
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_v, (int)off, ts.soff + 4096 * s, 0));
         lv[s] = make_float4(v.x, v.y, v.z, v.w);
         if (MODE >= 1) {
-            const f32x4v y = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_y, (int)off, ts.soff + 4096 * s, 0));
+            const f32x4 y = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_y, (int)off, ts.soff + 4096 * s, 0));
             ly[s] = make_float4(y.x, y.y, y.z, y.w);
         }
         if (MODE == 2) lm[s] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs_m, (int)(off == OOBV ? OOBV : off >> 2), (ts.soff + 4096 * s) >> 2, 0);
@@ -219,8 +220,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             v.z *= act_bwd_from_out_sel(y.z, g.src.act); v.w *= act_bwd_from_out_sel(y.w, g.src.act);
         }
         uint2 h, l;
-        split_pair_h2(v.x, v.y, sc_in, h.x, l.x);
-        split_pair_h2(v.z, v.w, sc_in, h.y, l.y);
+        split2(v.x, v.y, sc_in, h.x, l.x);
+        split2(v.z, v.w, sc_in, h.y, l.y);
         unsigned *d = buf + (pix0 + 16 * s) * S_PITCH + q4 * 2;
         *reinterpret_cast<uint2 *>(d) = h;
         *reinterpret_cast<uint2 *>(d + 32) = l;
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
-                x2[0][mt][t] = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4v *>(xb + xoff[mt][0] + t * 32));
+                x2[0][mt][t] = lds_x8<f16x8>(xb + xoff[mt][0] + t * 32);
         // Issue order pinned by hand (one scheduling barrier after every MFMA; see conv32k.hip and DESIGN.md section 4, item 15c):
         // the step's other work -- the next step's 3 MT pixel operand reads, the weight loads of the step after that, and the
         // loader's pieces (address, loads; derivative / mask, split in two halves per value pair, LDS writes) -- sits between the
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 constexpr int i = decltype(ic)::value;
                 if constexpr (i < n_read) {
                     constexpr int njx = (step + 1) >> 2, nc16 = (step + 1) & 3, mt = i / 2, t = i % 2;
-                    x2[nx][mt][t] = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4v *>(xb + xoff[mt][njx] + t * 32 + nc16 * 8));
+                    x2[nx][mt][t] = lds_x8<f16x8>(xb + xoff[mt][njx] + t * 32 + nc16 * 8);
                 } else if constexpr (i < n_read + n_w) {
                     constexpr int k = i - n_read, nt = k / 2, t = k % 2, njx = (step + W_AHEAD) >> 2, nc16 = (step + W_AHEAD) & 3;
                     const int nkx = g.sgn > 0 ? njx : 3 - njx;
@@ -392,8 +393,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                             c_v.z *= act_bwd_from_out_sel(y.z, g.src.act); c_v.w *= act_bwd_from_out_sel(y.w, g.src.act);
                         }
                     }
-                    if constexpr (piece == 1) split_pair_h2(c_v.x, c_v.y, sc_in, c_h.x, c_l.x);
-                    if constexpr (piece == 2) split_pair_h2(c_v.z, c_v.w, sc_in, c_h.y, c_l.y);
+                    if constexpr (piece == 1) split2(c_v.x, c_v.y, sc_in, c_h.x, c_l.x);
+                    if constexpr (piece == 2) split2(c_v.z, c_v.w, sc_in, c_h.y, c_l.y);
                     if constexpr (piece == 3) {
                         unsigned *d = nb + (pix0 + 16 * s) * S_PITCH + q4 * 2;
                         *reinterpret_cast<uint2 *>(d) = c_h;

@@ -28,7 +28,7 @@ struct Ep1 {
     uint16_t *bits_out;         // with relu: sign bits of the result for a later gated kernel, may be null
     float *out;
     int relu;
-    unsigned *amax_out = nullptr;   // AMAX array of `out` (conv32_common.h) for the 32-channel kernel that reads it next, or null
+    unsigned *amax_out = nullptr;   // AMAX array of `out` (amax.h) for the 32-channel kernel that reads it next, or null
 };
 
 // ================================================================================================
@@ -165,7 +165,6 @@ __global__ __launch_bounds__(256) void down_c1s_prep_kernel(Operand img, const f
 // 9 per wave; T is double-buffered in LDS so a tile needs one barrier.  With LOSS the reconstruction term of the
 // trainer (sum of the per-pixel loss, correct-pixel count, d/dlogits) is computed on the pixels as they are
 // produced: per-workgroup partial sums go to partial[2*blockIdx.x ..], the logits are still written.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int TRU = 16;
 constexpr int UG_PER_WAVE = (TRU + 2) * 2 / 4;          // 9
 constexpr int TS1 = 17;                                 // floats per position in the LDS T tile

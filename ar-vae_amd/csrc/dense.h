@@ -47,7 +47,7 @@ struct WideGemm {
     const float *bias;          // finished: per output column, may be null
     int act;                    // finished: activation (ARVAE_ACT_*)
     const float *gate;          // finished: optional ReLU gate: out = gate[m][n] > 0 ? value : 0
-    unsigned *amax_out;         // finished: AMAX array of the result (conv32_common.h), may be null
+    unsigned *amax_out;         // finished: AMAX array of the result (amax.h), may be null
     int dbg;                    // always 0: ablation bits of a retired timing probe (1 no MFMAs, 2 no LDS commits, 4 no result
                                 // stores), left in so that the kernels' code stays the code that was measured
 };

@@ -12,7 +12,7 @@
 #include <mutex>
 #include "diag.h"
 #include "common.h"
-#include "conv32_common.h"
+#include "amax.h"
 #include "dense.h"
 #include "reduce.h"
 #include "x3tile.h"
@@ -21,7 +21,6 @@
 
 namespace arvae {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ void mfma4(f32x16 &acc, const float (&a)[4], const float (&b)[4]) {
 #pragma unroll
@@ -312,8 +311,7 @@ struct TileLoader {
                 const unsigned off = ok ? (unsigned)((rel_row * (int)ld + rel_col) * 4) : 0xfffffff0u;
                 const int so = LAY == RG_ROWSK ? r0 * 4 : r0 * (int)ld * 4;
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7fffffff, 0x00020000);
-                typedef float f32x4t_ __attribute__((ext_vector_type(4)));
-                const f32x4t_ t = __builtin_bit_cast(f32x4t_, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, so, 0));
+                const f32x4 t = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, so, 0));
                 v[i] = float4{t.x, t.y, t.z, t.w};
             } else {
                 const float *src = base + (int64_t)(rok ? row : 0) * ld;
@@ -328,7 +326,7 @@ struct TileLoader {
             }
         }
     }
-    // three bf16 planes for the split-bf16 MFMA (x3tile.h)
+    // three bf16 planes for the split-bf16 MFMA (splitmath.h)
     typedef X3Plane<LAY, TP> Plane;
     static constexpr int PLANE = Plane::PLANE;
     __device__ __forceinline__ void commit3(unsigned short *lds) const {
@@ -336,7 +334,7 @@ struct TileLoader {
         for (int i = 0; i < NV; ++i) Plane::commit(lds, threadIdx.x + 256 * i, v[i]);
     }
     __device__ static __forceinline__ int lane_base(int w) { return Plane::lane_base(w); }
-    __device__ static __forceinline__ rg_bf16x8 operand(const unsigned short *lds, int base, int t, int s) {
+    __device__ static __forceinline__ bf16x8 operand(const unsigned short *lds, int base, int t, int s) {
         return Plane::operand(lds, base, t, s);
     }
 };
@@ -393,8 +391,8 @@ __device__ __forceinline__ void rows_gemm_x3_body(const RowsGemm &g, const int b
         }
 #pragma unroll
         for (int s = 0; s < RG_R / 16; ++s) {
-            const rg_bf16x8 ah = LoadA::operand(As, abase, 0, s), am = LoadA::operand(As, abase, 1, s), al = LoadA::operand(As, abase, 2, s);
-            const rg_bf16x8 bh = LoadB::operand(Bs, bbase, 0, s), bm = LoadB::operand(Bs, bbase, 1, s), bl = LoadB::operand(Bs, bbase, 2, s);
+            const bf16x8 ah = LoadA::operand(As, abase, 0, s), am = LoadA::operand(As, abase, 1, s), al = LoadA::operand(As, abase, 2, s);
+            const bf16x8 bh = LoadB::operand(Bs, bbase, 0, s), bm = LoadB::operand(Bs, bbase, 1, s), bl = LoadB::operand(Bs, bbase, 2, s);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
@@ -440,7 +438,7 @@ __global__ __launch_bounds__(256) void rows_gemm_x3_kernel(RowsGemm g) {
 // Wide Linear layers on the matrix pipe (round 6; Morpho-MNIST's Linear(2888, 256) / Linear(256, 2888), imagevae/mnist_vae.py:27-38,
 // BASELINE.json configs[2] "MFMA on fc z-projections").  The latent block's row kernels (midblock.hip) stream every matrix through
 // every workgroup on fp32 FMA chains: 80 + 85 us per step for these two layers' 6 GFLOP.  Here a layer's forward product and its
-// data gradient are tile GEMMs  C[M][N] = sum_k A[m][k] B(k, n)  on the three-term bf16 MFMA (x3tile.h: fp32-accurate, no operand
+// data gradient are tile GEMMs  C[M][N] = sum_k A[m][k] B(k, n)  on the three-term bf16 MFMA (splitmath.h: fp32-accurate, no operand
 // scales to carry), 64 x 64 tiles, 2 x 2 waves:
 //   * A is always "rows x K" (activations / gradients, [batch][features]); B is the layer's ONE per-step copy W'[n_mem][k_mem]
 //     (mid_prep: the NCHW-flatten permutation folded in) read as "rows x K" for the forward product and as "K x rows" -- through the
@@ -605,7 +603,7 @@ __device__ __forceinline__ void wide_mainloop(const void *a, int64_t lda, int64_
         if (dbg & 1) return;
 #pragma unroll
         for (int s = 0; s < RG_R / 16; ++s) {
-            rg_bf16x8 a3[NT][3], b3[NT][3];
+            bf16x8 a3[NT][3], b3[NT][3];
 #pragma unroll
             for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -720,7 +718,7 @@ __global__ __launch_bounds__(256, NT == 1 ? (WG_NBUF == 1 ? 3 : 2) : 1) void wid
             }
         }
     }
-    if (EP == WG_EP_FULL && g.amax_out != nullptr) {             // one AMAX writer unit per workgroup (conv32_common.h)
+    if (EP == WG_EP_FULL && g.amax_out != nullptr) {             // one AMAX writer unit per workgroup (amax.h)
         float *red = reinterpret_cast<float *>(wlds + NBUF * BUF);
         amax = wave_max(amax);
         __syncthreads();
@@ -919,7 +917,7 @@ __device__ __forceinline__ void rows_wgrad128_body(const RowsGemm &g, const int 
         }
 #pragma unroll
         for (int s = 0; s < RG_R / 16; ++s) {
-            rg_bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
+            bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 ah[i] = Load::operand(As, abase[i], 0, s); am[i] = Load::operand(As, abase[i], 1, s); al[i] = Load::operand(As, abase[i], 2, s);
@@ -932,8 +930,8 @@ __device__ __forceinline__ void rows_wgrad128_body(const RowsGemm &g, const int 
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
-                        const rg_bf16x8 x = prod == 0 ? al[a] : ((prod == 2 || prod == 3) ? am[a] : ah[a]);
-                        const rg_bf16x8 y = prod == 1 ? bl[b] : ((prod == 2 || prod == 4) ? bm[b] : bh[b]);
+                        const bf16x8 x = prod == 0 ? al[a] : ((prod == 2 || prod == 3) ? am[a] : ah[a]);
+                        const bf16x8 y = prod == 1 ? bl[b] : ((prod == 2 || prod == 4) ? bm[b] : bh[b]);
                         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc[a][b], 0, 0, 0);
                     }
         }

@@ -8,7 +8,7 @@
 // from the prepared DOWN part, prep32.h) and it owns two accumulator tiles (its MFMAs alternate between them).
 //   * a tile = 64 lo pixels (4 rows at 16x16, one image at 8x8) = two 32-pixel MFMA column tiles; weight = A operand
 //     (row = output channel), pixels = B operand, 32x32x16 fp16 on scaled two-term operands, three partial products per
-//     multiply-add, smallest first (conv32_common.h);
+//     multiply-add, smallest first (splitmath.h);
 //   * consumer wave = kernel row ky (K split four ways): 8 reduction steps (kx, 16-channel chunk) of 6 MFMAs per tile.  The
 //     four partial sums meet through a 24 KB LDS area; wave w finishes column tile w & 1, channel groups 2 (w >> 1),
 //     2 (w >> 1) + 1 (16-byte stores, one byte of ReLU sign bits per lane);
@@ -103,8 +103,8 @@ __device__ __forceinline__ void down32p_body(const float *__restrict__ hi, Ep32 
             const int pix = pix0 + 32 * s;
             if (SLOTS * 32 > PIX && pix >= PIX) return;
             uint2 hv, lw;
-            split_pair_h2(lv[set][s].x, lv[set][s].y, sc_in, hv.x, lw.x);
-            split_pair_h2(lv[set][s].z, lv[set][s].w, sc_in, hv.y, lw.y);
+            split2(lv[set][s].x, lv[set][s].y, sc_in, hv.x, lw.x);
+            split2(lv[set][s].z, lv[set][s].w, sc_in, hv.y, lw.y);
             unsigned *d = buf + pix * PSB2 + q * 2;
             *reinterpret_cast<uint2 *>(d) = hv;
             *reinterpret_cast<uint2 *>(d + 16) = lw;
@@ -280,7 +280,7 @@ __device__ __forceinline__ void down32p_body(const float *__restrict__ hi, Ep32 
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
-                x2[0][mt][t] = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4v *>(xb + xoff[mt][0] + t * 16));
+                x2[0][mt][t] = lds_x8<f16x8>(xb + xoff[mt][0] + t * 16);
         load_parts();
         int img0, r0;
         tile_origin<LO, 64>(tile, img0, r0);
@@ -305,7 +305,7 @@ __device__ __forceinline__ void down32p_body(const float *__restrict__ hi, Ep32 
                 if constexpr (i < 4) {
                     if constexpr (step + 1 < 8) {
                         constexpr int nkx = (step + 1) >> 1, nc = (step + 1) & 1, mt = i / 2, t = i % 2;
-                        x2[nx][mt][t] = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4v *>(xb + xoff[mt][nkx] + t * 16 + nc * 8));
+                        x2[nx][mt][t] = lds_x8<f16x8>(xb + xoff[mt][nkx] + t * 16 + nc * 8);
                     }
                 } else {
                     epi_item(std::integral_constant<int, e_lo + (i - 4)>{});

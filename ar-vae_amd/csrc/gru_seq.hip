@@ -18,6 +18,7 @@
 #include <algorithm>
 #include "diag.h"
 #include "common.h"
+#include "splitmath.h"
 #include "gru_mask.h"
 
 namespace arvae {
@@ -60,8 +61,6 @@ struct GruSeqBatch {
     GruSeq seq[GRU_SEQ_MAX];
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // reciprocals on v_rcp_f32 (1 ulp): __frcp_rn is a correctly rounded division -- v_div_scale x 2, v_rcp, four fused steps,
 // v_div_fmas, v_div_fixup -- and three of them per hidden unit and step were ~10 % of the forward recurrence's instructions
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
@@ -98,76 +97,19 @@ __device__ __forceinline__ int gru_off(int row, int pitch_bytes, int base_bytes)
 //   g = dh_all[t] + carry;  dpn = g (1-z)(1-n^2);  dpz = g (h_prev - n) z (1-z);  dpr = dpn gh_n r (1-r)
 //   dgi = [dpr, dpz, dpn];  dgh = [dpr, dpz, dpn r];  carry = g z + dgh . W_hh
 //
-// The backward recurrence on the bf16 MFMA at fp32 accuracy (the three-term split of conv32.hip; the diagnostic build's
+// The backward recurrence on the bf16 MFMA at fp32 accuracy (the three-term split of splitmath.h; the diagnostic build's
 // ARVAE_GRU_BF16_BWD form): W_hh is split once into hi + mid + lo bf16 terms per lane (144 VGPRs at H = 128), dgh is split
 // when it is written to LDS as three bf16 planes, and a multiply-add is the six partial products >= 2^-18 on
 // v_mfma_f32_16x16x32_bf16 (16 cycles each instead of 8 x 32 for the fp32 16x16x4), smallest first.
-typedef __bf16 bf16x8g __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2g __attribute__((ext_vector_type(2)));
-typedef float f32x2g __attribute__((ext_vector_type(2)));
-typedef int i32x4g __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &hi, unsigned &mid, unsigned &lo) {
-    const f32x2g x = {x0, x1};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2g));
-    const f32x2g r = {x0 - __builtin_bit_cast(float, hi << 16), x1 - __builtin_bit_cast(float, hi & 0xffff0000u)};
-    mid = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2g));
-    const f32x2g q = {r.x - __builtin_bit_cast(float, mid << 16), r.y - __builtin_bit_cast(float, mid & 0xffff0000u)};
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2g));
-}
-__device__ __forceinline__ void split3_x8(const float (&x)[8], bf16x8g &hi, bf16x8g &mid, bf16x8g &lo) {
-    i32x4g h, m, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        unsigned a, b, c;
-        split3_pair(x[2 * j], x[2 * j + 1], a, b, c);
-        h[j] = (int)a; m[j] = (int)b; l[j] = (int)c;
-    }
-    hi = __builtin_bit_cast(bf16x8g, h); mid = __builtin_bit_cast(bf16x8g, m); lo = __builtin_bit_cast(bf16x8g, l);
-}
-// one value -> its three bf16 terms into the three LDS planes (plane stride in ushorts)
-__device__ __forceinline__ void store_split3(unsigned short *p, int plane, float x) {
-    unsigned a, b, c;
-    split3_pair(x, 0.f, a, b, c);
-    p[0] = (unsigned short)a; p[plane] = (unsigned short)b; p[2 * plane] = (unsigned short)c;
-}
-// two values (rows `rowpitch` apart in every plane) for the price of one split
-__device__ __forceinline__ void store_split3_pair(unsigned short *p, int rowpitch, int plane, float x0, float x1) {
-    unsigned a, b, c;
-    split3_pair(x0, x1, a, b, c);
-    p[0] = (unsigned short)a; p[rowpitch] = (unsigned short)(a >> 16);
-    p[plane] = (unsigned short)b; p[plane + rowpitch] = (unsigned short)(b >> 16);
-    p[2 * plane] = (unsigned short)c; p[2 * plane + rowpitch] = (unsigned short)(c >> 16);
-}
-__device__ __forceinline__ bf16x8g lds_x8(const unsigned short *p) {
-    return __builtin_bit_cast(bf16x8g, *reinterpret_cast<const i32x4g *>(p));
-}
-// acc += a . w with a = (ah, am, al), w = (wh, wm, wl), the six products smallest first, into
-// three independent accumulators, product-major: consecutive MFMAs never hit the same accumulator (a dependent 16x16x32 MFMA
-// waits for its predecessor's result, about twice the issue interval), every accumulator still sees its six products in order
-#define GRU_MFMA6X3(A0, A1, A2, H0, M0, L0, H1, M1, L1, H2, M2, L2, WH0, WM0, WL0, WH1, WM1, WL1, WH2, WM2, WL2)                 \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(L0, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(L1, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(L2, WH2, A2, 0, 0, 0);                                                          \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H0, WL0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H1, WL1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H2, WL2, A2, 0, 0, 0);                                                          \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(M0, WM0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(M1, WM1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(M2, WM2, A2, 0, 0, 0);                                                          \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(M0, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(M1, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(M2, WH2, A2, 0, 0, 0);                                                          \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H0, WM0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H1, WM1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H2, WM2, A2, 0, 0, 0);                                                          \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H0, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H1, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(H2, WH2, A2, 0, 0, 0)
-
 #ifdef ARVAE_GRU_STAMPS
 __device__ unsigned long long g_gru_stamps[8];
 __device__ unsigned long long g_tick_stamps[9];
 #endif
 // ------------------------------------------------------------------------------------------------------------------
-// The forward recurrence on the fp16 MFMA with SCALED TWO-TERM operands (the arithmetic of conv32_common.h): s x = h + l with
+// The forward recurrence on the fp16 MFMA with SCALED TWO-TERM operands (the arithmetic of splitmath.h): s x = h + l with
 // h = fp16(s x), l = fp16(s x - h), a product = the three partial products l h', h l', h h' on v_mfma_f32_16x16x32_f16, smallest
 // first -- half the MFMAs and two thirds of the LDS operand bytes of the three-term bf16 split at the same accuracy (2^-22 per
-// product; measured against float64: conv32_common.h).  fp16 has 5 exponent bits, so the scales must place the operands.
+// product; measured against float64: splitmath.h).  fp16 has 5 exponent bits, so the scales must place the operands.
 // The SEQUENCE kernels take every scale from the data (round 5): W_hh's slice of a wave its own power of two (a column's scale
 // factors out of the dot product), the state the workgroup's max(1, max |h0|) -- a bound for the whole sequence, h_t being a convex
 // combination of a tanh output and h_(t-1) --, the backward pass's gradients a scale per batch row and step (gru_seq_bwd_h2_kernel):
@@ -175,46 +117,6 @@ __device__ unsigned long long g_tick_stamps[9];
 // from their maxima (tick_weight_amax_kernel, one launch in front of the weight prep; W_ih1 and W_hh1 share a scale because their
 // products share accumulators), the states' per beat from the workgroup's rows (a beat's states are convex combinations of tanh
 // outputs and the beat's initial state; the layer-1 input is a layer-0 state times 0 or the keep scale).
-typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2g __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split2_pair(float x0, float x1, float s, unsigned &hi, unsigned &lo) {
-    const float y0 = x0 * s, y1 = x1 * s;
-    const f32x2g y = {y0, y1};
-    const f16x2g h = __builtin_convertvector(y, f16x2g);
-    hi = __builtin_bit_cast(unsigned, h);
-    const f32x2g r = {y0 - (float)h.x, y1 - (float)h.y};
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2g));
-}
-__device__ __forceinline__ void split2_x8(const float (&x)[8], float s, f16x8g &hi, f16x8g &lo) {
-    i32x4g h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        unsigned a, b;
-        split2_pair(x[2 * j], x[2 * j + 1], s, a, b);
-        h[j] = (int)a; l[j] = (int)b;
-    }
-    hi = __builtin_bit_cast(f16x8g, h); lo = __builtin_bit_cast(f16x8g, l);
-}
-__device__ __forceinline__ f16x8g lds_h8(const unsigned short *p) {
-    return __builtin_bit_cast(f16x8g, *reinterpret_cast<const i32x4g *>(p));
-}
-// three accumulators (the gates), product-major as GRU_MFMA6X3: l h', h l', h h'
-#define GRU_MFMA3X3(A0, A1, A2, AH, AL, WH0, WL0, WH1, WL1, WH2, WL2)                                                             \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, WH2, A2, 0, 0, 0);                                                            \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WL0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WL1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WL2, A2, 0, 0, 0);                                                            \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WH2, A2, 0, 0, 0)
-
-// power-of-two scales found at run time (the backward recurrence's per-row scales, both recurrences' per-wave weight scales, the
-// forward recurrence's state scale)
-struct GruPow2 { float s, inv; };
-__device__ __forceinline__ GruPow2 gru_pow2(float amax) {        // 2^k with amax * 2^k in [2^14, 2^15), and 2^-k (amax 0: 2^125)
-    int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu);
-    e = e < 16 ? 16 : e;
-    return GruPow2{__builtin_bit_cast(float, (unsigned)(268 - e) << 23), __builtin_bit_cast(float, (unsigned)(e - 14) << 23)};
-}
 template <int CTRL> __device__ __forceinline__ float dpp_max(float v) {
     const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
     return fmaxf(v, o);
@@ -225,17 +127,6 @@ __device__ __forceinline__ float row16_max(float v) {
     v = dpp_max<0x4E>(v);
     v = dpp_max<0x141>(v);
     return dpp_max<0x140>(v);
-}
-__device__ __forceinline__ void store_split2_pair_s(unsigned short *p, int rowpitch, int plane, float x0, float x1, float sc) {
-    unsigned a, b;
-    split2_pair(x0, x1, sc, a, b);
-    p[0] = (unsigned short)a; p[rowpitch] = (unsigned short)(a >> 16);
-    p[plane] = (unsigned short)b; p[plane + rowpitch] = (unsigned short)(b >> 16);
-}
-__device__ __forceinline__ void store_split2_s(unsigned short *p, int plane, float x, float sc) {
-    unsigned a, b;
-    split2_pair(x, 0.f, sc, a, b);
-    p[0] = (unsigned short)a; p[plane] = (unsigned short)b;
 }
 // Quad q's lanes receive element q of the f32x4 their column's lane in quad 0 holds (three swaps of register halves / quarters): the
 // four live rows of a 16 x 16 MFMA result, one per lane.
@@ -308,7 +199,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
 
     // W_hh's slice of this wave as two fp16 terms at the wave's own scale (round 5: the slice's largest magnitude just below 2^15;
     // through round 4 a fixed 2^8, which overflowed fp16 for |w| >= 255)
-    f16x8g wh[3][KS], wl[3][KS];
+    f16x8 wh[3][KS], wl[3][KS];
     float w_inv;
     {
         float x[3][KS][8], m = 0.f;
@@ -327,12 +218,12 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         m = row16_max(m);
         m = fmaxf(m, __shfl_xor(m, 16));
         m = fmaxf(m, __shfl_xor(m, 32));
-        const GruPow2 sw = gru_pow2(m);
+        const Pow2 sw = pow2_for(m);
         w_inv = sw.inv;
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) split2_x8(x[g][ks], sw.s, wh[g][ks], wl[g][ks]);
+            for (int ks = 0; ks < KS; ++ks) split2_8<false>(x[g][ks], sw.s, wh[g][ks], wl[g][ks]);
     }
     const float bh_r = s.b_hh[unit], bh_z = s.b_hh[H + unit], bh_n = s.b_hh[2 * H + unit];
 
@@ -362,12 +253,12 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         lds_barrier();
 #pragma unroll
         for (int q = 0; q < H / 16; ++q) m = fmaxf(m, h0max[q]);
-        const GruPow2 sh = gru_pow2(m);
+        const Pow2 sh = pow2_for(m);
         h_s = sh.s;
         unscale = sh.inv * w_inv;
     }
 #pragma unroll
-    for (int i = 0; i < E; ++i) store_split2_s(&hbuf[0][lrow(i) * HP + unit], PLANE, h[i], h_s);
+    for (int i = 0; i < E; ++i) store_split2<false>(&hbuf[0][lrow(i) * HP + unit], PLANE, h[i], h_s);
     // per-step memory operations as raw buffer operations (gru_rsrc): a scalar step offset + one per-lane offset per array and row
     // (the running 64-bit pointers this kernel had cost 24 registers and a 64-bit add each per step; the first and last step's
     // missing operations were branches).  A dead row's stores go beyond the range.
@@ -434,13 +325,13 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
             gi_next[i][2] = gru_ld(rs_gi, gi_o[i] + 8 * H, so_gi);
             gru_st(keep_h[i], rs_hs, h_o[i], so_h);
             gru_st(keep_hm[i], rs_hms, hm_o[i], so_hm);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4g, keep_sv[i]), rs_svs, sv_o[i], so_sv, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, keep_sv[i]), rs_svs, sv_o[i], so_sv, 0);
             mk_cur[i] = __builtin_amdgcn_raw_buffer_load_b8(rs_mk, mk_o[i], so_mk, 0);
         };
         static_assert(KS <= 4, "one row's traffic per k-step; rows left over go last");
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const f16x8g ah = lds_h8(hb + 32 * ks), al = lds_h8(hb + PLANE + 32 * ks);
+            const f16x8 ah = lds_x8<f16x8>(hb + 32 * ks), al = lds_x8<f16x8>(hb + PLANE + 32 * ks);
             GRU_MFMA3X3(acc[0], acc[1], acc[2], ah, al, wh[0][ks], wl[0][ks], wh[1][ks], wl[1][ks], wh[2][ks], wl[2][ks]);
             __builtin_amdgcn_sched_barrier(0);
             if (ks < E) row_traffic(ks);
@@ -469,9 +360,9 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         }
         if constexpr (E >= 2) {
 #pragma unroll
-            for (int i = 0; i < E; i += 2) store_split2_pair_s(&hbuf[cur ^ 1][lrow(i) * HP + unit], HP, PLANE, h[i], h[i + 1], h_s);
+            for (int i = 0; i < E; i += 2) store_split2<false>(&hbuf[cur ^ 1][lrow(i) * HP + unit], HP, PLANE, h[i], h[i + 1], h_s);
         } else {
-            store_split2_s(&hbuf[cur ^ 1][quad * HP + unit], PLANE, h[0], h_s);
+            store_split2<false>(&hbuf[cur ^ 1][quad * HP + unit], PLANE, h[0], h_s);
         }
         keep_t = t;
 #ifdef ARVAE_GRU_STAMPS
@@ -492,7 +383,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         if (live[i]) {
             gru_st(keep_h[i], rs_h, h_o[i], keep_t * h_tp);
             gru_st(keep_hm[i], rs_hm, hm_o[i], keep_t * hm_tp);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4g, keep_sv[i]), rs_sv, sv_o[i], keep_t * R * (16 * H), 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, keep_sv[i]), rs_sv, sv_o[i], keep_t * R * (16 * H), 0);
             if (s.h_fin != nullptr) s.h_fin[(int64_t)rows[i] * s.h_fin_stride + unit] = keep_h[i];
         }
 }
@@ -514,13 +405,13 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
     const int row0 = blockIdx.x * RW;
 
     // B[k = c][n = unit] = W_hh[c][unit], c = 32 ks + 8 quad + j
-    bf16x8g wh[KS], wm[KS], wl[KS];
+    bf16x8 wh[KS], wm[KS], wl[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float x[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = s.w_hh[(int64_t)(32 * ks + 8 * quad + j) * H + unit];
-        split3_x8(x, wh[ks], wm[ks], wl[ks]);
+        split3_8(x, wh[ks], wm[ks], wl[ks]);
     }
 
     int rows[E];
@@ -584,9 +475,9 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
 #pragma unroll
             for (int i = 0; i < E; i += 2) {
                 unsigned short *d = &dbuf[cur][gru_lrow<E>(quad, i) * DP + unit];
-                store_split3_pair(d, DP, PLANE, o_gi[i][0], o_gi[i + 1][0]);
-                store_split3_pair(d + H, DP, PLANE, o_gi[i][1], o_gi[i + 1][1]);
-                store_split3_pair(d + 2 * H, DP, PLANE, o_hn[i], o_hn[i + 1]);
+                store_split3(d, DP, PLANE, o_gi[i][0], o_gi[i + 1][0]);
+                store_split3(d + H, DP, PLANE, o_gi[i][1], o_gi[i + 1][1]);
+                store_split3(d + 2 * H, DP, PLANE, o_hn[i], o_hn[i + 1]);
             }
         } else {
             unsigned short *d = &dbuf[cur][quad * DP + unit];
@@ -616,9 +507,9 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
         };
 #pragma unroll
         for (int ks = 0; ks < KS; ks += 3) {
-            const bf16x8g ah0 = lds_x8(db + 32 * ks), am0 = lds_x8(db + PLANE + 32 * ks), al0 = lds_x8(db + 2 * PLANE + 32 * ks);
-            const bf16x8g ah1 = lds_x8(db + 32 * (ks + 1)), am1 = lds_x8(db + PLANE + 32 * (ks + 1)), al1 = lds_x8(db + 2 * PLANE + 32 * (ks + 1));
-            const bf16x8g ah2 = lds_x8(db + 32 * (ks + 2)), am2 = lds_x8(db + PLANE + 32 * (ks + 2)), al2 = lds_x8(db + 2 * PLANE + 32 * (ks + 2));
+            const bf16x8 ah0 = lds_x8<bf16x8>(db + 32 * ks), am0 = lds_x8<bf16x8>(db + PLANE + 32 * ks), al0 = lds_x8<bf16x8>(db + 2 * PLANE + 32 * ks);
+            const bf16x8 ah1 = lds_x8<bf16x8>(db + 32 * (ks + 1)), am1 = lds_x8<bf16x8>(db + PLANE + 32 * (ks + 1)), al1 = lds_x8<bf16x8>(db + 2 * PLANE + 32 * (ks + 1));
+            const bf16x8 ah2 = lds_x8<bf16x8>(db + 32 * (ks + 2)), am2 = lds_x8<bf16x8>(db + PLANE + 32 * (ks + 2)), al2 = lds_x8<bf16x8>(db + 2 * PLANE + 32 * (ks + 2));
             GRU_MFMA6X3(acc[0], acc[1], acc[2], ah0, am0, al0, ah1, am1, al1, ah2, am2, al2, wh[ks], wm[ks], wl[ks], wh[ks + 1], wm[ks + 1],
                         wl[ks + 1], wh[ks + 2], wm[ks + 2], wl[ks + 2]);
             __builtin_amdgcn_sched_barrier(0);
@@ -663,15 +554,6 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
 // to [2^14, 2^15): a 16-lane butterfly per wave, one LDS slot per (row, wave), a barrier, NW slots read back.  Nothing can overflow
 // (the scaled maximum is below 2^15 by construction), a row whose gradient is 1e-9 keeps the same 22 bits as one at 1e+3, and W_hh^T
 // gets a per-wave scale from its own slice's maximum in the prologue (a column's scale factors out as well) instead of the fixed 2^8.
-// three accumulators, one k-step each, product-major (l h', h l', h h'): consecutive MFMAs never hit the same accumulator
-#define GRU_MFMA3K3(A0, A1, A2, H0, L0, H1, L1, H2, L2, WH0, WL0, WH1, WL1, WH2, WL2)                                              \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(L0, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(L1, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(L2, WH2, A2, 0, 0, 0);                                                            \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(H0, WL0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(H1, WL1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(H2, WL2, A2, 0, 0, 0);                                                            \
-    A0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(H0, WH0, A0, 0, 0, 0); A1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(H1, WH1, A1, 0, 0, 0); \
-    A2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(H2, WH2, A2, 0, 0, 0)
-
 template <int H, int RW>
 __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch, int T, int R) {
     static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
@@ -691,7 +573,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
     const int row0 = blockIdx.x * RW;
 
     // B[k = c][n = unit] = W_hh[c][unit], c = 32 ks + 8 quad + j: two fp16 terms at this wave's own scale
-    f16x8g wh[KS], wl[KS];
+    f16x8 wh[KS], wl[KS];
     float w_inv;
     {
         float x[KS][8], m = 0.f;
@@ -705,10 +587,10 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
         m = row16_max(m);
         m = fmaxf(m, __shfl_xor(m, 16));
         m = fmaxf(m, __shfl_xor(m, 32));
-        const GruPow2 sw = gru_pow2(m);
+        const Pow2 sw = pow2_for(m);
         w_inv = sw.inv;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) split2_x8(x[ks], sw.s, wh[ks], wl[ks]);
+        for (int ks = 0; ks < KS; ++ks) split2_8<false>(x[ks], sw.s, wh[ks], wl[ks]);
     }
     if (MW > NW && threadIdx.x < 16 * (MW - NW)) rmax[threadIdx.x / (MW - NW)][NW + threadIdx.x % (MW - NW)] = 0.f;   // (slots no wave writes)
 
@@ -786,12 +668,12 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
                 const f32x4 v = *reinterpret_cast<const f32x4 *>(&rmax[lrow(i)][q]);
                 m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
             }
-            const GruPow2 sc = gru_pow2(m);
+            const Pow2 sc = pow2_for(m);
             unscale[i] = sc.inv * w_inv;
             unsigned short *d = &dbuf[lrow(i) * DP + unit];
-            store_split2_s(d, PLANE, o_gi[i][0], sc.s);
-            store_split2_s(d + H, PLANE, o_gi[i][1], sc.s);
-            store_split2_s(d + 2 * H, PLANE, o_hn[i], sc.s);
+            store_split2<false>(d, PLANE, o_gi[i][0], sc.s);
+            store_split2<false>(d + H, PLANE, o_gi[i][1], sc.s);
+            store_split2<false>(d + 2 * H, PLANE, o_hn[i], sc.s);
         }
         lds_barrier();                       // the operand image is written; the maxima have been read
         f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -809,9 +691,9 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
         };
 #pragma unroll
         for (int ks = 0; ks < KS; ks += 3) {
-            const f16x8g ah0 = lds_h8(db + 32 * ks), al0 = lds_h8(db + PLANE + 32 * ks);
-            const f16x8g ah1 = lds_h8(db + 32 * (ks + 1)), al1 = lds_h8(db + PLANE + 32 * (ks + 1));
-            const f16x8g ah2 = lds_h8(db + 32 * (ks + 2)), al2 = lds_h8(db + PLANE + 32 * (ks + 2));
+            const f16x8 ah0 = lds_x8<f16x8>(db + 32 * ks), al0 = lds_x8<f16x8>(db + PLANE + 32 * ks);
+            const f16x8 ah1 = lds_x8<f16x8>(db + 32 * (ks + 1)), al1 = lds_x8<f16x8>(db + PLANE + 32 * (ks + 1));
+            const f16x8 ah2 = lds_x8<f16x8>(db + 32 * (ks + 2)), al2 = lds_x8<f16x8>(db + PLANE + 32 * (ks + 2));
             GRU_MFMA3K3(acc[0], acc[1], acc[2], ah0, al0, ah1, al1, ah2, al2, wh[ks], wl[ks], wh[ks + 1], wl[ks + 1], wh[ks + 2], wl[ks + 2]);
             __builtin_amdgcn_sched_barrier(0);
             if (ks / 3 < E) row_stores(ks / 3);
@@ -1064,12 +946,6 @@ struct TickPrep {
     uint4 *out;
 };
 
-// one accumulator: l h', h l', h h'
-#define GRU_MFMA3(ACC, AH, AL, WH, WL)                                                 \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, WH, ACC, 0, 0, 0);                \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WL, ACC, 0, 0, 0);                \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WH, ACC, 0, 0, 0)
-
 // the same free-running pass on the scaled two-term fp16 operands of gru_seq_fwd_h2_kernel: two thirds of the weight stream
 // (590 instead of 885 KB per tick and workgroup, the kernel's bound) and half the MFMAs
 // largest magnitude of each of the three matrices (one workgroup per matrix) -> wmax[0 .. 3): the free-running kernel's weight scales
@@ -1094,8 +970,8 @@ __global__ __launch_bounds__(1024) void tick_weight_amax_kernel(TickPrep p, floa
     }
 }
 // the matrices' scales: W_hh0 its own, W_ih1 and W_hh1 one between them (their products with the layer-1 operands share accumulators)
-__device__ __forceinline__ GruPow2 tick_weight_scale(const float *wmax, int m) {
-    return gru_pow2(m == 0 ? wmax[0] : fmaxf(wmax[1], wmax[2]));
+__device__ __forceinline__ Pow2 tick_weight_scale(const float *wmax, int m) {
+    return pow2_for(m == 0 ? wmax[0] : fmaxf(wmax[1], wmax[2]));
 }
 
 template <int H>
@@ -1113,8 +989,8 @@ __global__ __launch_bounds__(256) void tick_weight_prep_h2_kernel(TickPrep p, co
     const float *src = (m == 0 ? p.w[0] : m == 1 ? p.w[1] : p.w[2]) + (int64_t)(g * H + 16 * w + col) * H + 32 * ks + 8 * quad;
     const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + 4);
     const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-    f16x8g hi, lo;
-    split2_x8(x, tick_weight_scale(wmax, m).s, hi, lo);
+    f16x8 hi, lo;
+    split2_8<false>(x, tick_weight_scale(wmax, m).s, hi, lo);
     uint4 *dst = p.out + ((int64_t)((m * KS + ks) * NW + w) * 6 + g * 2) * 64 + lane;
     dst[0] = __builtin_bit_cast(uint4, hi);
     dst[64] = __builtin_bit_cast(uint4, lo);
@@ -1163,12 +1039,12 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     // load -- per-load 64-bit addresses would be hoisted out of the tick loop into 200+ VGPRs
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(packed), 0, 3 * KS * NW * 6 * 64 * 16, 0x00020000);
     const int wlane = (w * 6 * 64 + lane) * 16;
-    f16x8g wb[RS][2];
+    f16x8 wb[RS][2];
     auto fetch = [&](int gg) {                     // gg = (matrix * KS + ks) * 3 + gate, compile-time at every call site
         const int g = gg / 3, gate = gg % 3;
 #pragma unroll
         for (int term = 0; term < 2; ++term)
-            wb[gg % RS][term] = __builtin_bit_cast(f16x8g, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, (g * NW * 6 + gate * 2 + term) * 64 * 16, 0));
+            wb[gg % RS][term] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, (g * NW * 6 + gate * 2 + term) * 64 * 16, 0));
     };
 #pragma unroll
     for (int d = 0; d < PFD; ++d) fetch(d % NGG);
@@ -1219,7 +1095,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
         for (int q = 0; q < 3; ++q) acc0[q] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const f16x8g ah = lds_h8(ab + 32 * ks), al = lds_h8(ab + PLANE + 32 * ks);
+            const f16x8 ah = lds_x8<f16x8>(ab + 32 * ks), al = lds_x8<f16x8>(ab + PLANE + 32 * ks);
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const int gg = (0 * KS + ks) * 3 + q;
@@ -1265,15 +1141,15 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                 lds_barrier();
 #pragma unroll
                 for (int q = 0; q < H / 16; ++q) mx = fmaxf(mx, hmax[q]);
-                const GruPow2 sh = gru_pow2(mx);
+                const Pow2 sh = pow2_for(mx);
                 h_s = sh.s;
                 us0 = sh.inv * w0_inv;
                 us12 = sh.inv * w12_inv;
             }
 #pragma unroll
             for (int i = 0; i < E; ++i) {
-                store_split2_s(&hA0[cur][lrow(i) * HP + unit], PLANE, h0[i], h_s);
-                store_split2_s(&hA1[cur][lrow(i) * HP + unit], PLANE, h1[i], h_s);
+                store_split2<false>(&hA0[cur][lrow(i) * HP + unit], PLANE, h0[i], h_s);
+                store_split2<false>(&hA1[cur][lrow(i) * HP + unit], PLANE, h1[i], h_s);
             }
             lds_barrier();
         }
@@ -1300,8 +1176,8 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                 const float z = fast_sigmoid(gi[i][1] + az[i] * us0 + b0z);
                 const float n = fast_tanh(gi[i][2] + r * (an[i] * us0 + b0n));
                 h0[i] = (1.f - z) * n + z * h0[i];
-                store_split2_s(&hA0[cur ^ 1][lrow(i) * HP + unit], PLANE, h0[i], h_s);
-                store_split2_s(&midp[lrow(i) * HP + unit], PLANE, h0[i] * keep[i], h_s);
+                store_split2<false>(&hA0[cur ^ 1][lrow(i) * HP + unit], PLANE, h0[i], h_s);
+                store_split2<false>(&midp[lrow(i) * HP + unit], PLANE, h0[i] * keep[i], h_s);
             }
         }
         TSTAMP(2);                                             // layer 0 gates (wait for the projections) + LDS writes
@@ -1315,7 +1191,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                 const unsigned short *ab = m == 1 ? &midp[aoff] : &hA1[cur][aoff];
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    const f16x8g ah = lds_h8(ab + 32 * ks), al = lds_h8(ab + PLANE + 32 * ks);
+                    const f16x8 ah = lds_x8<f16x8>(ab + 32 * ks), al = lds_x8<f16x8>(ab + PLANE + 32 * ks);
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
                         const int gg = (m * KS + ks) * 3 + q;
@@ -1338,7 +1214,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                 const float z = fast_sigmoid(az[i] * us12 + b1z);
                 const float n = fast_tanh(ai[i] * us12 + b1in + r * (ah[i] * us12 + b1hn));
                 h1[i] = (1.f - z) * n + z * h1[i];
-                store_split2_s(&hA1[cur ^ 1][lrow(i) * HP + unit], PLANE, h1[i], h_s);
+                store_split2<false>(&hA1[cur ^ 1][lrow(i) * HP + unit], PLANE, h1[i], h_s);
                 h1f[lrow(i)][unit] = h1[i];
             }
         }

@@ -13,7 +13,8 @@
 // LDS in k-major order [BK][BM+1], from where each lane reads the single A and B value the
 // 32x32x2 MFMA wants (lane = (row|col) + 32 * k-parity) with conflict-free ds_read_b32.
 #include "common.h"
-#include "conv32_common.h"
+#include "amax.h"
+#include "conv32_common.h"       // raw buffer access
 #include "dense.h"
 #include "conv32.h"
 #include "conv_c1.h"
@@ -22,7 +23,6 @@
 
 namespace arvae {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
 
@@ -54,7 +54,7 @@ struct Epilogue {
     float *out;
     int act;
     GateOp gate = GateOp{};      // down_single_channel_mfma_kernel only: result *= act'(gate.y) * 2 gate.mask at the output location
-    unsigned *amax_out = nullptr;    // down_single_channel_mfma_kernel only: AMAX array of `out` (conv32_common.h), one writer unit per image
+    unsigned *amax_out = nullptr;    // down_single_channel_mfma_kernel only: AMAX array of `out` (amax.h), one writer unit per image
 };
 
 // gather context of a tensor position (n, y0, x0) and of a (ky, kx, channel) tap
@@ -432,7 +432,6 @@ __global__ __launch_bounds__(256) void up_single_channel_kernel(Geom g, const fl
 // (lo read exactly once, 64-byte pieces per position straight into the MFMA lane layout), then every output pixel
 // gathers its <= 16 contributions from the T image in LDS (col2im).  The lane-per-pixel version above re-reads each lo
 // pixel 16 times through L1: 1.9 ms for the Morpho-MNIST logits layer (164 MB of lo) against ~0.1 ms here.
-typedef float f32x4t __attribute__((ext_vector_type(4)));
 template <int KQ>                                            // clo = 16 * KQ
 __global__ __launch_bounds__(256) void up_single_channel_mfma_kernel(Geom g, const float *__restrict__ lo,
                                                                       const float *__restrict__ wt, Epilogue ep) {
@@ -441,7 +440,7 @@ __global__ __launch_bounds__(256) void up_single_channel_mfma_kernel(Geom g, con
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, quad = lane >> 4;
     const int taps = g.kh * g.kw, npos = g.lh * g.lw, clo = 16 * KQ;
     const int img = blockIdx.x;
-    f32x4t b[KQ];
+    f32x4 b[KQ];
 #pragma unroll
     for (int kq = 0; kq < KQ; ++kq)
 #pragma unroll
@@ -450,14 +449,14 @@ __global__ __launch_bounds__(256) void up_single_channel_mfma_kernel(Geom g, con
     const int mtiles = (npos + 15) / 16;
     // two M-tiles per round, the NEXT round's 2 * KQ loads requested before this round's MFMAs (round 5: a wave's five rounds were
     // five exposed round trips to HBM; positions past the end clamp to the last one, so the requests need no condition)
-    f32x4t a[2][KQ], an[2][KQ];
-    auto request = [&](int mt0, f32x4t (&dst)[2][KQ]) __attribute__((always_inline)) {
+    f32x4 a[2][KQ], an[2][KQ];
+    auto request = [&](int mt0, f32x4 (&dst)[2][KQ]) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int pos = 16 * (mt0 + 4 * u) + col;
             const float *src = lo_img + (int64_t)(pos < npos ? pos : npos - 1) * clo + 4 * quad;
 #pragma unroll
-            for (int kq = 0; kq < KQ; ++kq) dst[u][kq] = *reinterpret_cast<const f32x4t *>(src + 16 * kq);
+            for (int kq = 0; kq < KQ; ++kq) dst[u][kq] = *reinterpret_cast<const f32x4 *>(src + 16 * kq);
         }
     };
     request(wave, a);
@@ -467,7 +466,7 @@ __global__ __launch_bounds__(256) void up_single_channel_mfma_kernel(Geom g, con
         for (int u = 0; u < 2; ++u) {
             const int mt = mt0 + 4 * u;
             if (mt >= mtiles) break;
-            f32x4t acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kq = 0; kq < KQ; ++kq)
 #pragma unroll
@@ -571,7 +570,7 @@ __global__ __launch_bounds__(256) void down_single_channel_mfma_kernel(Geom g, O
         uint32_t ly, lx;
         g.d_lw.divmod((uint32_t)(pos < npos ? pos : npos - 1), ly, lx);
         const int y0 = (int)ly * g.stride - g.pad, x0 = (int)lx * g.stride - g.pad;
-        f32x4t acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         // keep-mask bytes / gate values of this lane's four (position, 4 channels) slots: requested before the MFMAs
         const int e_pos = lane >> 4, e_c = 4 * (lane & 15);
         unsigned mk[4], oo[4];                               // (oo: the slot's element offset in the output, OOB / 4 for none)

@@ -19,7 +19,7 @@
 #include "rng.h"
 #include "midprep.h"
 #include "midcluster.h"
-#include "conv32_common.h"
+#include "amax.h"
 #include "conv32.h"
 #include "midblock.h"
 
@@ -39,7 +39,7 @@ struct MidLayer {
     float *gpre;         // gradient w.r.t. the pre-activation [batch][n] (backward writes it for the weight gradient)
     int k, n, act;
     int kb;              // row length of mb: k rounded up to a multiple of 4 (zero-padded: the decoder's first layer reads z)
-    // round 6: the saved output / the pre-activation gradient ALSO as their three bf16 terms, planes [3][batch][n] (x3tile.h), for the
+    // round 6: the saved output / the pre-activation gradient ALSO as their three bf16 terms, planes [3][batch][n] (splitmath.h), for the
     // tile GEMMs that read them as pre-split operands (dense.hip wide_gemm_x3_kernel), or null
     unsigned short *y_planes, *g_planes;
     // ... and a wide layer's own prepared matrix for those GEMMs: planes [3][n_pad][kb_pad]
@@ -66,7 +66,7 @@ struct MidArgs {
     float beta, inv_batch, reg_scale;
     float *d_mu, *d_ls;
     // the matrices this pass streams, except the first one: requested once per XCD at the top of the kernel (mid_warm)
-    unsigned *amax_out;                              // AMAX array (conv32_common.h) of the pass's last output -- dec[nd-1].y forward,
+    unsigned *amax_out;                              // AMAX array (amax.h) of the pass's last output -- dec[nd-1].y forward,
                                                      // d_x0 backward -- for the 32-channel conv kernel that reads it next, or null
     const float *warm_ptr[2 * MID_MAX_LAYERS + 1];
     int warm_lines[2 * MID_MAX_LAYERS + 1];          // 128-byte lines
@@ -230,8 +230,8 @@ __device__ __forceinline__ float4 dact4(float4 g, float4 y, int act) {       // 
 __device__ __forceinline__ void store_planes(unsigned short *p, int64_t pstride, int rows, int row, int col, const float4 &v) {
     const int64_t idx = x3_tiled_index(rows, row, col);
     unsigned h0, m0, l0, h1, m1, l1;
-    rg_split3(v.x, v.y, h0, m0, l0);
-    rg_split3(v.z, v.w, h1, m1, l1);
+    split3(v.x, v.y, h0, m0, l0);
+    split3(v.z, v.w, h1, m1, l1);
     *reinterpret_cast<uint2 *>(p + idx) = uint2{h0, h1};
     *reinterpret_cast<uint2 *>(p + pstride + idx) = uint2{m0, m1};
     *reinterpret_cast<uint2 *>(p + 2 * pstride + idx) = uint2{l0, l1};

@@ -24,7 +24,8 @@
 #include <mutex>
 
 #include "diag.h"
-#include "conv32_common.h"
+#include "amax.h"
+#include "conv32_common.h"       // raw buffer access
 #include "midcluster.h"
 
 namespace arvae {
@@ -108,14 +109,14 @@ __device__ __forceinline__ void mc_load(const float *__restrict__ w, float4 (&wr
 // A operand: lane (g = lane / 16, r = lane % 16) holds in[row r][16 b + 4 g + j] for step j of block b (one 16-byte LDS read);
 // D: lane holds rows 4 g + j, column lane % 16.
 template <class S, int N>
-__device__ __forceinline__ void mc_mma(const float *in, int ld, const float4 (&wr)[N], f32x4v (&acc)[4]) {
+__device__ __forceinline__ void mc_mma(const float *in, int ld, const float4 (&wr)[N], f32x4 (&acc)[4]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
     if (S::T <= 8) {
         const int tile = wave % S::T, rt = tile & 1, kq = wave / S::T;
         const float *ap = in + (16 * rt + r) * ld + 16 * kq * S::NKB + 4 * g;
         // two interleaved chains (a 16x16x4 MFMA's result is 8 passes away): even / odd k blocks, summed at the end
-        acc[0] = f32x4v{0.f, 0.f, 0.f, 0.f};
-        f32x4v odd = {0.f, 0.f, 0.f, 0.f};
+        acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 odd = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < S::NKB; u += 2) {
             const float4 a = ld4(ap + 16 * u), b = ld4(ap + 16 * (u + 1));
@@ -134,7 +135,7 @@ __device__ __forceinline__ void mc_mma(const float *in, int ld, const float4 (&w
         for (int t = 0; t < S::TPW; ++t) {
             const int rt = (wave * S::TPW + t) & 1;
             const float *ap = in + (16 * rt + r) * ld + 4 * g;
-            acc[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int u = 0; u < S::KB; ++u) {
                 const float4 a = ld4(ap + 16 * u);
@@ -149,7 +150,7 @@ __device__ __forceinline__ void mc_mma(const float *in, int ld, const float4 (&w
 
 // split products (T <= 8): this wave's partial tile -> red[kq][row][col]
 template <class S>
-__device__ __forceinline__ void mc_partials(const f32x4v &acc, float *red) {
+__device__ __forceinline__ void mc_partials(const f32x4 &acc, float *red) {
     static_assert(S::T <= 8, "split products only");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
     const int tile = wave % S::T, ct = tile >> 1, rt = tile & 1, kq = wave / S::T;
@@ -283,7 +284,7 @@ __device__ __forceinline__ void st_sc1(float v, float *base, int64_t index) {
 // is a template parameter: two waves share a SIMD and 16 values per lane go through here, so every instruction per value
 // costs ~0.05 us of the pass.
 template <class S, int ACT, bool FWD>
-__device__ __forceinline__ void mc_wide_epilogue(const f32x4v (&acc)[4], const float (&bias)[4], const float (&y)[4][4], float *dst, float *own,
+__device__ __forceinline__ void mc_wide_epilogue(const f32x4 (&acc)[4], const float (&bias)[4], const float (&y)[4][4], float *dst, float *own,
                                                  int m, int row0, int valid) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
 #pragma unroll
@@ -309,7 +310,7 @@ __device__ __forceinline__ void mc_wide_epilogue(const f32x4v (&acc)[4], const f
     }
 }
 template <class S, bool FWD>
-__device__ __forceinline__ void mc_wide_epilogue_act(int act, const f32x4v (&acc)[4], const float (&bias)[4], const float (&y)[4][4], float *dst,
+__device__ __forceinline__ void mc_wide_epilogue_act(int act, const f32x4 (&acc)[4], const float (&bias)[4], const float (&y)[4][4], float *dst,
                                                      float *own, int m, int row0, int valid) {
     if (act == ARVAE_ACT_RELU) mc_wide_epilogue<S, ARVAE_ACT_RELU, FWD>(acc, bias, y, dst, own, m, row0, valid);
     else if (act == ARVAE_ACT_SELU) mc_wide_epilogue<S, ARVAE_ACT_SELU, FWD>(acc, bias, y, dst, own, m, row0, valid);
@@ -381,11 +382,11 @@ __device__ __forceinline__ void mc_up_load(const float *__restrict__ up, float4 
 #pragma unroll
     for (int u = 0; u < 8; ++u) wr[u] = ld4(up + ((int64_t)((wave * 8 + u) * 64 + lane)) * 4);
 }
-__device__ __forceinline__ void mc_up_mma(const float *win, const float4 (&wr)[8], f32x4v (&acc)[2]) {
+__device__ __forceinline__ void mc_up_mma(const float *win, const float4 (&wr)[8], f32x4 (&acc)[2]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
     const int a = wave >> 2, b = (wave >> 1) & 1;
-    acc[0] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    acc[1] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int t = u >> 1, ty = t >> 1, tx = t & 1;
@@ -415,11 +416,11 @@ __device__ __forceinline__ void mc_wgrad_tap(const float *lo512, const float *__
     const int ky = m >> 2, kx = m & 3;
     const __amdgpu_buffer_rsrc_t rs_lo = make_rsrc(lo512 + (int64_t)row0 * MC_K0, (int64_t)valid * MC_K0 * 4);
     const __amdgpu_buffer_rsrc_t rs_hi = make_rsrc(hi + (int64_t)row0 * 2048, (int64_t)valid * 2048 * 4);
-    f32x4v acc[2][2];
+    f32x4 acc[2][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int pi = 0; pi < 2; ++pi) {
         const int px = 2 * wave + pi, y = 2 * (px >> 2) - 1 + ky, x = 2 * (px & 3) - 1 + kx;
@@ -478,7 +479,7 @@ __device__ __forceinline__ void midc_forward_body(const McArgs &p, int place) {
     const int frow = tid >> 4, fc = tid & 15;                 // the output a thread finalises in a 16-column slice
     MC_STAMP(0, 0);
     float4 wa[8], wb[8];
-    f32x4v acc[4];
+    f32x4 acc[4];
     // Requests in the order their data is needed (memory returns loads in order): the conv features of the cluster's rows
     // (64 KB, eight 16-byte loads per thread) -- FOLD: the window of the conv layer that makes them, and its matrix --, enc0's
     // weights, then everything the later phases would otherwise wait for
@@ -651,7 +652,7 @@ __device__ __forceinline__ void midc_forward_body(const McArgs &p, int place) {
         if (!mc_wait(ctr, tu, p.status, MC_E_FWD, p.wait_ticks)) return;
         placed_before = mc_placed(p, m);
         mc_up_window(p.y_d2, row0, valid, m, bufA);
-        f32x4v au[2];
+        f32x4 au[2];
         mc_up_mma(bufA, wu, au);
         const int g = lane >> 4, a = wave >> 2, b = (wave >> 1) & 1, ct = wave & 1;
         const int pix = (2 * (m >> 2) + a) * 8 + 2 * (m & 3) + b;
@@ -740,7 +741,7 @@ __device__ __forceinline__ void midc_backward_body(const McArgs &p, int place) {
     const int64_t fidx = (int64_t)(row0 + (fon ? frow : 0)) * MC_H + 16 * m + fc;     // this thread's element of a 256-wide tensor
     MC_STAMP(1, 0);
     float4 wa[8], wb[8];
-    f32x4v acc[4];
+    f32x4 acc[4];
     // requests in the order of need: the arriving gradient (and, where it still has to be taken through the activation, the saved
     // output), the first product's weights, then what the later phases would otherwise wait for
     constexpr int NG = MC_R * (MC_K0 / 4) / MC_T;
@@ -954,7 +955,7 @@ __device__ __forceinline__ void midc_backward_body(const McArgs &p, int place) {
         placed_before = mc_placed(p, m);
         mc_wgrad_bias_finish(red, slab_e);
         mc_up_window(p.d_x0, row0, valid, m, bufA);
-        f32x4v au[2];
+        f32x4 au[2];
         mc_up_mma(bufA, wu, au);
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)

@@ -129,7 +129,7 @@ __device__ __forceinline__ void mid_prep_block(const MidPrepArgs &a, int block) 
             const float x0 = (n_ok && km < p.k) ? src(nf, p.kp.to_feat(km)) : 0.f;
             const float x1 = (n_ok && km + 1 < p.k) ? src(nf, p.kp.to_feat(km + 1)) : 0.f;
             unsigned h, m, l;
-            rg_split3(x0, x1, h, m, l);
+            split3(x0, x1, h, m, l);
             pl[e] = h;
             pl[e + pairs] = m;
             pl[e + 2 * pairs] = l;

@@ -8,7 +8,7 @@
 #include "midprep.h"
 #include "regloss.h"
 #include "vae_finish.h"
-#include "conv32_common.h"
+#include "amax.h"
 #include "conv32.h"
 #include "conv_c1.h"
 #include "conv64.h"
@@ -88,7 +88,7 @@ struct LayerSlots {
     // wide (64-channel, row-staged) conv layers: the split weights of both orientations ([0] Conv2d-forward, [1] transposed), made by
     // ONE launch at the start of the forward pass and used by the layer's forward and data-gradient launches
     int64_t wide[2];
-    // AMAX arrays (conv32_common.h: the partial maxima a tensor carries for the 32-channel kernels that scale it into fp16) of
+    // AMAX arrays (amax.h: the partial maxima a tensor carries for the 32-channel kernels that scale it into fp16) of
     // the output and of the gradient w.r.t. it
     int64_t amax, gamax;
 };
@@ -330,7 +330,7 @@ struct LayerBwd {
     arvae_stream_t st;
     const float *wprep;
     float *wide_prep;
-    // g_amax / in_amax: AMAX arrays (conv32_common.h) of g and of `in`, or null -- a 32-channel kernel that needs one then gets it
+    // g_amax / in_amax: AMAX arrays (amax.h) of g and of `in`, or null -- a 32-channel kernel that needs one then gets it
     // made in tmp_amax / tmp2_amax; din_amax: where the maxima of d_in go when the kernel that writes it delivers them (din_has)
     const unsigned *g_amax, *in_amax;
     unsigned *tmp_amax, *tmp2_amax, *din_amax;
@@ -802,7 +802,7 @@ extern "C" int arvae_image_vae_backward(const arvae_image_vae_t *m, int32_t batc
                   "image_vae_backward: null pointer");
     hipStream_t st = as_stream(stream);
     const View V(ws, L);
-    // AMAX array (conv32_common.h) that belongs to a gradient buffer of this pass
+    // AMAX array (amax.h) that belongs to a gradient buffer of this pass
     auto grad_amax = [&](const float *p) -> unsigned * {
         if (p == nullptr) return nullptr;
         for (int i = 0; i < m->n_enc; ++i) if (p == V.enc[i].keep) return V.enc[i].gamax;

@@ -1,24 +1,12 @@
 // The step's weight preparation as device functions, so that it can ride in another kernel's grid (conv_c1.hip pairs it with
 // the first encoder layer's launch): the scaled two-term fp16 split of the 32-channel conv weights in per-lane MFMA operand order
-// (layout: conv32_common.h) and the latent block's matrix layouts (midprep.h).
+// (the split: splitmath.h; the layout: conv32_common.h) and the latent block's matrix layouts (midprep.h).
 #pragma once
 #include "common.h"
 #include "conv32_common.h"
 #include "midprep.h"
 
 namespace arvae {
-
-// eight scaled values -> their (h, l) operand registers
-__device__ __forceinline__ void split8_h2(const float (&x)[8], float s, f16x8 &hi, f16x8 &lo) {
-    i32x4v h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        unsigned a, b;
-        split_pair_h2(x[2 * j], x[2 * j + 1], s, a, b);
-        h[j] = (int)a; l[j] = (int)b;
-    }
-    hi = __builtin_bit_cast(f16x8, h); lo = __builtin_bit_cast(f16x8, l);
-}
 
 constexpr int PREP_MAX_LAYERS = 8;
 struct PrepArgs {
@@ -64,7 +52,7 @@ __device__ __forceinline__ void conv32_prep_block(const PrepArgs &p, const int b
         dst = out + PREP_DOWN_UINT4 + (cls * PREP_UP_SLOTS + ((ty * 2 + tx) * 2 + c) * 2) * 64 + lane;
     }
     f16x8 h, l;
-    split8_h2(x, sc.s, h, l);
+    split2_8(x, sc.s, h, l);
     dst[0] = __builtin_bit_cast(uint4, h);
     dst[64] = __builtin_bit_cast(uint4, l);
 }

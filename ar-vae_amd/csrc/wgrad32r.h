@@ -15,7 +15,7 @@
 //   * zero padding: the column halo is two LDS pixels per ring row that are zeroed once; a row above / below an image is
 //     whatever the stream holds there (the neighbouring image's row), so the consumers zero the lo values of the pixels
 //     whose tap row falls outside their image instead (ky = 0 on an image's first lo row, ky = 3 on its last).
-// Same numerics as wgrad32x_kernel: scaled two-term fp16 operands (conv32_common.h), three partial products, smallest first,
+// Same numerics as wgrad32x_kernel: scaled two-term fp16 operands (splitmath.h), three partial products, smallest first,
 // fp32 accumulation, the inverse scales applied to the slab, per-workgroup slabs reduced in fixed order (reduce.hip).
 #pragma once
 #include "common.h"
@@ -76,13 +76,13 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
         const __amdgpu_buffer_rsrc_t rs_hi = make_rsrc(hi, (int64_t)n_img * RS::HW * RB);
         const __amdgpu_buffer_rsrc_t rs_lo = make_rsrc(lo, (int64_t)n_img * LO * LO * PIXB);
         float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);         // BIAS 1: lo sums, BIAS 2: hi sums, channels 4 chunk .. +3
-        // (the split: split_pair_h2, conv32_common.h -- single-issue instructions only)
+        // (the split: split2, splitmath.h -- single-issue instructions only)
         float sc_h = 1.f, sc_l = 1.f;                            // the operands' scales (set behind the first loads)
         const AmaxLoad al_h = amax_issue(amax_hi), al_l = amax_issue(amax_lo);
         auto put = [&](unsigned *dst, int plane, const float4 &v, float sc) __attribute__((always_inline)) {
             uint2 hv, lv;
-            split_pair_h2(v.x, v.y, sc, hv.x, lv.x);
-            split_pair_h2(v.z, v.w, sc, hv.y, lv.y);
+            split2(v.x, v.y, sc, hv.x, lv.x);
+            split2(v.z, v.w, sc, hv.y, lv.y);
             *reinterpret_cast<uint2 *>(dst) = hv;
             *reinterpret_cast<uint2 *>(dst + plane) = lv;
         };
@@ -206,13 +206,13 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
         auto read_block = [&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
 #pragma unroll
-            for (int t = 0; t < 2; ++t) b2[b][t] = lds_tr_f16x8(lbuf + t * LPLANE + loff[b][0], lbuf + t * LPLANE + loff[b][1]);
+            for (int t = 0; t < 2; ++t) b2[b][t] = lds_tr_x8<f16x8>(lbuf + t * LPLANE + loff[b][0], lbuf + t * LPLANE + loff[b][1]);
             const unsigned *hb = b == 0 ? hrow0 : hrow1;
 #pragma unroll
             for (int kx = 0; kx < 4; ++kx)
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
-                    a2[b][kx][t] = lds_tr_f16x8(hb + kx * HP + t * HPLANE + hcol[b][0], hb + kx * HP + t * HPLANE + hcol[b][1]);
+                    a2[b][kx][t] = lds_tr_x8<f16x8>(hb + kx * HP + t * HPLANE + hcol[b][0], hb + kx * HP + t * HPLANE + hcol[b][1]);
         };
         // tap row outside the image for this lane's 8 pixels (one lo row or part of one): their lo values become zero
         auto mask_b = [&](auto bc, int k) __attribute__((always_inline)) {
@@ -220,10 +220,9 @@ __device__ __forceinline__ void wgrad32r_body(const float *__restrict__ lo, cons
             if (wave == 0 || wave == 3) {
                 const int rimg = (RS::TR * k + (16 * b + 8 * half) / LO) & (LO - 1);
                 const bool outside = wave == 0 ? rimg == 0 : rimg == LO - 1;
-                typedef int i32x4q __attribute__((ext_vector_type(4)));
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    i32x4q v = __builtin_bit_cast(i32x4q, b2[b][t]);
+                    i32x4 v = __builtin_bit_cast(i32x4, b2[b][t]);
                     v.x = outside ? 0 : v.x; v.y = outside ? 0 : v.y; v.z = outside ? 0 : v.z; v.w = outside ? 0 : v.w;
                     b2[b][t] = __builtin_bit_cast(f16x8, v);
                 }

@@ -2,12 +2,11 @@
 // dense.hip beside the grouped Linear weight gradients): see the comment at the body.
 #pragma once
 #include "common.h"
+#include "splitmath.h"
 #include "reduce.h"
 
 namespace arvae {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int HI1 = 64, LO1 = 32, CC = 32;  // image side, feature-map side, channels of the 1 <-> 32 channel links
 
 // ================================================================================================

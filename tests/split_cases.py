@@ -1,4 +1,4 @@
-"""Case tables and the bar of the float64 accuracy tests of the split-operand MFMA kernels, shared by the GPU test
+"""Case tables and the bar of the float64 accuracy tests of the split-operand MFMA kernels (ar-vae_amd/csrc/splitmath.h), shared by the GPU test
 (test_split_kernels_float64.py) and by the CPU model that proves the bar discriminates (test_three_term_arithmetic.py).
 No test in here: the tables only.
 

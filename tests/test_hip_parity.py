@@ -627,7 +627,7 @@ def _conv32_maps_float64(hi_np, lo_np, w_np, b_np):
 @pytest.mark.parametrize('size', [16, 8, 4])
 def test_scaled_two_term_fp16_kernels_hold_fp32_accuracy_vs_float64(dev, size):
     """The 32-channel conv kernels run the fp16 MFMA on scaled two-term operands (three partial products, fp32 accumulation;
-    conv32_common.h): against a float64 reference of the same three maps their relative L2 error stays below 5e-7, i.e. fp32
+    splitmath.h): against a float64 reference of the same three maps their relative L2 error stays below 5e-7, i.e. fp32
     rounding noise -- the bar the three-term bf16 generation (rounds 1-3) and the fp32-MFMA generation before it were held to."""
     rs = np.random.RandomState(11)
     n = 24 if size == 16 else 64

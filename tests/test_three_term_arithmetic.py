@@ -1,7 +1,7 @@
-"""CPU model of the three-term bf16 arithmetic (ar-vae_amd/csrc/x3tile.h: rg_split3 and X3_MFMA6) next to the two-term fp16 model
+"""CPU model of the three-term bf16 arithmetic (ar-vae_amd/csrc/splitmath.h: split3 and X3_MFMA6) next to the two-term fp16 model
 (test_two_term_arithmetic.py), and the proof that the bar of test_split_kernels_float64.py tells a right kernel from a wrong one.
 
-rg_split3: hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round-to-nearest-even (torch.bfloat16 rounds the same way);
+split3: hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round-to-nearest-even (torch.bfloat16 rounds the same way);
 a multiply-add is the six partial products lo hi', hi lo', mid mid', mid hi', hi mid', hi hi' (each exact in fp32: 8 x 8 bits),
 accumulated in fp32.  As in the two-term model the accumulation is modelled in float64 and rounded once: what the kernels add
 on top is the fp32 summation's own error, which the sequential chain below bounds from above."""
@@ -16,7 +16,7 @@ PRODUCTS6 = {'lh': (2, 0), 'hl': (0, 2), 'mm': (1, 1), 'mh': (1, 0), 'hm': (0, 1
 
 
 def split3(x):
-    """rg_split3 on an fp32 array -> (hi, mid, lo) as float64 arrays holding bf16 values"""
+    """splitmath.h split3 on an fp32 array -> (hi, mid, lo) as float64 arrays holding bf16 values"""
     t = torch.from_numpy(np.ascontiguousarray(x, np.float32))
     hi = t.bfloat16().float()
     r = t - hi                                           # exact in fp32

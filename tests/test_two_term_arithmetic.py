@@ -1,5 +1,5 @@
 """CPU model of the arithmetic the 32-channel (and wide 64-channel) conv kernels run on the matrix pipe (ar-vae_amd/csrc/
-conv32_common.h): every operand tensor is multiplied by the power of two that brings its largest magnitude into [2^14, 2^15) and
+splitmath.h: pow2_for, split2, H2_MFMA3): every operand tensor is multiplied by the power of two that brings its largest magnitude into [2^14, 2^15) and
 split into two fp16 terms h = fp16(s x), l = fp16(s x - h); a product is the three partial products l h', h l', h h' accumulated
 in fp32, and the result is multiplied by the two inverse scales.  numpy restatement (float16 rounding is IEEE round-to-nearest-even,
 as v_cvt_pk_f16_f32): pins the error bounds DESIGN.md section 4 item 23 states, without a GPU."""

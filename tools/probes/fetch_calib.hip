@@ -13,13 +13,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef int i32x4v __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, int64_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
 }
 __device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float sum4(float4 v) { return v.x + v.y + v.z + v.w; }
