@@ -16,6 +16,7 @@
 // The weight gradients (dW_hh = dgh^T h_prev, dW_ih = dgi^T x) and the input gradients are ordinary dense launches
 // over all T*R rows afterwards (ops.py).
 #include <algorithm>
+#include <cmath>
 #include "diag.h"
 #include "common.h"
 #include "splitmath.h"
@@ -1008,10 +1009,39 @@ __device__ __forceinline__ void tick_argmax_stage(float &v, int &ix) {
     ix = take ? oi : ix;
 }
 
+// inclusive prefix sum over the 16 lanes of a DPP row, in every lane: four row shifts (lanes the shift leaves without a source add 0)
+template <int CTRL> __device__ __forceinline__ float dpp_shr_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float row16_prefix(float v) {
+    v = dpp_shr_add<0x111>(v);
+    v = dpp_shr_add<0x112>(v);
+    v = dpp_shr_add<0x114>(v);
+    return dpp_shr_add<0x118>(v);
+}
+
+// what the free-running kernel feeds back (measurevae/decoder.py:502-516): the top-1 note, or a note drawn from softmax(logits / T)
+constexpr int PICK_ARGMAX = 0, PICK_MULTINOMIAL = 1;
+// the draws of PICK_MULTINOMIAL: u [batch][ticks] in (0, 1] and 1 / T (null and unused for PICK_ARGMAX)
+struct TickSample {
+    const float *u;
+    float inv_t;
+};
+
 // (RW: batch rows per workgroup, 16 or 4 -- one element per lane and four times the workgroups, as gru_seq_fwd_h2_kernel: the gates,
 // the token's projections, the state splits and the rows' argmax are per-element work; the weight stream per workgroup is unchanged)
-template <int H, bool MASKED, int RW>
-__global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, const uint4 *__restrict__ packed) {
+//
+// PICK_MULTINOMIAL replaces the two halves of the pick, at the same two barriers.  Behind the logits a wave holds, per row, its tile's
+// 16 notes in one DPP row: it takes the tile's maximum m_c (row16_max), e_v = exp((l_v - m_c) / T) (0 for notes past the
+// vocabulary) and the 16 inclusive prefixes of e (row16_prefix), and publishes m_c, the 16 prefixes and (as the last of them) the
+// tile's sum to LDS.  Behind the barrier every lane rescales the at most four tile sums to the row's maximum M = max_c m_c
+// (s_c = exp((m_c - M) / T) <= 1, the tile that holds M keeps its e = 1: the total is >= 1), accumulates them tile by tile
+// (S_c = fma(sum_c, s_c, S_(c-1))), takes target = u * S_last, the first tile with S_c >= target, and in it the first note
+// with fma(prefix_k, s_c, S_(c-1)) >= target: lane `col` tests note `col`, the lowest set ballot bit of the row is the note.  A
+// tile's sum is the prefix of its last note INSIDE the vocabulary, so that note's test is the expression that made S_c and the
+// tile's search ends on a note that exists; S_last >= u * S_last (u clamped to [0, 1]) ends the tiles'.
+template <int H, bool MASKED, int RW, int PICK>
+__global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, const uint4 *__restrict__ packed, TickSample smp) {
     static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
     constexpr int E = RW / 4;
     constexpr int NW = H / 16, KS = H / 32, KQ = H / 16;
@@ -1027,6 +1057,8 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     __shared__ float cand_v[4][16];
     __shared__ float hmax[H / 16];
     __shared__ int cand_i[4][16];
+    __shared__ float smp_max[4][16];               // PICK_MULTINOMIAL: [tile][row] maximum, [tile][row][note] inclusive prefixes of e
+    __shared__ float smp_pre[4][16][16];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
@@ -1160,6 +1192,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
             gi[i][0] = gb[i][0] + pt[0]; gi[i][1] = gb[i][1] + pt[H]; gi[i][2] = gb[i][2] + pt[2 * H];
             keep[i] = MASKED ? p.keep_scale * (float)p.mask[((int64_t)t * B + rows[i]) * H + unit] : 1.f;
         }
+        float un[E];                                           // this tick's draws of the lane's rows (PICK_MULTINOMIAL)
+        if constexpr (PICK == PICK_MULTINOMIAL) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) un[i] = fminf(fmaxf(smp.u[(int64_t)rows[i] * ticks + t], 0.f), 1.f);
+        }
         TSTAMP(0);                                             // tick top: a beat's state; the token's projections requested
         // ---- layer 0: matrix 0 (multiplied at the end of the previous tick unless a beat starts)
         {
@@ -1239,6 +1276,23 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                     float v[E], lv[E];
                     int ix[E];
                     elems(lg, lv);
+                    if constexpr (PICK == PICK_MULTINOMIAL) {
+                        // the tile's maximum, e relative to it and e's prefixes per row; stage by stage over the rows, as below
+                        float mx[E], pre[E];
+#pragma unroll
+                        for (int i = 0; i < E; ++i) { v[i] = note_ok ? fmaxf(lv[i] + bout, 0.f) : -1.f; mx[i] = row16_max(v[i]); }
+#pragma unroll
+                        for (int i = 0; i < E; ++i) pre[i] = note_ok ? __expf((v[i] - mx[i]) * smp.inv_t) : 0.f;
+#pragma unroll
+                        for (int i = 0; i < E; ++i) pre[i] = row16_prefix(pre[i]);
+#pragma unroll
+                        for (int i = 0; i < E; ++i) smp_pre[w][lrow(i)][col] = pre[i];
+                        if (col == 0) {
+#pragma unroll
+                            for (int i = 0; i < E; ++i) smp_max[w][lrow(i)] = mx[i];
+                        }
+                        return;
+                    }
 #pragma unroll
                     for (int i = 0; i < E; ++i) { v[i] = note_ok ? fmaxf(lv[i] + bout, 0.f) : -1.f; ix[i] = note; }
 #pragma unroll
@@ -1276,20 +1330,63 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
         }
         TSTAMP(6);                                             // barrier + logits / argmax (first waves) + the next tick's layer 0
         lds_barrier();
+        if constexpr (PICK == PICK_MULTINOMIAL) {
+            // tile sums rescaled to the row's maximum -> the tile, then the note inside it (one lane per note, the quad's ballot bits)
+            int tile[E];
+            float base[E], scale[E], target[E];
 #pragma unroll
-        for (int i = 0; i < E; ++i) {
-            const int r = lrow(i);
-            float v = cand_v[0][r];
-            int ix = cand_i[0][r];
-            for (int c = 1; c < ntile; ++c) {
-                const float ov = cand_v[c][r];
-                const int oi = cand_i[c][r];
-                const bool take = ov > v;                      // later tiles hold larger indices: ties keep the earlier
-                v = take ? ov : v;
-                ix = take ? oi : ix;
+            for (int i = 0; i < E; ++i) {
+                const int r = lrow(i);
+                float m[4], sum[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const bool on = c < ntile;
+                    m[c] = on ? smp_max[c][r] : -1.f;
+                    sum[c] = on ? smp_pre[c][r][min(15, p.vocab - 1 - 16 * c)] : 0.f;    // the tile's last note's own prefix
+                }
+                const float big = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
+                float sc[4], run[5];
+                run[0] = 0.f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    sc[c] = __expf((m[c] - big) * smp.inv_t);
+                    run[c + 1] = __builtin_fmaf(sum[c], sc[c], run[c]);
+                }
+                target[i] = un[i] * run[4];                    // (tiles past the vocabulary add 0: run[4] is the last live tile's)
+                tile[i] = 0; base[i] = run[0]; scale[i] = sc[0];
+#pragma unroll
+                for (int c = 1; c < 4; ++c) {
+                    const bool next = run[c] < target[i];      // tile c - 1 ends below the target: the note lies further on
+                    tile[i] = next ? c : tile[i];
+                    base[i] = next ? run[c] : base[i];
+                    scale[i] = next ? sc[c] : scale[i];
+                }
             }
-            tok[i] = ix;
-            if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const float ck = __builtin_fmaf(smp_pre[tile[i]][lrow(i)][col], scale[i], base[i]);
+                const unsigned long long reached = __ballot(ck >= target[i]);
+                // (a row whose logits are not finite compares false everywhere: clamped to a note that exists)
+                const int ix = min(max(16 * tile[i] + __ffs((int)((unsigned)(reached >> (16 * quad)) & 0xffffu)) - 1, 0), p.vocab - 1);
+                tok[i] = ix;
+                if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const int r = lrow(i);
+                float v = cand_v[0][r];
+                int ix = cand_i[0][r];
+                for (int c = 1; c < ntile; ++c) {
+                    const float ov = cand_v[c][r];
+                    const int oi = cand_i[c][r];
+                    const bool take = ov > v;                  // later tiles hold larger indices: ties keep the earlier
+                    v = take ? ov : v;
+                    ix = take ? oi : ix;
+                }
+                tok[i] = ix;
+                if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+            }
         }
         TSTAMP(7);                                             // barrier + the tiles' candidates -> token
     }
@@ -1421,10 +1518,11 @@ extern "C" int arvae_tick_free_run_supported(int32_t hidden, int32_t vocab) {
     return arvae_gru_seq_supported(hidden) && vocab >= 1 && vocab <= 64 && vocab <= 16 * (hidden / 16);
 }
 
-extern "C" int arvae_tick_free_run(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride, const float *gib,
-                                   const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
-                                   int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int64_t *tokens, float *ws,
-                                   arvae_stream_t stream) {
+// uniforms null: the top-1 note is fed back; else a note drawn at uniforms [batch][ticks] from softmax(logits * inv_temperature)
+static int tick_free_run_launch(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride, const float *gib,
+                                const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
+                                int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
+                                int64_t *tokens, float *ws, arvae_stream_t stream) {
     ARVAE_REQUIRE(wts && h0_l0 && h0_l1 && gib && ptab && tokens, "tick_free_run: null pointer");
     ARVAE_REQUIRE(wts->w_hh0 && wts->b_hh0 && wts->w_ih1 && wts->b_ih1 && wts->w_hh1 && wts->b_hh1 && wts->w_out && wts->b_out,
                   "tick_free_run: null weight pointer");
@@ -1455,11 +1553,17 @@ extern "C" int arvae_tick_free_run(const arvae_tick_weights_t *wts, const float 
     const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
     const int rw = gru_rows_per_wg(batch, 1);
     const dim3 gr((batch + rw - 1) / rw);
+    const TickSample smp{uniforms, inv_temperature};
+#define TICK_H2_PICK(HH, MM, RWV, PICK)                                                                                          \
+    {                                                                                                                        \
+        if ((RWV) == 4) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 4, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);    \
+        else if ((RWV) == 8) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 8, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp); \
+        else ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 16, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);              \
+    }
 #define TICK_H2_RW(HH, MM, RWV)                                                                                                  \
     {                                                                                                                        \
-        if ((RWV) == 4) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 4>), gr, dim3(4 * HH), 0, st, p, packed);               \
-        else if ((RWV) == 8) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 8>), gr, dim3(4 * HH), 0, st, p, packed);          \
-        else ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, 16>), gr, dim3(4 * HH), 0, st, p, packed);                         \
+        if (uniforms != nullptr) TICK_H2_PICK(HH, MM, RWV, PICK_MULTINOMIAL)                                                 \
+        else TICK_H2_PICK(HH, MM, RWV, PICK_ARGMAX)                                                                          \
     }
 #define TICK_H2(HH)                                                                                                              \
     {                                                                                                                        \
@@ -1474,7 +1578,28 @@ extern "C" int arvae_tick_free_run(const arvae_tick_weights_t *wts, const float 
     else TICK_H2(32)
 #undef TICK_H2
 #undef TICK_H2_RW
+#undef TICK_H2_PICK
     return check_launch("tick_free_run_h2_kernel");
+}
+
+extern "C" int arvae_tick_free_run(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride, const float *gib,
+                                   const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
+                                   int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int64_t *tokens, float *ws,
+                                   arvae_stream_t stream) {
+    return tick_free_run_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, hidden, vocab,
+                                nullptr, 1.f, tokens, ws, stream);
+}
+
+extern "C" int arvae_tick_free_run_sampled(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                           const float *gib, const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch,
+                                           int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
+                                           float inv_temperature, int64_t *tokens, float *ws, arvae_stream_t stream) {
+    ARVAE_REQUIRE(uniforms != nullptr, "tick_free_run_sampled: null uniforms");
+    ARVAE_REQUIRE(ws != nullptr, "tick_free_run_sampled: the sampled pass needs the workspace (arvae_tick_free_run_ws_floats)");
+    ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
+                  "tick_free_run_sampled: inverse temperature %f is not a positive finite number", (double)inv_temperature);
+    return tick_free_run_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, hidden, vocab,
+                                uniforms, inv_temperature, tokens, ws, stream);
 }
 
 #ifdef ARVAE_GRU_STAMPS

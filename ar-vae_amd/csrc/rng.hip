@@ -9,6 +9,11 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(float *__restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) out[i] = rng_normal(s, (uint64_t)i);
 }
 
+__global__ __launch_bounds__(256) void philox_uniform_kernel(float *__restrict__ out, int64_t count, RngStream s) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256)
+        out[i] = rng_unit(rng_block(s, (uint64_t)i).x);
+}
+
 // sixteen mask bytes per Philox block: byte j of the block's 128 bits keeps its element when the byte is < threshold
 // (keep probability quantised to 1/256: exact for the reference's p = 0.5)
 __global__ __launch_bounds__(256) void philox_keep_mask_kernel(uint8_t *__restrict__ out, int64_t count, uint32_t threshold, RngStream s) {
@@ -126,6 +131,15 @@ extern "C" int arvae_philox_normal(float *out, int64_t count, uint64_t seed, uin
     if (blocks > 2048) blocks = 2048;
     ARVAE_LAUNCH(philox_normal_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), out, count, RngStream{seed, offset, dev_step, step});
     return check_launch("philox_normal_kernel");
+}
+
+extern "C" int arvae_philox_uniform(float *out, int64_t count, uint64_t seed, uint32_t offset, uint32_t step, const uint32_t *dev_step,
+                                    arvae_stream_t stream) {
+    ARVAE_REQUIRE(out != nullptr && count > 0, "philox_uniform: bad argument");
+    int64_t blocks = (count + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    ARVAE_LAUNCH(philox_uniform_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), out, count, RngStream{seed, offset, dev_step, step});
+    return check_launch("philox_uniform_kernel");
 }
 
 extern "C" int arvae_philox_keep_mask(uint8_t *out, int64_t count, float keep_prob, uint64_t seed, uint32_t offset, uint32_t step,

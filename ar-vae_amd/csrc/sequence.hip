@@ -5,6 +5,7 @@
 // GRU cell (PyTorch gate order r, z, n stacked in rows; reference measurevae/encoder.py:27-34,
 // measurevae/decoder.py:338-368 via nn.GRU):
 //     r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r * gh_n);  h' = (1-z)*n + z*h
+#include <cmath>
 #include "common.h"
 #include "attributes.h"
 #include "sequence.h"
@@ -326,6 +327,29 @@ __global__ __launch_bounds__(256) void row_argmax_kernel(const float *__restrict
     }
 }
 
+// idx[b] = the note drawn from softmax(w[b] * inv_t) at the uniform u[b] in (0, 1] (reference decoder.py:502-505 torch.multinomial of the
+// softmax, the draw an explicit input): with e_j = exp((w[b][j] - max_j w[b][j]) * inv_t) and C_k = e_0 + ... + e_k summed in index
+// order, the smallest k with C_k >= u[b] * C_{cols-1}.  The second walk repeats the first one's additions, so its last prefix IS the
+// total and the search always ends inside the row.
+__global__ __launch_bounds__(256) void row_sample_kernel(const float *__restrict__ w, int rows, int cols, const float *__restrict__ u,
+                                                          float inv_t, int64_t *__restrict__ idx) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) {
+        const float *row = w + (int64_t)r * cols;
+        float mx = row[0];
+        for (int j = 1; j < cols; ++j) mx = fmaxf(mx, row[j]);
+        float total = 0.f;
+        for (int j = 0; j < cols; ++j) total += expf((row[j] - mx) * inv_t);
+        const float target = u[r] * total;
+        float c = 0.f;
+        int arg = cols - 1;
+        for (int j = 0; j < cols; ++j) {
+            c += expf((row[j] - mx) * inv_t);
+            if (c >= target) { arg = j; break; }
+        }
+        idx[r] = arg;
+    }
+}
+
 // out[r] = [a[r] | b[r]]  and the adjoint split
 __global__ __launch_bounds__(256) void concat_cols_kernel(const float *__restrict__ a, const float *__restrict__ b, int64_t rows,
                                                            int ca, int cb, float *__restrict__ out) {
@@ -520,6 +544,15 @@ extern "C" int arvae_row_argmax(const float *w, int32_t rows, int32_t cols, int6
     ARVAE_REQUIRE(w && idx && rows > 0 && cols > 0, "row_argmax: bad argument");
     ARVAE_LAUNCH(row_argmax_kernel, dim3(blocks_for(rows)), dim3(256), 0, as_stream(stream), w, rows, cols, idx);
     return check_launch("row_argmax_kernel");
+}
+
+extern "C" int arvae_row_sample(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature, int64_t *idx,
+                                arvae_stream_t stream) {
+    ARVAE_REQUIRE(w && u && idx && rows > 0 && cols > 0, "row_sample: bad argument");
+    ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f, "row_sample: inverse temperature %f is not a positive finite number",
+                  (double)inv_temperature);
+    ARVAE_LAUNCH(row_sample_kernel, dim3(blocks_for(rows)), dim3(256), 0, as_stream(stream), w, rows, cols, u, inv_temperature, idx);
+    return check_launch("row_sample_kernel");
 }
 
 extern "C" int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,

@@ -249,9 +249,11 @@ class HierarchicalDecoder(Decoder):
         self.tick_emb_to_note_emb = _dense_layer(h, num_notes)
         self.use_teacher_forcing = True
         self.teacher_forcing_prob = 0.5
-        self.sampling = 'argmax'
+        self.sampling = 'argmax'                               # or 'multinomial' (decoder.py:372,431-434,502-505)
+        self.temperature = 1.0                                 # softmax(probs / temperature); 1 = the reference's softmax(probs)
         self.xavier_initialization()
         self._mask_queue = deque()
+        self._uniform_queue = deque()
 
     def __repr__(self):
         return f'{self.name}{self.note_embedding_dim},{self.rnn_class},{self.num_layers},{self.rnn_hidden_size},{self.dropout},)'
@@ -259,6 +261,21 @@ class HierarchicalDecoder(Decoder):
     def push_dropout_masks(self, beat_mask, tick_mask):
         """explicit keep-masks (4, B, H) and (24, B, H) uint8 for the layer-0 hidden states."""
         self._mask_queue.append((beat_mask, tick_mask))
+
+    def push_sampling_uniforms(self, u):
+        """explicit draws (B, 24) float32 in (0, 1] for the next forward that samples (sampling == 'multinomial', train, not
+        teacher-forced): tick t of row b takes the smallest note whose softmax CDF reaches u[b, t]."""
+        self._uniform_queue.append(u)
+
+    def _sampling_uniforms(self, b, device):
+        """the (B, 24) draws of one sampled forward: the pushed buffer, else ONE launch of the library's generator (one offset)"""
+        ticks = 24
+        if self._uniform_queue:
+            u = self._uniform_queue.popleft().to(device=device, dtype=torch.float32).contiguous()
+            if tuple(u.shape) != (b, ticks):
+                raise ValueError(f'sampling uniforms must be ({b}, {ticks}), got {tuple(u.shape)}')
+            return u
+        return ops.philox_uniform((b, ticks), device)
 
     def hidden_init(self, inp, rnn_type):
         """(B, feats) -> [layer-0 hidden, layer-1 hidden]  (view(B, 2, H).transpose(0, 1), decoder.py:388-406)."""
@@ -294,9 +311,15 @@ class HierarchicalDecoder(Decoder):
             teacher_forced = torch.rand(1).item() < self.teacher_forcing_prob       # host coin (decoder.py:427-428)
         else:
             teacher_forced = False
-        if train and self.sampling != 'argmax':
-            raise NotImplementedError('only argmax sampling is implemented')
+        if self.sampling not in ('argmax', 'multinomial'):
+            raise NotImplementedError(f'sampling {self.sampling!r}: argmax and multinomial are implemented')
+        if not self.temperature > 0:
+            raise ValueError('the sampling temperature must be positive')
+        sampling = self.sampling if train else 'argmax'        # decoder.py:431-434
         b = z.size(0)
+        uniforms = None                                        # drawn only by a forward that samples: argmax consumes no offset
+        if sampling == 'multinomial' and not teacher_forced:
+            uniforms = self._sampling_uniforms(b, z.device)
         masks = (None, None)
         if self.training and self.dropout > 0:
             if self._mask_queue:
@@ -307,9 +330,28 @@ class HierarchicalDecoder(Decoder):
                 masks = (both[:4], both[4:])
         if _use_sequence_kernels(self.rnn_hidden_size):
             beat_out = self.beat_rnn_sequence(z, 4, masks[0])
-            return self.tick_rnn_sequence(score_tensor, beat_out, 6, teacher_forced, masks[1])
+            return self.tick_rnn_sequence(score_tensor, beat_out, 6, teacher_forced, masks[1], uniforms)
         beat_out = self.forward_beat_rnn(z, 4, masks[0])
-        return self.forward_tick_rnn(score_tensor, beat_out, 6, teacher_forced, 'argmax', masks[1])
+        return self.forward_tick_rnn(score_tensor, beat_out, 6, teacher_forced, sampling, masks[1], uniforms)
+
+    def generate(self, z, sampling='multinomial', temperature=1.0, uniforms=None):
+        """Free-running decode of latent codes z (B, z_dim) without autograd and with dropout off: -> (weights (B, 24, V), samples
+        (B, 1, 24)).  sampling 'multinomial' draws every fed-back note from softmax(probs / temperature) (uniforms: explicit (B, 24)
+        draws in (0, 1], else one launch of the library's generator); 'argmax' feeds the top-1 note back."""
+        if sampling not in ('argmax', 'multinomial'):
+            raise NotImplementedError(f'sampling {sampling!r}: argmax and multinomial are implemented')
+        dummy = torch.zeros(z.size(0), 24, dtype=torch.int64, device=z.device)
+        saved = (self.sampling, self.temperature, self.use_teacher_forcing, self.training)
+        self.sampling, self.temperature, self.use_teacher_forcing = sampling, float(temperature), False
+        self.train(False)
+        try:
+            if uniforms is not None and sampling == 'multinomial':
+                self.push_sampling_uniforms(uniforms)
+            with torch.no_grad():
+                return self.forward(z, dummy, sampling == 'multinomial')      # train=True is what lets `sampling` apply
+        finally:
+            self.sampling, self.temperature, self.use_teacher_forcing = saved[:3]
+            self.train(saved[3])
 
     # ---- whole-sequence path ------------------------------------------------------------------------------------
     def _two_layer_sequence(self, rnn, steps, gi0, h0, mask):
@@ -335,12 +377,12 @@ class HierarchicalDecoder(Decoder):
         m = None if mask is None else mask.contiguous().view(seq_len * b, -1)
         return self._two_layer_sequence(self.rnn_beat, seq_len, gi0, h, m)
 
-    def tick_rnn_sequence(self, score_tensor, beat_out, tick_seq_len, teacher_forced, mask=None):
+    def tick_rnn_sequence(self, score_tensor, beat_out, tick_seq_len, teacher_forced, mask=None, uniforms=None):
         """The tick RNN restarts from a beat-dependent hidden state at every beat (decoder.py:459-525), so given the
         fed-back tokens the four beats are independent 6-step sequences: they run as ONE sequence launch per layer over
         4*B rows (row = beat*B + b).  With teacher forcing the fed-back tokens are the score; otherwise they come from
         the free-running pass `_free_running_tokens` (argmax is not differentiated, decoder.py:506-516), and the same
-        graph is then evaluated on those tokens."""
+        graph is then evaluated on those tokens.  uniforms (B, 24): the fed-back notes are drawn (decoder.py:502-505)."""
         nb, b = beat_out.shape[0], beat_out.shape[1]
         hid, steps = self.rnn_hidden_size, tick_seq_len
         ticks = nb * steps
@@ -360,7 +402,7 @@ class HierarchicalDecoder(Decoder):
             tokens = score_tensor
         else:
             with torch.no_grad():
-                tokens = self._free_running_tokens(beat_out.detach(), h0, beat_emb, mask)
+                tokens = self._free_running_tokens(beat_out.detach(), h0, beat_emb, mask, uniforms)
         w_ih0, _, b_ih0, _ = self.rnn_tick.cell(0)
         if (3 * hid) % 4 == 0 and (self.num_notes + 1) * 1024 + (steps * nb * b + 15) // 16 * 8 <= 65536:    # (the segment sum's LDS)
             # layer-0 input projection by lookup: W_ih0 applied once to the vocabulary's embeddings, x_0 and the beat embeddings
@@ -377,8 +419,9 @@ class HierarchicalDecoder(Decoder):
         weights = probs.view(steps, nb, b, -1).permute(2, 1, 0, 3).reshape(b, ticks, -1)       # tick = 6*beat + j
         return weights, tokens[:, None, :]
 
-    def _free_running_tokens(self, beat_out, h0, beat_emb, mask):
-        """argmax-feedback pass (no autograd): the tokens the decoder feeds itself, int64 (B, 24)."""
+    def _free_running_tokens(self, beat_out, h0, beat_emb, mask, uniforms=None):
+        """feedback pass (no autograd): the tokens the decoder feeds itself, int64 (B, 24): the top-1 note, or with uniforms
+        (B, 24) the note drawn from softmax(probs / temperature) at that tick's uniform."""
         nb, b = beat_out.shape[0], beat_out.shape[1]
         hid = self.rnn_hidden_size
         w_ih0, w_hh0, b_ih0, b_hh0 = self.rnn_tick.cell(0)
@@ -394,7 +437,8 @@ class HierarchicalDecoder(Decoder):
             out = self.tick_emb_to_note_emb[0]
             weights = tuple(t.detach() for t in (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias))
             return ops.tick_free_run(weights, h0[0].detach(), h0[1].detach(), gib, ptab,
-                                     None if mask is None else mask.contiguous(), 1.0 / (1.0 - self.dropout), b, nb, 6)
+                                     None if mask is None else mask.contiguous(), 1.0 / (1.0 - self.dropout), b, nb, 6,
+                                     uniforms=uniforms, temperature=self.temperature)
         prev = self.x_0.detach()[None].expand(b, -1).contiguous()
         tokens = []
         for i in range(nb):
@@ -404,7 +448,8 @@ class HierarchicalDecoder(Decoder):
                 t = i * 6 + j
                 gi0 = ops.dense(ops.concat_cols(prev, be), w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
                 h = self._two_layer_step(self.rnn_tick, gi0, h, None if mask is None else mask[t].contiguous())
-                idx = ops.row_argmax(_lin(h[1], self.tick_emb_to_note_emb[0], ACT_RELU))
+                probs = _lin(h[1], self.tick_emb_to_note_emb[0], ACT_RELU)
+                idx = ops.row_argmax(probs) if uniforms is None else ops.row_sample(probs, uniforms[:, t].contiguous(), self.temperature)
                 prev = ops.embed(idx.view(b, 1), self.note_embedding_layer.weight).view(b, -1)
                 tokens.append(idx)
         return torch.stack(tokens, 1)
@@ -421,8 +466,12 @@ class HierarchicalDecoder(Decoder):
             out.append(h[1])
         return out
 
-    def forward_tick_rnn(self, score_tensor, beat_rnn_out, tick_seq_len, teacher_forced, sampling, mask=None):
+    def forward_tick_rnn(self, score_tensor, beat_rnn_out, tick_seq_len, teacher_forced, sampling, mask=None, uniforms=None):
+        if sampling not in ('argmax', 'multinomial'):
+            raise NotImplementedError(f'sampling {sampling!r}: argmax and multinomial are implemented')
         b = score_tensor.size(0)
+        if sampling == 'multinomial' and uniforms is None and not (self.use_teacher_forcing and teacher_forced):
+            uniforms = self._sampling_uniforms(b, score_tensor.device)
         w_ih0, _, b_ih0, _ = self.rnn_tick.cell(0)
         prev = ops.broadcast_rows(self.x_0, b)                             # learned start embedding
         weights, samples = [], []
@@ -437,6 +486,8 @@ class HierarchicalDecoder(Decoder):
                 probs = _lin(h[1], self.tick_emb_to_note_emb[0], ACT_RELU)
                 if self.use_teacher_forcing and teacher_forced:
                     idx = score_tensor[:, t].contiguous()
+                elif sampling == 'multinomial':
+                    idx = ops.row_sample(probs.detach(), uniforms[:, t].contiguous(), self.temperature)
                 else:
                     idx = ops.row_argmax(probs.detach())
                 prev = ops.embed(idx.view(b, 1), self.note_embedding_layer.weight).view(b, -1)   # carries across beats
@@ -517,3 +568,18 @@ class MeasureVAE(Model):
         z_prior = ops.normal_noise(mu.shape, mu.device) if need_prior_sample else None     # the reference's second, unused draw
         weights, samples = self.decoder(z=z_tilde, score_tensor=measure_score_tensor, train=train)
         return weights, samples, z_dist, prior_dist, z_tilde, z_prior
+
+    def forward_test(self, measure_score_tensor):
+        """(B, M, 24) -> weights (B, M, 24, V), samples (B, 1, 24*M): every measure encoded, its code drawn, and decoded free-running
+        with train=False, as the reference (measure_vae.py:133-166) -- there one encoder and one decoder call per measure, here ONE of
+        each over the M*B rows in measure-major order (row = m*B + b), so that a pushed (M*B, Z) noise is the reference's draw order."""
+        b, m, ticks = measure_score_tensor.shape
+        if ticks != self.num_ticks_per_measure:
+            raise AssertionError('a measure has 24 ticks')
+        rows = measure_score_tensor.transpose(0, 1).reshape(m * b, ticks).contiguous()
+        z_tilde = self.encoder(rows)._arvae_sample
+        dummy = torch.zeros(m * b, ticks, dtype=torch.int64, device=rows.device)
+        weights, samples = self.decoder(z=z_tilde, score_tensor=dummy, train=False)
+        weights = weights.view(m, b, ticks, -1).transpose(0, 1).contiguous()
+        samples = samples.view(m, b, ticks).transpose(0, 1).reshape(b, 1, m * ticks)
+        return weights, samples

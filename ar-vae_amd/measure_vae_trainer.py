@@ -130,7 +130,7 @@ class MeasureVAETrainer(Trainer):
         from .fused_measure import FusedMeasureVAE
         from .measure_vae import _use_sequence_kernels
         reg_dims = tuple(self.reg_dim) if self.use_reg_loss else ()
-        key = (reg_dims, float(self.beta), float(self.gamma), float(self.delta))
+        key = (reg_dims, float(self.beta), float(self.gamma), float(self.delta), self.model.decoder.sampling)
         if self._fused is None or self._fused[0] != key:
             usable = (_use_sequence_kernels(self.model.encoder.rnn_hidden_size) and next(self.model.parameters()).is_cuda
                       and FusedMeasureVAE.supports(self.model, self.optimizer, reg_dims) is None)
@@ -269,17 +269,28 @@ class MeasureVAETrainer(Trainer):
             json.dump(self.metrics, f, indent=2)
         return self.metrics
 
-    def decode_latent_codes(self, latent_codes):
+    def decode_latent_codes(self, latent_codes, sampling='argmax', temperature=1.0, uniforms=None):
         """(n, z_dim) latent codes -> (music21 score or None, note indices (n, 1, 24) int64): the decoder alone, free-running
         (measure_vae_trainer.py:281-288).  The score object needs the dataset's music21 converter (`tensor_to_m21score`);
-        datasets without one (the device-resident loaders here) give None."""
+        datasets without one (the device-resident loaders here) give None.  sampling='multinomial': every fed-back note is drawn
+        from softmax(probs / temperature) (HierarchicalDecoder.generate; uniforms: explicit (n, 24) draws) instead of the top-1."""
         dev = next(self.model.parameters()).device
         z = torch.as_tensor(latent_codes, dtype=torch.float32, device=dev).contiguous()
-        dummy = torch.zeros(z.size(0), self.model.num_ticks_per_measure, dtype=torch.int64, device=dev)
-        with torch.no_grad():
-            _, tensor_score = self.model.decoder(z, dummy, False)
+        if sampling == 'argmax':
+            dummy = torch.zeros(z.size(0), self.model.num_ticks_per_measure, dtype=torch.int64, device=dev)
+            with torch.no_grad():
+                _, tensor_score = self.model.decoder(z, dummy, False)
+        else:
+            _, tensor_score = self.model.decoder.generate(z, sampling=sampling, temperature=temperature, uniforms=uniforms)
         to_score = getattr(self.dataset, 'tensor_to_m21score', None)
         return (to_score(tensor_score) if callable(to_score) else None), tensor_score
+
+    def sample_measures(self, num, temperature=1.0):
+        """num measures drawn from the model: z ~ N(0, I) from the library's generator, every note drawn from
+        softmax(probs / temperature).  -> (music21 score or None, note indices (num, 1, 24) int64)"""
+        dev = next(self.model.parameters()).device
+        z = ops.normal_noise((int(num), self.model.latent_space_dim), dev)
+        return self.decode_latent_codes(z, sampling='multinomial', temperature=temperature)
 
     def compute_latent_interpolations(self, latent_code, original_score=None, dim1=0, num_points=5):
         """Sweep latent dimension dim1 over [-4, 4] (measure_vae_trainer.py:290-308): all num_points codes are decoded in ONE

@@ -802,20 +802,35 @@ def tick_free_run_supported(hidden, vocab):
     return bool(_lib.load().arvae_tick_free_run_supported(int(hidden), int(vocab)))
 
 
-def tick_free_run(weights, h0_l0, h0_l1, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat):
+def tick_free_run(weights, h0_l0, h0_l1, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, uniforms=None, temperature=1.0):
     """tokens (B, beats*ticks_per_beat) int64 of the free-running tick decoder; no autograd (csrc/gru_seq.hip).
-    weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, w_out, b_out)."""
-    _dev(*weights, h0_l0, h0_l1, gib, ptab, mask)
+    weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, w_out, b_out).
+    uniforms None: the top-1 note is fed back (arvae_tick_free_run).  uniforms (B, beats*ticks_per_beat) float32 in (0, 1]: the note
+    drawn from softmax(logits / temperature) by inverting its CDF at that tick's uniform (arvae_tick_free_run_sampled)."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab, mask, uniforms)
     lib = _lib.load()
     hid, vocab = weights[0].shape[1], weights[6].shape[0]
     tw = _lib.TickWeights(*[_ptr(t) for t in weights])
     tokens = torch.empty(batch, beats * ticks_per_beat, device=gib.device, dtype=torch.int64)
     ws = torch.empty(lib.arvae_tick_free_run_ws_floats(hid), device=gib.device, dtype=torch.float32)
     with _timed('tick_free_run', 2.0 * batch * beats * ticks_per_beat * (9 * hid * hid + vocab * hid), 0.0):
-        _lib.check(lib.arvae_tick_free_run(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), _ptr(mask),
-                                           float(keep_scale), batch, beats, ticks_per_beat, hid, vocab, _ptr(tokens),
-                                           _ptr(ws), _stream()), 'tick_free_run')
+        if uniforms is None:
+            _lib.check(lib.arvae_tick_free_run(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), _ptr(mask),
+                                               float(keep_scale), batch, beats, ticks_per_beat, hid, vocab, _ptr(tokens),
+                                               _ptr(ws), _stream()), 'tick_free_run')
+        else:
+            u = _sampling_uniforms(uniforms, (batch, beats * ticks_per_beat))
+            _lib.check(lib.arvae_tick_free_run_sampled(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), _ptr(mask),
+                                                       float(keep_scale), batch, beats, ticks_per_beat, hid, vocab, _ptr(u),
+                                                       1.0 / float(temperature), _ptr(tokens), _ptr(ws), _stream()),
+                       'tick_free_run_sampled')
     return tokens
+
+
+def _sampling_uniforms(u, shape):
+    if u.dtype != torch.float32 or tuple(u.shape) != tuple(shape):
+        raise ValueError(f'sampling uniforms must be float32 of shape {tuple(shape)}, got {u.dtype} {tuple(u.shape)}')
+    return u.contiguous()
 
 
 class _EmbedFn(Function):
@@ -935,6 +950,19 @@ def row_argmax(w):
     w = w.contiguous()
     idx = torch.empty(w.shape[0], device=w.device, dtype=torch.int64)
     _lib.check(lib.arvae_row_argmax(_ptr(w), w.shape[0], w.shape[1], _ptr(idx), _stream()), 'row_argmax')
+    return idx
+
+
+def row_sample(w, u, temperature=1.0):
+    """one index per row of a [rows, cols] tensor of logits, drawn from softmax(w / temperature) by inverting its CDF at u [rows] in
+    (0, 1] (the decoder's multinomial feedback, measurevae/decoder.py:502-505, with the draw an explicit input); int64 [rows]."""
+    _dev(w, u)
+    lib = _lib.load()
+    w = w.contiguous()
+    u = _sampling_uniforms(u, (w.shape[0],))
+    idx = torch.empty(w.shape[0], device=w.device, dtype=torch.int64)
+    _lib.check(lib.arvae_row_sample(_ptr(w), w.shape[0], w.shape[1], _ptr(u), 1.0 / float(temperature), _ptr(idx), _stream()),
+               'row_sample')
     return idx
 
 
@@ -1123,6 +1151,15 @@ def normal_noise(shape, device):
     _dev(out)
     _lib.check(_lib.load().arvae_philox_normal(_ptr(out), out.numel(), rng_seed(), rng_next_offset(), 0,
                                                 _ptr(rng_device_step(device)), _stream()), 'philox_normal')
+    return out
+
+
+def philox_uniform(shape, device):
+    """u in (0, 1], one per element, for the decoder's multinomial feedback (measurevae/decoder.py:502-505): one library launch"""
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    _dev(out)
+    _lib.check(_lib.load().arvae_philox_uniform(_ptr(out), out.numel(), rng_seed(), rng_next_offset(), 0,
+                                                 _ptr(rng_device_step(device)), _stream()), 'philox_uniform')
     return out
 
 

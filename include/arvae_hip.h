@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 13  /* 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 14  /* 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -310,6 +310,16 @@ int arvae_tick_free_run(const arvae_tick_weights_t *weights, const float *h0_l0,
                         const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
                         int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int64_t *tokens, float *ws,
                         arvae_stream_t stream);
+/* The same pass with MULTINOMIAL feedback (decoder.sampling == 'multinomial', measurevae/decoder.py:431-434,502-505:
+ * torch.multinomial(softmax(probs), 1) is the next input), the draw an explicit input: uniforms [batch][beats*ticks_per_beat] in (0, 1]
+ * (arvae_philox_uniform, or the caller's own).  With l_v = relu(W_out h1 + b_out)_v, e_v = exp((l_v - max_v l_v) * inv_temperature) and
+ * C_k = sum_{v <= k} e_v, the note of a row at a tick is the smallest k with C_k >= u * C_{vocab-1}; inv_temperature = 1 is the
+ * reference's softmax(probs).  The total is the last prefix value itself, so a note in [0, vocab) always exists.  Needs the
+ * workspace (ws == NULL: ARVAE_E_INVALID); same shapes as arvae_tick_free_run_supported. */
+int arvae_tick_free_run_sampled(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1, int64_t h0_stride /* 0 = hidden */,
+                                const float *gib, const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
+                                int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
+                                int64_t *tokens, float *ws, arvae_stream_t stream);
 
 /* nn.Embedding (measurevae/encoder.py:36-37,111; decoder.py:18,516): out row (b,t) = table[idx[b][t]];
  * time_major: rows ordered (t, b) instead of (b, t).  embed_bwd adds to (accumulate != 0) or overwrites dtable, in a fixed summation order, and needs
@@ -348,6 +358,11 @@ int arvae_tick_gi_bwd(const float *dgi, const int64_t *tokens, int32_t batch, in
 
 /* top-1 index per row, lowest index on ties (the decoder's argmax feedback, measurevae/decoder.py:506-507) */
 int arvae_row_argmax(const float *w, int32_t rows, int32_t cols, int64_t *idx, arvae_stream_t stream);
+/* one index per row drawn from softmax(w[r] * inv_temperature) by inverting its CDF at u[r] in (0, 1] (the decoder's multinomial
+ * feedback tick by tick, measurevae/decoder.py:502-505; the semantics of arvae_tick_free_run_sampled on given logits): the smallest
+ * k with C_k >= u[r] * C_{cols-1}.  Any cols >= 1; inv_temperature finite and > 0. */
+int arvae_row_sample(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature, int64_t *idx,
+                     arvae_stream_t stream);
 
 /* out[r] = [a[r] | b[r]] (torch.cat along dim 1/2, decoder.py:503) and its adjoint (db optionally accumulated) */
 int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,
@@ -613,6 +628,10 @@ int arvae_measure_vae_backward(const arvae_measure_vae_t *model, int32_t batch, 
  * ------------------------------------------------------------------------------------------------ */
 int arvae_philox_normal(float *out, int64_t count, uint64_t seed, uint32_t offset, uint32_t step, const uint32_t *dev_step,
                         arvae_stream_t stream);
+/* one u in (0, 1] per element: (x + 1) * 2^-32 of the first word x of the element's own block, the word arvae_philox_normal's radius
+ * takes (the draws of torch.multinomial, measurevae/decoder.py:502-505, as an explicit buffer) */
+int arvae_philox_uniform(float *out, int64_t count, uint64_t seed, uint32_t offset, uint32_t step, const uint32_t *dev_step,
+                         arvae_stream_t stream);
 int arvae_philox_keep_mask(uint8_t *out, int64_t count, float keep_prob, uint64_t seed, uint32_t offset, uint32_t step,
                            const uint32_t *dev_step, arvae_stream_t stream);
 int arvae_philox_keep_masks(int32_t n_masks, uint8_t *const *outs, const int64_t *counts, float keep_prob, uint64_t seed,

@@ -2,7 +2,8 @@
 """Train / evaluate the MeasureVAE on MI355X: counterpart of the reference's train_measure_vae.py (same flags and
 defaults).  Only the `folk` one-bar dataset in its pre-built tensor form is supported (arvae_amd.data.FolkNBarDataset):
 building it from ABC files with music21, and the `bach` chorales, are offline steps outside this build.  `--metrics` adds the
-reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary."""
+reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary; `--sample N [--temperature T]` adds N measures
+drawn from the model (z from the prior, every note from softmax(probs / T)) as lists of note names."""
 import json
 import os
 import sys
@@ -57,12 +58,17 @@ METRICS_FLAG = '--metrics'
 METRICS_HELP = (f'{METRICS_FLAG}: add the disentanglement metrics (Interpretability, SCC, Modularity, MIG, SAP; '
                 'arvae_amd.evaluation) to the evaluation summary.')
 with_metrics = False
+# likewise opt-in and outside the reference's flags: measures drawn from the evaluated model (MeasureVAETrainer.sample_measures)
+SAMPLE_FLAG, TEMPERATURE_FLAG = '--sample', '--temperature'
+SAMPLE_HELP = (f'{SAMPLE_FLAG} N [{TEMPERATURE_FLAG} T]: add `samples` to the evaluation summary, N measures drawn from the model '
+               '(z from the prior, every note from softmax(probs / T), T = 1 by default) as 24 note names each.')
+num_samples, temperature = 0, 1.0
 
 
 def with_options(fn):
     for names, kwargs in reversed(MEASURE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP)(fn)
+    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP)(fn)
 
 
 @with_options
@@ -133,14 +139,40 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         summary.update(trainer.test_model(batch_size=eval_bs))
         if with_metrics:
             summary.update(eval_metrics_or_warn(codes, attrs, names))
+        if num_samples > 0:
+            trainer.cuda()
+            model.eval()
+            _, notes = trainer.sample_measures(num_samples, temperature)
+            summary['samples'] = [[dataset.index2note_dicts[int(i)] for i in row] for row in notes.squeeze(1).tolist()]
         print(json.dumps(summary, indent=2))
 
 
+def _take_value(argv, flag, cast, default):
+    """-> (value of `flag VALUE` / `flag=VALUE` in argv or default, argv without it)"""
+    rest, value, i = [], default, 0
+    while i < len(argv):
+        a = argv[i]
+        if a == flag:
+            if i + 1 >= len(argv):
+                raise SystemExit(f'{flag} needs a value')
+            value, i = cast(argv[i + 1]), i + 1
+        elif a.startswith(flag + '='):
+            value = cast(a[len(flag) + 1:])
+        else:
+            rest.append(a)
+        i += 1
+    return value, rest
+
+
 def run(argv=None):
-    """the command line: the reference's flags (main) plus this build's opt-in --metrics"""
-    global with_metrics
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample and --temperature"""
+    global with_metrics, num_samples, temperature
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
+    num_samples, argv = _take_value(argv, SAMPLE_FLAG, int, 0)
+    temperature, argv = _take_value(argv, TEMPERATURE_FLAG, float, 1.0)
+    if num_samples < 0 or not temperature > 0:
+        raise SystemExit(f'{SAMPLE_FLAG} takes a count >= 0 and {TEMPERATURE_FLAG} a positive number')
     main(args=[a for a in argv if a != METRICS_FLAG])
 
 
