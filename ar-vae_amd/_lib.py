@@ -10,7 +10,7 @@ import threading
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libarvae_hip.so')
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_i32, c_i64, c_f32, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
@@ -61,6 +61,15 @@ class GruSeqDesc(ctypes.Structure):
 class TickWeights(ctypes.Structure):
     """arvae_tick_weights_t"""
     _fields_ = [(n, c_vp) for n in ('w_hh0', 'b_hh0', 'w_ih1', 'b_ih1', 'w_hh1', 'b_hh1', 'w_out', 'b_out')]
+
+
+TICK_MAX_LAYERS = 4
+
+
+class TickStack(ctypes.Structure):
+    """arvae_tick_stack_t"""
+    _fields_ = ([('layers', c_i32), ('reserved', c_i32)] + [(n, c_vp * TICK_MAX_LAYERS) for n in ('w_ih', 'w_hh', 'b_ih', 'b_hh')] +
+                [('w_out', c_vp), ('b_out', c_vp), ('h0', c_vp * TICK_MAX_LAYERS), ('h0_stride', c_i64)])
 
 
 class MeasureVaeDesc(ctypes.Structure):
@@ -129,6 +138,10 @@ SIGNATURES = {
                                     c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_sampled': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                             c_vp, c_f32, c_vp, c_vp, c_vp]),
+    'arvae_tick_free_run_layers_supported': (c_i32, [c_i32, c_i32, c_i32]),
+    'arvae_tick_free_run_layers_ws_floats': (c_i64, [c_i32, c_i32]),
+    'arvae_tick_free_run_layers': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp,
+                                           c_vp, c_vp]),
     'arvae_embed_fwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'arvae_embed_bwd_ws_floats': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     'arvae_embed_bwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),

@@ -17,6 +17,7 @@
 // over all T*R rows afterwards (ops.py).
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "diag.h"
 #include "common.h"
 #include "splitmath.h"
@@ -1401,6 +1402,407 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
 #endif
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The free-running tick decoder for layer counts other than two (nn.GRU(num_layers = L), measurevae/decoder.py:331-363): the contract of
+// tick_free_run_h2_kernel -- pre-multiplied layer-0 projections, state restart per beat, tokens as the only output, the same two picks --
+// with the layer stack a template parameter.  Two layers keep their own kernel above; this one has no layer-0 product under the
+// logits (at L = 1 there is nothing else to hide it behind, at L >= 3 the stream of 2L - 1 matrices is what bounds a tick).
+//   matrices 0 .. 2L-2 of the packed workspace: W_hh0, then per upper layer l its W_ih_l (2l - 1) and W_hh_l (2l), every one as
+//   scaled two-term fp16 in the per-lane order of tick_weight_prep_h2_kernel, streamed through one register ring across the tick;
+//   scales: W_hh0 its own, W_ih_l and W_hh_l one between them (r and z share accumulators), the states one per beat = the maximum
+//   over the workgroup's rows of ALL L initial states (times the keep scale: a boundary's operand is a state times 0 or keep_scale);
+//   boundary l -> l + 1 has its own keep-mask [ticks][B][H], l major; the logits read the TOP layer's state (layer 0's at L = 1).
+// A workgroup owns its RW rows for the whole sequence: LDS barriers only, nothing waits on another workgroup.
+// LDS (bytes): per layer the two state images of two fp16 planes, one boundary operand (two from L = 3 on, alternating: a layer's gates
+// write the next boundary while other waves still read the last), the top state in fp32, W_out, the pick's scratch: 64032 at L = 1,
+// H = 128; 62992 / 72208 at L = 3 / 4, H = 64 (multinomial) of the 163840 a workgroup may hold.
+// Offered for L = 1 at every hidden size and L = 3, 4 up to hidden 64 (arvae_tick_free_run_layers_supported).
+constexpr int TICK_MAX_LAYERS = 4;
+struct TickStack {
+    const float *b_ih[TICK_MAX_LAYERS], *b_hh[TICK_MAX_LAYERS];    // (b_ih[0] unused: part of gib)
+    const float *w_out, *b_out;
+    const float *h0[TICK_MAX_LAYERS];                              // per layer [beats*B] rows of H values h0_stride floats apart
+    int64_t h0_stride;
+    const float *gib, *ptab;                                       // as TickFreeRun
+    const uint8_t *mask;                                           // [L-1][beats*tpb][B][H] or null
+    float keep_scale;
+    int batch, beats, tpb, vocab;
+    int64_t *tokens;
+};
+struct TickPrepN {
+    const float *w[2 * TICK_MAX_LAYERS - 1];
+    int nmat;
+    uint4 *out;
+};
+
+// tick_weight_amax_kernel for 2L - 1 matrices: one workgroup per matrix -> wmax[matrix]
+template <int H>
+__global__ __launch_bounds__(1024) void tick_stack_amax_kernel(TickPrepN p, float *__restrict__ wmax) {
+    __shared__ float red[16];
+    const float *w = p.w[blockIdx.x];
+    float m = 0.f;
+    for (int i = threadIdx.x; i < 3 * H * H / 4; i += 1024) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(w + 4 * i);
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int q = 0; q < 16; ++q) t = fmaxf(t, red[q]);
+        wmax[blockIdx.x] = t;
+    }
+}
+// matrix m's scale: W_hh0 its own, an upper layer's pair (2l - 1, 2l) one between them
+__device__ __forceinline__ Pow2 tick_stack_scale(const float *wmax, int m) {
+    const int first = ((m + 1) >> 1) * 2 - 1;
+    return pow2_for(m == 0 ? wmax[0] : fmaxf(wmax[first], wmax[first + 1]));
+}
+// tick_weight_prep_h2_kernel for 2L - 1 matrices (the same per-lane layout, matrix major)
+template <int H>
+__global__ __launch_bounds__(256) void tick_stack_prep_kernel(TickPrepN p, const float *__restrict__ wmax) {
+    constexpr int NW = H / 16, KS = H / 32;
+    const int tid = blockIdx.x * 256 + threadIdx.x;
+    const int lane = tid & 63;
+    int rest = tid >> 6;
+    const int g = rest % 3; rest /= 3;
+    const int w = rest % NW; rest /= NW;
+    const int ks = rest % KS;
+    const int m = rest / KS;
+    if (m >= p.nmat) return;
+    const int col = lane & 15, quad = lane >> 4;
+    const float *src = p.w[m] + (int64_t)(g * H + 16 * w + col) * H + 32 * ks + 8 * quad;
+    const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + 4);
+    const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    f16x8 hi, lo;
+    split2_8<false>(x, tick_stack_scale(wmax, m).s, hi, lo);
+    uint4 *dst = p.out + ((int64_t)((m * KS + ks) * NW + w) * 6 + g * 2) * 64 + lane;
+    dst[0] = __builtin_bit_cast(uint4, hi);
+    dst[64] = __builtin_bit_cast(uint4, lo);
+}
+
+template <int H, int L, int RW, int PICK>
+__global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p, const uint4 *__restrict__ packed, TickSample smp) {
+    static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
+    static_assert(L >= 1 && L <= TICK_MAX_LAYERS, "layer count");
+    constexpr int E = RW / 4;
+    constexpr int NW = H / 16, KS = H / 32, KQ = H / 16, M = 2 * L - 1;
+    constexpr int NGG = 3 * M * KS;                // weight groups per tick: (matrix, k-step, gate), 2 x 16 bytes per lane each
+    constexpr int RS = NGG % 6 == 0 ? 6 : 3;       // register ring of groups; RS - 1 groups are in flight
+    constexpr int PFD = RS - 1;
+    constexpr int HP = H + 8, PLANE = 16 * HP, HS = H + 4;
+    constexpr int NMID = L > 2 ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) unsigned short hA[L][2][2 * PLANE];
+    __shared__ __attribute__((aligned(16))) unsigned short midp[NMID][2 * PLANE];
+    __shared__ __attribute__((aligned(16))) float topf[16][HS];
+    __shared__ __attribute__((aligned(16))) float wout_s[64][HS];
+    __shared__ float cand_v[4][16];
+    __shared__ float hmax[H / 16];
+    __shared__ int cand_i[4][16];
+    __shared__ float smp_max[4][16];
+    __shared__ float smp_pre[4][16][16];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int col = lane & 15, quad = lane >> 4;
+    const int unit = 16 * w + col;
+    const int row0 = blockIdx.x * RW;
+    const int B = p.batch;
+    const int ntile = (p.vocab + 15) / 16;
+
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(packed), 0, M * KS * NW * 6 * 64 * 16, 0x00020000);
+    const int wlane = (w * 6 * 64 + lane) * 16;
+    f16x8 wb[RS][2];
+    auto fetch = [&](int gg) {                     // gg = (matrix * KS + ks) * 3 + gate, compile-time at every call site
+        const int g = gg / 3, gate = gg % 3;
+#pragma unroll
+        for (int term = 0; term < 2; ++term)
+            wb[gg % RS][term] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, (g * NW * 6 + gate * 2 + term) * 64 * 16, 0));
+    };
+#pragma unroll
+    for (int d = 0; d < PFD; ++d) fetch(d % NGG);
+
+    for (int e = threadIdx.x; e < 64 * H; e += H * 4) {       // note projection weights -> LDS (rows >= vocab: zeros)
+        const int n = e / H, k = e - n * H;
+        wout_s[n][k] = n < p.vocab ? p.w_out[(int64_t)n * H + k] : 0.f;
+    }
+    // layer 0: b_hh alone (b_ih is inside gib); upper layers: r and z take b_ih + b_hh, n keeps them apart
+    float br[L], bz[L], bin[L], bhn[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        const float *bh = p.b_hh[l];
+        br[l] = bh[unit]; bz[l] = bh[H + unit]; bhn[l] = bh[2 * H + unit]; bin[l] = 0.f;
+        if (l > 0) {
+            const float *bi = p.b_ih[l];
+            br[l] += bi[unit]; bz[l] += bi[H + unit]; bin[l] = bi[2 * H + unit];
+        }
+    }
+    const int note = 16 * w + col;
+    const bool note_ok = w < ntile && note < p.vocab;
+    const float bout = note_ok ? p.b_out[note] : 0.f;
+
+    auto lrow = [&](int i) { return gru_lrow<E>(quad, i); };
+    int rows[E];
+    bool live[E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+        const int r = row0 + lrow(i);
+        live[i] = r < B;
+        rows[i] = live[i] ? r : B - 1;
+    }
+    float h[L][E], gb[E][3];
+    int tok[E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) tok[i] = p.vocab;
+    const int ticks = p.beats * p.tpb;
+    const bool masked = p.mask != nullptr;
+    const uint8_t *mask_bytes = masked ? p.mask : reinterpret_cast<const uint8_t *>(p.gib);
+    const float *wmax = reinterpret_cast<const float *>(packed) + 3 * M * H * H;
+    float w_inv[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) w_inv[l] = tick_stack_scale(wmax, 2 * l).inv;
+    const float keep_bound = masked ? fmaxf(p.keep_scale, 1.f) : 1.f;
+    float h_s = 1.f, us[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) us[l] = 1.f;
+    const int arow = gru_arow<E>(col);
+    const int aoff = arow * HP + 8 * quad;
+    auto elems = [&](const f32x4 &acc, float (&out)[E]) __attribute__((always_inline)) { gru_elems<E>(acc, out); };
+    // matrix m's 3 KS groups against the state image `ab`: gate q of every k-step into acc[q == 2 ? nslot : q]
+    auto product = [&](auto mc, const unsigned short *ab, f32x4 (&acc)[4], int nslot) __attribute__((always_inline)) {
+        constexpr int m = decltype(mc)::value;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const f16x8 ah = lds_x8<f16x8>(ab + 32 * ks), al = lds_x8<f16x8>(ab + PLANE + 32 * ks);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int gg = (m * KS + ks) * 3 + q;
+                fetch((gg + PFD) % NGG);
+                __builtin_amdgcn_sched_barrier(0);
+                GRU_MFMA3(acc[q == 2 ? nslot : q], ah, al, wb[gg % RS][0], wb[gg % RS][1]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    // layer l's new state of the lane's elements -> its next image, the boundary above it (times the keep byte) or, on top, the logits' fp32 operand
+    auto publish = [&](auto lc, int nxt, const unsigned (&keep)[E]) __attribute__((always_inline)) {
+        constexpr int l = decltype(lc)::value;
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            store_split2<false>(&hA[l][nxt][lrow(i) * HP + unit], PLANE, h[l][i], h_s);
+            if constexpr (l < L - 1) {
+                const float factor = masked ? p.keep_scale * (float)keep[i] : 1.f;
+                store_split2<false>(&midp[l % NMID][lrow(i) * HP + unit], PLANE, h[l][i] * factor, h_s);
+            }
+            else topf[lrow(i)][unit] = h[l][i];
+        }
+    };
+    auto upper_layer = [&](auto lc, int cur, const unsigned (&keep)[E]) __attribute__((always_inline)) {
+        constexpr int l = decltype(lc)::value;
+        f32x4 a1[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // r, z, i_n, h_n
+        product(std::integral_constant<int, 2 * l - 1>{}, &midp[(l - 1) % NMID][aoff], a1, 2);
+        product(std::integral_constant<int, 2 * l>{}, &hA[l][cur][aoff], a1, 3);
+        float ar[E], az[E], ai[E], ah[E];
+        elems(a1[0], ar); elems(a1[1], az); elems(a1[2], ai); elems(a1[3], ah);
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const float r = fast_sigmoid(ar[i] * us[l] + br[l]);
+            const float z = fast_sigmoid(az[i] * us[l] + bz[l]);
+            const float n = fast_tanh(ai[i] * us[l] + bin[l] + r * (ah[i] * us[l] + bhn[l]));
+            h[l][i] = (1.f - z) * n + z * h[l][i];
+        }
+        publish(lc, cur ^ 1, keep);
+        lds_barrier();
+    };
+
+    for (int t = 0; t < ticks; ++t) {
+        const int cur = t & 1;
+        const int beat = t / p.tpb;
+        if (t % p.tpb == 0) {                                  // the states restart at every beat
+            lds_barrier();
+            float mx = 1.f;
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const int64_t brow = (int64_t)beat * B + rows[i];
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    h[l][i] = p.h0[l][brow * p.h0_stride + unit];
+                    mx = fmaxf(mx, fabsf(h[l][i]));
+                }
+                const float *g = p.gib + brow * 3 * H + unit;
+                gb[i][0] = g[0]; gb[i][1] = g[H]; gb[i][2] = g[2 * H];
+            }
+            mx = row16_max(mx * keep_bound);
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            if (lane == 0) hmax[w] = mx;
+            lds_barrier();
+#pragma unroll
+            for (int q = 0; q < H / 16; ++q) mx = fmaxf(mx, hmax[q]);
+            const Pow2 sh = pow2_for(mx);
+            h_s = sh.s;
+#pragma unroll
+            for (int l = 0; l < L; ++l) us[l] = sh.inv * w_inv[l];
+#pragma unroll
+            for (int i = 0; i < E; ++i)
+#pragma unroll
+                for (int l = 0; l < L; ++l) store_split2<false>(&hA[l][cur][lrow(i) * HP + unit], PLANE, h[l][i], h_s);
+            lds_barrier();
+        }
+        // the token's projections and every boundary's keep bytes are requested here, in front of the tick's weight stream, so that
+        // no weight group waits on their account: they are older than the tick's weight loads in the in-order counter.  The bytes stay
+        // raw until `publish` turns them into factors -- converted here they would be waited for at once, a round trip per tick in
+        // front of the first group.  No branch around the byte loads (a load under a run-time test is followed by a full drain):
+        // without masks they read byte 0 of the projections and the select in `publish` drops it
+        float gi[E][3];
+        unsigned keep[L > 1 ? L - 1 : 1][E];
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const float *pt = p.ptab + (int64_t)tok[i] * 3 * H + unit;
+            gi[i][0] = gb[i][0] + pt[0]; gi[i][1] = gb[i][1] + pt[H]; gi[i][2] = gb[i][2] + pt[2 * H];
+#pragma unroll
+            for (int l = 0; l < (L > 1 ? L - 1 : 1); ++l) {
+                keep[l][i] = 1u;
+                if constexpr (L > 1) {
+                    const int64_t at = masked ? (((int64_t)l * ticks + t) * B + rows[i]) * H + unit : 0;
+                    keep[l][i] = mask_bytes[at];
+                }
+            }
+        }
+        float un[E];
+        if constexpr (PICK == PICK_MULTINOMIAL) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) un[i] = fminf(fmaxf(smp.u[(int64_t)rows[i] * ticks + t], 0.f), 1.f);
+        }
+        // ---- layer 0: matrix 0 on its own state, the input projections from the token
+        {
+            f32x4 a0[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            product(std::integral_constant<int, 0>{}, &hA[0][cur][aoff], a0, 2);
+            float ar[E], az[E], an[E];
+            elems(a0[0], ar); elems(a0[1], az); elems(a0[2], an);
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const float r = fast_sigmoid(gi[i][0] + ar[i] * us[0] + br[0]);
+                const float z = fast_sigmoid(gi[i][1] + az[i] * us[0] + bz[0]);
+                const float n = fast_tanh(gi[i][2] + r * (an[i] * us[0] + bhn[0]));
+                h[0][i] = (1.f - z) * n + z * h[0][i];
+            }
+            publish(std::integral_constant<int, 0>{}, cur ^ 1, keep[0]);
+            lds_barrier();
+        }
+        // ---- upper layers: W_ih_l on the boundary below, W_hh_l on the layer's own state
+        // (the top layer publishes no boundary: its keep argument is not read)
+        if constexpr (L > 1) upper_layer(std::integral_constant<int, 1>{}, cur, keep[L > 2 ? 1 : 0]);
+        if constexpr (L > 2) upper_layer(std::integral_constant<int, 2>{}, cur, keep[L > 3 ? 2 : 0]);
+        if constexpr (L > 3) upper_layer(std::integral_constant<int, 3>{}, cur, keep[0]);
+        // ---- logits (fp32 MFMA, weights in LDS) and the tiles' half of the pick on the first waves
+        if (w < ntile) {
+            f32x4 lg = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kq = 0; kq < KQ; ++kq) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(&topf[arow][16 * kq + 4 * quad]);
+                const f32x4 b = *reinterpret_cast<const f32x4 *>(&wout_s[note][16 * kq + 4 * quad]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) lg = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], lg, 0, 0, 0);
+            }
+            float v[E], lv[E];
+            elems(lg, lv);
+#pragma unroll
+            for (int i = 0; i < E; ++i) v[i] = note_ok ? fmaxf(lv[i] + bout, 0.f) : -1.f;
+            if constexpr (PICK == PICK_MULTINOMIAL) {          // the tile's maximum, e relative to it and e's prefixes per row
+                float mx[E], pre[E];
+#pragma unroll
+                for (int i = 0; i < E; ++i) mx[i] = row16_max(v[i]);
+#pragma unroll
+                for (int i = 0; i < E; ++i) pre[i] = note_ok ? __expf((v[i] - mx[i]) * smp.inv_t) : 0.f;
+#pragma unroll
+                for (int i = 0; i < E; ++i) pre[i] = row16_prefix(pre[i]);
+#pragma unroll
+                for (int i = 0; i < E; ++i) smp_pre[w][lrow(i)][col] = pre[i];
+                if (col == 0) {
+#pragma unroll
+                    for (int i = 0; i < E; ++i) smp_max[w][lrow(i)] = mx[i];
+                }
+            } else {
+                int ix[E];
+#pragma unroll
+                for (int i = 0; i < E; ++i) ix[i] = note;
+#pragma unroll
+                for (int i = 0; i < E; ++i) tick_argmax_stage<0xB1>(v[i], ix[i]);
+#pragma unroll
+                for (int i = 0; i < E; ++i) tick_argmax_stage<0x4E>(v[i], ix[i]);
+#pragma unroll
+                for (int i = 0; i < E; ++i) tick_argmax_stage<0x141>(v[i], ix[i]);
+#pragma unroll
+                for (int i = 0; i < E; ++i) tick_argmax_stage<0x140>(v[i], ix[i]);
+                if (col == 0) {
+#pragma unroll
+                    for (int i = 0; i < E; ++i) { cand_v[w][lrow(i)] = v[i]; cand_i[w][lrow(i)] = ix[i]; }
+                }
+            }
+        }
+        lds_barrier();
+        // ---- the rows' half of the pick, on every lane (the arithmetic of tick_free_run_h2_kernel)
+        if constexpr (PICK == PICK_MULTINOMIAL) {
+            int tile[E];
+            float base[E], scale[E], target[E];
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const int r = lrow(i);
+                float m[4], sum[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const bool on = c < ntile;
+                    m[c] = on ? smp_max[c][r] : -1.f;
+                    sum[c] = on ? smp_pre[c][r][min(15, p.vocab - 1 - 16 * c)] : 0.f;
+                }
+                const float big = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
+                float sc[4], run[5];
+                run[0] = 0.f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    sc[c] = __expf((m[c] - big) * smp.inv_t);
+                    run[c + 1] = __builtin_fmaf(sum[c], sc[c], run[c]);
+                }
+                target[i] = un[i] * run[4];
+                tile[i] = 0; base[i] = run[0]; scale[i] = sc[0];
+#pragma unroll
+                for (int c = 1; c < 4; ++c) {
+                    const bool next = run[c] < target[i];
+                    tile[i] = next ? c : tile[i];
+                    base[i] = next ? run[c] : base[i];
+                    scale[i] = next ? sc[c] : scale[i];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const float ck = __builtin_fmaf(smp_pre[tile[i]][lrow(i)][col], scale[i], base[i]);
+                const unsigned long long reached = __ballot(ck >= target[i]);
+                const int ix = min(max(16 * tile[i] + __ffs((int)((unsigned)(reached >> (16 * quad)) & 0xffffu)) - 1, 0), p.vocab - 1);
+                tok[i] = ix;
+                if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const int r = lrow(i);
+                float v = cand_v[0][r];
+                int ix = cand_i[0][r];
+                for (int c = 1; c < ntile; ++c) {
+                    const float ov = cand_v[c][r];
+                    const int oi = cand_i[c][r];
+                    const bool take = ov > v;                  // later tiles hold larger indices: ties keep the earlier
+                    v = take ? ov : v;
+                    ix = take ? oi : ix;
+                }
+                tok[i] = ix;
+                if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+            }
+        }
+    }
+}
+
 }  // namespace arvae
 
 using namespace arvae;
@@ -1600,6 +2002,98 @@ extern "C" int arvae_tick_free_run_sampled(const arvae_tick_weights_t *wts, cons
                   "tick_free_run_sampled: inverse temperature %f is not a positive finite number", (double)inv_temperature);
     return tick_free_run_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, hidden, vocab,
                                 uniforms, inv_temperature, tokens, ws, stream);
+}
+
+// ---- layer counts other than two (tick_free_run_layers_kernel) ----------------------------------------------------
+static int tick_stack_matrices(int layers) { return 2 * layers - 1; }
+
+extern "C" int arvae_tick_free_run_layers_supported(int32_t hidden, int32_t vocab, int32_t layers) {
+    // hidden 128 with three or four layers is NOT offered: those instantiations fed back wrong notes in a few per cent of the rows,
+    // differently from run to run, and the cause is not found: such stacks go tick by tick
+    if (hidden == 128 && layers >= 3) return 0;
+    return arvae_tick_free_run_supported(hidden, vocab) && (layers == 1 || layers == 3 || layers == 4);
+}
+
+extern "C" int64_t arvae_tick_free_run_layers_ws_floats(int32_t hidden, int32_t layers) {
+    // 2L - 1 matrices [3H][H] as two 16-bit terms each, and their maxima behind (padded to a 16-byte multiple)
+    if (!arvae_gru_seq_supported(hidden) || layers < 1 || layers > TICK_MAX_LAYERS) return 0;
+    return (int64_t)tick_stack_matrices(layers) * 3 * hidden * hidden + 8;
+}
+
+template <int HH, int LL>
+static void tick_stack_launch(const TickStack &p, const TickPrepN &tp, float *ws, int rw, const TickSample &smp, hipStream_t st) {
+    constexpr int M = 2 * LL - 1;
+    float *wmax = ws + (int64_t)3 * M * HH * HH;
+    const int items = M * (HH / 32) * (HH / 16) * 3 * 64;
+    const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
+    const dim3 gr((p.batch + rw - 1) / rw);
+    ARVAE_LAUNCH(tick_stack_amax_kernel<HH>, dim3(M), dim3(1024), 0, st, tp, wmax);
+    ARVAE_LAUNCH(tick_stack_prep_kernel<HH>, dim3((items + 255) / 256), dim3(256), 0, st, tp, wmax);
+#define TICK_STACK_RW(PICK)                                                                                                       \
+    {                                                                                                                            \
+        if (rw == 4) ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, 4, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);        \
+        else if (rw == 8) ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, 8, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);   \
+        else ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, 16, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);               \
+    }
+    if (smp.u != nullptr) TICK_STACK_RW(PICK_MULTINOMIAL)
+    else TICK_STACK_RW(PICK_ARGMAX)
+#undef TICK_STACK_RW
+}
+
+extern "C" int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask,
+                                          float keep_scale, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
+                                          int32_t vocab, const float *uniforms, float inv_temperature, int64_t *tokens, float *ws,
+                                          arvae_stream_t stream) {
+    ARVAE_REQUIRE(stack && gib && ptab && tokens, "tick_free_run_layers: null pointer");
+    ARVAE_REQUIRE(ws != nullptr, "tick_free_run_layers: null workspace (arvae_tick_free_run_layers_ws_floats)");
+    const int layers = stack->layers;
+    ARVAE_REQUIRE(layers >= 1 && layers <= ARVAE_TICK_MAX_LAYERS, "tick_free_run_layers: %d layers (1 .. %d)", layers, ARVAE_TICK_MAX_LAYERS);
+    ARVAE_REQUIRE(batch >= 1 && beats >= 1 && ticks_per_beat >= 1, "tick_free_run_layers: empty problem");
+    ARVAE_REQUIRE(arvae_gru_seq_supported(hidden), "tick_free_run_layers: hidden size %d is not built (32, 64, 128)", hidden);
+    ARVAE_REQUIRE(arvae_tick_free_run_supported(hidden, vocab), "tick_free_run_layers: vocabulary of %d notes not supported at hidden size %d",
+                  vocab, hidden);
+    ARVAE_REQUIRE(arvae_tick_free_run_layers_supported(hidden, vocab, layers),
+                  "tick_free_run_layers: %d layers at hidden size %d are not offered (1, 3, 4 layers, three and four up to hidden 64; "
+                  "two layers: arvae_tick_free_run)", layers, hidden);
+    ARVAE_REQUIRE(stack->w_out && stack->b_out, "tick_free_run_layers: null weight pointer");
+    for (int l = 0; l < layers; ++l) {
+        ARVAE_REQUIRE(stack->w_hh[l] && stack->b_hh[l] && stack->h0[l], "tick_free_run_layers: null pointer in layer %d", l);
+        ARVAE_REQUIRE(l == 0 || (stack->w_ih[l] && stack->b_ih[l]), "tick_free_run_layers: null input weights in layer %d", l);
+    }
+    ARVAE_REQUIRE(stack->h0_stride == 0 || stack->h0_stride >= hidden, "tick_free_run_layers: h0_stride %lld is below the hidden size %d",
+                  (long long)stack->h0_stride, hidden);
+    ARVAE_REQUIRE(mask == nullptr || layers == 1 || (std::isfinite(keep_scale) && keep_scale >= 0.f),
+                  "tick_free_run_layers: keep scale %f is not a finite non-negative number", (double)keep_scale);
+    ARVAE_REQUIRE(uniforms == nullptr || (std::isfinite(inv_temperature) && inv_temperature > 0.f),
+                  "tick_free_run_layers: inverse temperature %f is not a positive finite number", (double)inv_temperature);
+    ARVAE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "tick_free_run_layers: workspace must be 16-byte aligned");
+    TickStack p{};
+    TickPrepN tp{};
+    tp.nmat = tick_stack_matrices(layers);
+    tp.out = reinterpret_cast<uint4 *>(ws);
+    for (int l = 0; l < layers; ++l) {
+        p.b_ih[l] = stack->b_ih[l]; p.b_hh[l] = stack->b_hh[l]; p.h0[l] = stack->h0[l];
+        tp.w[2 * l] = stack->w_hh[l];
+        if (l > 0) tp.w[2 * l - 1] = stack->w_ih[l];
+    }
+    p.w_out = stack->w_out; p.b_out = stack->b_out;
+    p.h0_stride = stack->h0_stride != 0 ? stack->h0_stride : hidden;
+    p.gib = gib; p.ptab = ptab; p.mask = layers > 1 ? mask : nullptr; p.keep_scale = keep_scale;
+    p.batch = batch; p.beats = beats; p.tpb = ticks_per_beat; p.vocab = vocab; p.tokens = tokens;
+    hipStream_t st = as_stream(stream);
+    const int rw = gru_rows_per_wg(batch, 1);
+    const TickSample smp{uniforms, uniforms != nullptr ? inv_temperature : 1.f};
+#define TICK_STACK_H(LL)                                                                                                          \
+    {                                                                                                                            \
+        if (hidden == 128) { if constexpr (LL == 1) tick_stack_launch<128, 1>(p, tp, ws, rw, smp, st); }                         \
+        else if (hidden == 64) tick_stack_launch<64, LL>(p, tp, ws, rw, smp, st);                                                \
+        else tick_stack_launch<32, LL>(p, tp, ws, rw, smp, st);                                                                  \
+    }
+    if (layers == 1) TICK_STACK_H(1)
+    else if (layers == 3) TICK_STACK_H(3)
+    else TICK_STACK_H(4)
+#undef TICK_STACK_H
+    return check_launch("tick_free_run_layers_kernel");
 }
 
 #ifdef ARVAE_GRU_STAMPS

@@ -30,6 +30,8 @@ class FusedMeasureVAE(_ArenaBound):
     def supports(model, optimizer, reg_dims):
         """None when the executor can run `model` from `optimizer`'s arena, else the reason it cannot (str)."""
         enc, dec = model.encoder, model.decoder
+        if enc.num_layers != 2 or dec.num_layers != 2:               # (arvae_measure_vae_t holds two layers per RNN)
+            return 'layer count not built in the executor'
         if not (ops.gru_sequence_supported(enc.rnn_hidden_size) and ops.gru_sequence_supported(dec.rnn_hidden_size)):
             return 'hidden size not built as a sequence kernel'
         if dec.sampling != 'argmax':

@@ -5,7 +5,8 @@ Same class names, constructor arguments, forward contract and state_dict keys as
     MeasureVAE.forward(score, metadata, train) -> (weights (B,24,V), samples (B,1,24), z_dist, prior_dist, z_tilde, z_prior)
 Every GRU layer runs as whole-sequence launches (csrc/gru_seq.hip: all time steps of a layer, both directions, in one
 kernel forward and one backward; input projections and weight gradients as whole-sequence GEMMs); the free-running
-decoder gets its tokens from one more launch.  Hidden sizes other than 32 / 64 / 128 (or ARVAE_GRU_STEPWISE=1) fall back
+decoder gets its tokens from one more launch.  Any layer count >= 1 (nn.GRU(num_layers=L): layer k > 0 reads layer k-1's outputs,
+dropout between layers only); the two-layer stacks of the reference's defaults keep their own one-launch tick kernel.  Hidden sizes other than 32 / 64 / 128 (or ARVAE_GRU_STEPWISE=1) fall back
 to one launch per GRU cell and time step (csrc/sequence.hip + the dense kernels).  autograd only chains the launches.
 """
 import os
@@ -64,6 +65,26 @@ def _gru_step(x_proj, h, w_hh, b_hh):
     return ops.gru_gates(x_proj, gh, h)
 
 
+def _split_layers(flat, hidden, layers):
+    """(R, layers*H) -> the `layers` initial states (R, H): view(R, layers, H).transpose(0, 1) of decoder.py:388-406"""
+    parts = []
+    for _ in range(layers - 1):
+        head, flat = ops.split_cols(flat, hidden)
+        parts.append(head)
+    return parts + [flat]
+
+
+def _boundary_masks(mask, layers, inner, what):
+    """an explicit keep-mask as the list of its layers-1 boundaries' masks, each of shape `inner`: (layers-1, *inner), or at two
+    layers also the bare `inner` of the one boundary"""
+    if mask is not None and layers == 2 and tuple(mask.shape) == tuple(inner):
+        return [mask]
+    if mask is None or tuple(mask.shape) != (layers - 1,) + tuple(inner):
+        got = None if mask is None else tuple(mask.shape)
+        raise ValueError(f'{what} keep-mask must be {(layers - 1,) + tuple(inner)} (one per layer boundary), got {got}')
+    return list(torch.unbind(mask, 0))
+
+
 def _use_sequence_kernels(hidden):
     """whole-sequence GRU launches (csrc/gru_seq.hip) when the hidden size is built; ARVAE_GRU_STEPWISE=1 keeps the
     one-launch-per-time-step path (A/B measurements, and the only path for other hidden sizes)."""
@@ -74,8 +95,10 @@ class Encoder(Model):
     def __init__(self, note_embedding_dim, rnn_hidden_size, num_layers, num_notes, dropout, bidirectional, z_dim,
                  rnn_class=nn.GRU):
         super().__init__()
-        if not bidirectional or num_layers != 2:
-            raise NotImplementedError('the HIP encoder implements the reference configuration: 2-layer bidirectional GRU')
+        if not bidirectional:
+            raise NotImplementedError('the HIP encoder implements the reference configuration: a bidirectional GRU')
+        if num_layers < 1:
+            raise ValueError('num_layers must be at least 1')
         self.bidirectional, self.num_directions = bidirectional, 2
         self.note_embedding_dim, self.num_layers = note_embedding_dim, num_layers
         self.rnn_hidden_size, self.z_dim, self.dropout, self.rnn_class = rnn_hidden_size, z_dim, dropout, rnn_class
@@ -96,7 +119,10 @@ class Encoder(Model):
                 f'{self.dropout},{self.bidirectional},{self.z_dim},)')
 
     def push_dropout_mask(self, mask):
-        """explicit keep-mask (24, B, 2H) uint8 for the layer-0 outputs (parity runs)."""
+        """explicit keep-masks (num_layers - 1, 24, B, 2H) uint8 for the outputs of every layer but the last (parity runs); with two
+        layers also (24, B, 2H).  A one-layer GRU has no boundary to drop at: refused."""
+        if self.num_layers == 1:
+            raise ValueError('a one-layer GRU has no inter-layer dropout: there is no mask to push')
         self._mask_queue.append(mask)
 
     def embed_forward(self, score_tensor):
@@ -183,29 +209,37 @@ class Encoder(Model):
         hid = self.rnn_hidden_size
         # (T, B, E); with the lookup path of layer 0 nothing reads it and autograd drops the launch's backward
         emb = None if _use_sequence_kernels(hid) else ops.embed(score_tensor, self.note_embedding_layer.weight, time_major=True)
-        dropping = self.training and self.dropout > 0
-        mask = None
+        layers = self.num_layers
+        dropping = self.training and self.dropout > 0 and layers > 1          # nn.GRU drops between layers only
+        masks = None
         if dropping:
             dev = score_tensor.device
-            mask = self._mask_queue.popleft().to(dev) if self._mask_queue else ops.keep_mask((steps, b, 2 * hid), self.dropout, dev)
+            if self._mask_queue:
+                masks = _boundary_masks(self._mask_queue.popleft().to(dev), layers, (steps, b, 2 * hid), 'encoder')
+            else:                                                # one draw (one Philox offset) per boundary, lowest boundary first
+                masks = [ops.keep_mask((steps, b, 2 * hid), self.dropout, dev) for _ in range(layers - 1)]
         if _use_sequence_kernels(hid):
             out0, fin0 = self._first_layer_by_lookup(score_tensor, steps, b)
             if out0 is None:
                 emb = ops.embed(score_tensor, self.note_embedding_layer.weight, time_major=True)
                 out0, fin0 = self._layer_sequence(emb.view(steps * b, -1), steps, b, 0)
-            mid = out0.view(steps * b, 2 * hid)
-            if dropping:
-                mid = ops.dropout_mask(mid, mask.contiguous().view(steps * b, 2 * hid), self.dropout)
-            _, fin1 = self._layer_sequence(mid, steps, b, 1)
-            # h_n of nn.GRU: (layer 0 fwd, layer 0 rev, layer 1 fwd, layer 1 rev), each direction's LAST processed step
-            hidden = ops.concat_cols(fin0, fin1)
+            # h_n of nn.GRU: (layer 0 fwd, layer 0 rev, layer 1 fwd, layer 1 rev, ...), each direction's LAST processed step
+            out, hidden = out0, fin0
+            for layer in range(1, layers):
+                mid = out.view(steps * b, 2 * hid)
+                if dropping:
+                    mid = ops.dropout_mask(mid, masks[layer - 1].contiguous().view(steps * b, 2 * hid), self.dropout)
+                out, fin = self._layer_sequence(mid, steps, b, layer)
+                hidden = ops.concat_cols(hidden, fin)
         else:
             seq = list(torch.unbind(emb, 0))
-            seq, finals0 = self._layer(seq, 0)
-            if dropping:
-                seq = [ops.dropout_mask(s, m, self.dropout) for s, m in zip(seq, torch.unbind(mask.contiguous(), 0))]
-            _, finals1 = self._layer(seq, 1)
-            hidden = ops.concat_cols(ops.concat_cols(finals0[0], finals0[1]), ops.concat_cols(finals1[0], finals1[1]))
+            seq, finals = self._layer(seq, 0)
+            hidden = ops.concat_cols(finals[0], finals[1])
+            for layer in range(1, layers):
+                if dropping:
+                    seq = [ops.dropout_mask(s, m, self.dropout) for s, m in zip(seq, torch.unbind(masks[layer - 1].contiguous(), 0))]
+                seq, finals = self._layer(seq, layer)
+                hidden = ops.concat_cols(hidden, ops.concat_cols(finals[0], finals[1]))
         la, lb = self.linear_mean[0], self.linear_log_std[0]
         both = ops.dense_pair(hidden, la.weight, la.bias, lb.weight, lb.bias, ACT_SELU)      # (B, 2 * 2H) or None
         if both is not None:
@@ -232,8 +266,8 @@ class Decoder(nn.Module):
 class HierarchicalDecoder(Decoder):
     def __init__(self, note_embedding_dim, num_notes, z_dim, num_layers, rnn_hidden_size, dropout, rnn_class=nn.GRU):
         super().__init__(note_embedding_dim, num_notes, z_dim)
-        if num_layers != 2:
-            raise NotImplementedError('the HIP decoder implements the reference configuration: 2-layer GRUs')
+        if num_layers < 1:
+            raise ValueError('num_layers must be at least 1')
         self.name = 'HierarchicalDecoder'
         self.rnn_class, self.num_layers, self.rnn_hidden_size, self.dropout = rnn_class, num_layers, rnn_hidden_size, dropout
         h = rnn_hidden_size
@@ -259,7 +293,10 @@ class HierarchicalDecoder(Decoder):
         return f'{self.name}{self.note_embedding_dim},{self.rnn_class},{self.num_layers},{self.rnn_hidden_size},{self.dropout},)'
 
     def push_dropout_masks(self, beat_mask, tick_mask):
-        """explicit keep-masks (4, B, H) and (24, B, H) uint8 for the layer-0 hidden states."""
+        """explicit keep-masks (num_layers - 1, 4, B, H) and (num_layers - 1, 24, B, H) uint8 for the hidden states of every layer but
+        the last of the beat and the tick RNN; with two layers also (4, B, H) and (24, B, H).  One-layer GRUs have no boundary: refused."""
+        if self.num_layers == 1:
+            raise ValueError('a one-layer GRU has no inter-layer dropout: there are no masks to push')
         self._mask_queue.append((beat_mask, tick_mask))
 
     def push_sampling_uniforms(self, u):
@@ -278,23 +315,24 @@ class HierarchicalDecoder(Decoder):
         return ops.philox_uniform((b, ticks), device)
 
     def hidden_init(self, inp, rnn_type):
-        """(B, feats) -> [layer-0 hidden, layer-1 hidden]  (view(B, 2, H).transpose(0, 1), decoder.py:388-406)."""
+        """(B, feats) -> [layer-0 hidden, layer-1 hidden, ...]  (view(B, L, H).transpose(0, 1), decoder.py:388-406)."""
         if rnn_type == 'beat':
             flat = _lin(inp, self.z_to_beat_rnn_input[0], ACT_SELU)
         elif rnn_type == 'tick':
             flat = _lin(inp, self.beat_emb_to_tick_rnn_hidden[0], ACT_SELU)
         else:
             raise ValueError
-        return list(ops.split_cols(flat, self.rnn_hidden_size))
+        return _split_layers(flat, self.rnn_hidden_size, self.num_layers)
 
-    def _two_layer_step(self, rnn, gi0, h, mask):
-        w_hh0, b_hh0 = rnn.cell(0)[1], rnn.cell(0)[3]
-        h0 = _gru_step(gi0, h[0], w_hh0, b_hh0)
-        mid = ops.dropout_mask(h0, mask, self.dropout) if mask is not None else h0
-        w_ih1, w_hh1, b_ih1, b_hh1 = rnn.cell(1)
-        gi1 = ops.dense(mid, w_ih1, b_ih1, Link.dense(w_ih1.shape[1], w_ih1.shape[0]), ACT_NONE)
-        h1 = _gru_step(gi1, h[1], w_hh1, b_hh1)
-        return [h0, h1]
+    def _stack_step(self, rnn, gi0, h, masks):
+        """one time step of the layer stack: h = the layers' states, masks = per boundary a keep-mask (B, H), or None"""
+        new = [_gru_step(gi0, h[0], rnn.cell(0)[1], rnn.cell(0)[3])]
+        for layer in range(1, self.num_layers):
+            mid = ops.dropout_mask(new[-1], masks[layer - 1], self.dropout) if masks is not None else new[-1]
+            w_ih, w_hh, b_ih, b_hh = rnn.cell(layer)
+            gi = ops.dense(mid, w_ih, b_ih, Link.dense(w_ih.shape[1], w_ih.shape[0]), ACT_NONE)
+            new.append(_gru_step(gi, h[layer], w_hh, b_hh))
+        return new
 
     def forward(self, z, score_tensor, train):
         if z.size(1) != self.z_dim or z.size(0) != score_tensor.size(0):
@@ -320,14 +358,16 @@ class HierarchicalDecoder(Decoder):
         uniforms = None                                        # drawn only by a forward that samples: argmax consumes no offset
         if sampling == 'multinomial' and not teacher_forced:
             uniforms = self._sampling_uniforms(b, z.device)
-        masks = (None, None)
-        if self.training and self.dropout > 0:
+        masks = (None, None)                                   # per RNN: its layers-1 boundaries' keep-masks
+        layers, h = self.num_layers, self.rnn_hidden_size
+        if self.training and self.dropout > 0 and layers > 1:  # nn.GRU drops between layers only
             if self._mask_queue:
-                masks = tuple(m.to(z.device) for m in self._mask_queue.popleft())
+                beat, tick = (m.to(z.device) for m in self._mask_queue.popleft())
+                masks = (_boundary_masks(beat, layers, (4, b, h), 'beat'), _boundary_masks(tick, layers, (24, b, h), 'tick'))
             else:
-                h = self.rnn_hidden_size                    # one draw for the beat (4 steps) and the tick (24 steps) masks
-                both = ops.keep_mask((4 + 24, b, h), self.dropout, z.device)
-                masks = (both[:4], both[4:])
+                # per boundary ONE draw (one Philox offset) for the beat (4 steps) and the tick (24 steps) masks, lowest boundary first
+                both = [ops.keep_mask((4 + 24, b, h), self.dropout, z.device) for _ in range(layers - 1)]
+                masks = ([m[:4] for m in both], [m[4:] for m in both])
         if _use_sequence_kernels(self.rnn_hidden_size):
             beat_out = self.beat_rnn_sequence(z, 4, masks[0])
             return self.tick_rnn_sequence(score_tensor, beat_out, 6, teacher_forced, masks[1], uniforms)
@@ -354,18 +394,20 @@ class HierarchicalDecoder(Decoder):
             self.train(saved[3])
 
     # ---- whole-sequence path ------------------------------------------------------------------------------------
-    def _two_layer_sequence(self, rnn, steps, gi0, h0, mask):
-        """2-layer unidirectional GRU over `steps`: gi0 (T, R, 3H) or (R, 3H); h0 = [layer-0, layer-1] initial states;
-        mask (T*R, H) keep-mask on the layer-0 outputs (nn.GRU's inter-layer dropout).  -> layer-1 outputs (T, R, H)"""
+    def _stack_sequence(self, rnn, steps, gi0, h0, masks):
+        """unidirectional GRU stack over `steps`: gi0 (T, R, 3H) or (R, 3H); h0 = the layers' initial states; masks = per boundary a
+        (T*R, H) keep-mask on the lower layer's outputs (nn.GRU's inter-layer dropout), or None.  -> top layer's outputs (T, R, H)"""
         hid = self.rnn_hidden_size
-        out0, _ = ops.gru_sequence(steps, [(gi0, rnn.cell(0)[1], rnn.cell(0)[3], h0[0], False)], finals=False)
-        rows = out0.shape[1]
-        mid = out0.view(steps * rows, hid)
-        if mask is not None:
-            mid = ops.dropout_mask(mid, mask, self.dropout)
-        w_ih1, w_hh1, b_ih1, b_hh1 = rnn.cell(1)
-        gi1 = ops.dense(mid, w_ih1, b_ih1, Link.dense(w_ih1.shape[1], w_ih1.shape[0]), ACT_NONE).view(steps, rows, -1)
-        return ops.gru_sequence(steps, [(gi1, w_hh1, b_hh1, h0[1], False)], finals=False)[0]
+        out, _ = ops.gru_sequence(steps, [(gi0, rnn.cell(0)[1], rnn.cell(0)[3], h0[0], False)], finals=False)
+        rows = out.shape[1]
+        for layer in range(1, self.num_layers):
+            mid = out.view(steps * rows, hid)
+            if masks is not None:
+                mid = ops.dropout_mask(mid, masks[layer - 1], self.dropout)
+            w_ih, w_hh, b_ih, b_hh = rnn.cell(layer)
+            gi = ops.dense(mid, w_ih, b_ih, Link.dense(w_ih.shape[1], w_ih.shape[0]), ACT_NONE).view(steps, rows, -1)
+            out = ops.gru_sequence(steps, [(gi, w_hh, b_hh, h0[layer], False)], finals=False)[0]
+        return out
 
     def beat_rnn_sequence(self, z, seq_len, mask=None):
         """-> (4, B, H) beat embeddings (decoder.py:436-457)"""
@@ -374,8 +416,8 @@ class HierarchicalDecoder(Decoder):
         w_ih0, _, b_ih0, _ = self.rnn_beat.cell(0)
         x0 = ops.broadcast_rows(self.b_0, b)
         gi0 = ops.dense(x0, w_ih0, b_ih0, Link.dense(1, w_ih0.shape[0]), ACT_NONE)           # the same input every beat
-        m = None if mask is None else mask.contiguous().view(seq_len * b, -1)
-        return self._two_layer_sequence(self.rnn_beat, seq_len, gi0, h, m)
+        m = None if mask is None else [k.contiguous().view(seq_len * b, -1) for k in mask]
+        return self._stack_sequence(self.rnn_beat, seq_len, gi0, h, m)
 
     def tick_rnn_sequence(self, score_tensor, beat_out, tick_seq_len, teacher_forced, mask=None, uniforms=None):
         """The tick RNN restarts from a beat-dependent hidden state at every beat (decoder.py:459-525), so given the
@@ -388,16 +430,16 @@ class HierarchicalDecoder(Decoder):
         ticks = nb * steps
         bo = beat_out.view(nb * b, hid)
         la, lb = self.beat_emb_to_tick_rnn_hidden[0], self.beat_emb_to_tick_rnn_input[0]
-        both = ops.dense_pair(bo, la.weight, la.bias, lb.weight, lb.bias, ACT_SELU)           # (4B, 2H + H) or None
+        both = ops.dense_pair(bo, la.weight, la.bias, lb.weight, lb.bias, ACT_SELU)           # (4B, L H + H) or None
         if both is not None:
             flat, beat_emb = ops.split_cols(both, la.weight.shape[0])
-            h0 = list(ops.split_cols(flat, hid))
+            h0 = _split_layers(flat, hid, self.num_layers)
         else:
             h0 = self.hidden_init(bo, 'tick')
             beat_emb = _lin(bo, lb, ACT_SELU)                                                  # (4B, H)
         m = None
-        if mask is not None:                                                                   # (24, B, H) -> rows (j, beat, b)
-            m = mask.view(nb, steps, b, hid).transpose(0, 1).contiguous().view(steps * nb * b, hid)
+        if mask is not None:                                                                   # per boundary (24, B, H) -> rows (j, beat, b)
+            m = [k.view(nb, steps, b, hid).transpose(0, 1).contiguous().view(steps * nb * b, hid) for k in mask]
         if self.use_teacher_forcing and teacher_forced:
             tokens = score_tensor
         else:
@@ -414,8 +456,8 @@ class HierarchicalDecoder(Decoder):
             prev = prev.view(nb, steps, b, -1).transpose(0, 1).reshape(steps * nb * b, -1)     # rows (j, beat, b)
             inp = ops.concat_cols(prev, beat_emb[None].expand(steps, -1, -1).reshape(steps * nb * b, hid))
             gi0 = ops.dense(inp, w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE).view(steps, nb * b, -1)
-        out1 = self._two_layer_sequence(self.rnn_tick, steps, gi0, h0, m)                      # (6, 4B, H)
-        probs = _lin(out1.view(steps * nb * b, hid), self.tick_emb_to_note_emb[0], ACT_RELU)
+        top = self._stack_sequence(self.rnn_tick, steps, gi0, h0, m)                           # (6, 4B, H)
+        probs = _lin(top.view(steps * nb * b, hid), self.tick_emb_to_note_emb[0], ACT_RELU)
         weights = probs.view(steps, nb, b, -1).permute(2, 1, 0, 3).reshape(b, ticks, -1)       # tick = 6*beat + j
         return weights, tokens[:, None, :]
 
@@ -425,30 +467,41 @@ class HierarchicalDecoder(Decoder):
         nb, b = beat_out.shape[0], beat_out.shape[1]
         hid = self.rnn_hidden_size
         w_ih0, w_hh0, b_ih0, b_hh0 = self.rnn_tick.cell(0)
-        if os.environ.get('ARVAE_TICK_STEPWISE', '0') != '1' and ops.tick_free_run_supported(hid, self.num_notes):
-            # one launch (csrc/gru_seq.hip tick_free_run_kernel).  W_ih0 acts on [previous-note embedding | beat
-            # embedding]: the beat half is applied once per beat, the note half once per vocabulary entry (+ x_0).
+        layers = self.num_layers
+        stepwise = os.environ.get('ARVAE_TICK_STEPWISE', '0') == '1'
+        one_launch = not stepwise and (ops.tick_free_run_supported(hid, self.num_notes) if layers == 2 else
+                                       ops.tick_free_run_layers_supported(hid, self.num_notes, layers))
+        if one_launch:
+            # one launch (csrc/gru_seq.hip: tick_free_run_h2_kernel for two layers, tick_free_run_layers_kernel otherwise).  W_ih0
+            # acts on [previous-note embedding | beat embedding]: the beat half is applied once per beat, the note half once per
+            # vocabulary entry (+ x_0).
             emb_dim = self.note_embedding_dim
             w_note, w_beat = w_ih0.detach()[:, :emb_dim].contiguous(), w_ih0.detach()[:, emb_dim:].contiguous()
             gib = ops.dense(beat_emb.detach(), w_beat, b_ih0.detach(), Link.dense(hid, 3 * hid), ACT_NONE)
             table = torch.cat((self.note_embedding_layer.weight.detach(), self.x_0.detach()[None]), 0)
             ptab = ops.dense(table, w_note, None, Link.dense(emb_dim, 3 * hid), ACT_NONE)
-            w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
             out = self.tick_emb_to_note_emb[0]
-            weights = tuple(t.detach() for t in (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias))
-            return ops.tick_free_run(weights, h0[0].detach(), h0[1].detach(), gib, ptab,
-                                     None if mask is None else mask.contiguous(), 1.0 / (1.0 - self.dropout), b, nb, 6,
-                                     uniforms=uniforms, temperature=self.temperature)
+            keep_scale = 1.0 / (1.0 - self.dropout)
+            if layers == 2:
+                w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
+                weights = tuple(t.detach() for t in (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias))
+                return ops.tick_free_run(weights, h0[0].detach(), h0[1].detach(), gib, ptab,
+                                         None if mask is None else mask[0].contiguous(), keep_scale, b, nb, 6,
+                                         uniforms=uniforms, temperature=self.temperature)
+            cells = [tuple(t.detach() for t in self.rnn_tick.cell(k)) for k in range(layers)]     # the boundaries' masks: (layers-1, 24, B, H)
+            return ops.tick_free_run_layers(cells, out.weight.detach(), out.bias.detach(), [s.detach() for s in h0], gib, ptab,
+                                            None if mask is None else torch.stack([k.contiguous() for k in mask], 0),
+                                            keep_scale, b, nb, 6, uniforms=uniforms, temperature=self.temperature)
         prev = self.x_0.detach()[None].expand(b, -1).contiguous()
         tokens = []
         for i in range(nb):
-            h = [h0[0].detach()[i * b:(i + 1) * b], h0[1].detach()[i * b:(i + 1) * b]]
+            h = [s.detach()[i * b:(i + 1) * b] for s in h0]
             be = beat_emb.detach()[i * b:(i + 1) * b]
             for j in range(6):
                 t = i * 6 + j
                 gi0 = ops.dense(ops.concat_cols(prev, be), w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
-                h = self._two_layer_step(self.rnn_tick, gi0, h, None if mask is None else mask[t].contiguous())
-                probs = _lin(h[1], self.tick_emb_to_note_emb[0], ACT_RELU)
+                h = self._stack_step(self.rnn_tick, gi0, h, None if mask is None else [k[t].contiguous() for k in mask])
+                probs = _lin(h[-1], self.tick_emb_to_note_emb[0], ACT_RELU)
                 idx = ops.row_argmax(probs) if uniforms is None else ops.row_sample(probs, uniforms[:, t].contiguous(), self.temperature)
                 prev = ops.embed(idx.view(b, 1), self.note_embedding_layer.weight).view(b, -1)
                 tokens.append(idx)
@@ -462,8 +515,8 @@ class HierarchicalDecoder(Decoder):
         gi0 = ops.dense(x0, w_ih0, b_ih0, Link.dense(1, w_ih0.shape[0]), ACT_NONE)
         out = []
         for i in range(seq_len):
-            h = self._two_layer_step(self.rnn_beat, gi0, h, None if mask is None else mask[i].contiguous())
-            out.append(h[1])
+            h = self._stack_step(self.rnn_beat, gi0, h, None if mask is None else [k[i].contiguous() for k in mask])
+            out.append(h[-1])
         return out
 
     def forward_tick_rnn(self, score_tensor, beat_rnn_out, tick_seq_len, teacher_forced, sampling, mask=None, uniforms=None):
@@ -482,8 +535,8 @@ class HierarchicalDecoder(Decoder):
                 t = i * tick_seq_len + j
                 inp = ops.concat_cols(prev, beat_emb)
                 gi0 = ops.dense(inp, w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
-                h = self._two_layer_step(self.rnn_tick, gi0, h, None if mask is None else mask[t].contiguous())
-                probs = _lin(h[1], self.tick_emb_to_note_emb[0], ACT_RELU)
+                h = self._stack_step(self.rnn_tick, gi0, h, None if mask is None else [k[t].contiguous() for k in mask])
+                probs = _lin(h[-1], self.tick_emb_to_note_emb[0], ACT_RELU)
                 if self.use_teacher_forcing and teacher_forced:
                     idx = score_tensor[:, t].contiguous()
                 elif sampling == 'multinomial':

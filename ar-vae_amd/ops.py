@@ -827,6 +827,42 @@ def tick_free_run(weights, h0_l0, h0_l1, gib, ptab, mask, keep_scale, batch, bea
     return tokens
 
 
+def tick_free_run_layers_supported(hidden, vocab, layers):
+    """True when the one-launch free-running tick decoder is built for a `layers`-deep tick RNN other than the two-layer one
+    (tick_free_run_supported / tick_free_run); else go tick by tick."""
+    return bool(_lib.load().arvae_tick_free_run_layers_supported(int(hidden), int(vocab), int(layers)))
+
+
+def tick_free_run_layers(cells, w_out, b_out, h0, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, uniforms=None,
+                         temperature=1.0):
+    """tick_free_run for a GRU stack of len(cells) layers (arvae_tick_free_run_layers): cells[l] = (w_ih, w_hh, b_ih, b_hh) of layer l
+    (layer 0's input weights are not read: gib / ptab hold their products), h0 = the layers' initial states (beats*B, H) each,
+    mask None or uint8 (layers-1, beats*ticks_per_beat, B, H), one keep-mask per layer boundary."""
+    layers = len(cells)
+    if len(h0) != layers or layers > _lib.TICK_MAX_LAYERS:
+        raise ValueError(f'{layers} layers need {layers} initial states (at most {_lib.TICK_MAX_LAYERS} layers)')
+    h0 = [s.contiguous() for s in h0]
+    _dev(*[t for c in cells for t in c], w_out, b_out, *h0, gib, ptab, mask, uniforms)
+    lib = _lib.load()
+    hid, vocab, ticks = cells[0][1].shape[1], w_out.shape[0], beats * ticks_per_beat
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (layers - 1, ticks, batch, hid)):
+        raise ValueError(f'keep-masks must be uint8 of shape {(layers - 1, ticks, batch, hid)}, got {mask.dtype} {tuple(mask.shape)}')
+    ts = _lib.TickStack()
+    ts.layers = layers
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(cells):
+        ts.w_ih[l], ts.w_hh[l], ts.b_ih[l], ts.b_hh[l], ts.h0[l] = _ptr(w_ih), _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(h0[l])
+    ts.w_out, ts.b_out, ts.h0_stride = _ptr(w_out), _ptr(b_out), 0
+    tokens = torch.empty(batch, ticks, device=gib.device, dtype=torch.int64)
+    ws = torch.empty(lib.arvae_tick_free_run_layers_ws_floats(hid, layers), device=gib.device, dtype=torch.float32)
+    u = None if uniforms is None else _sampling_uniforms(uniforms, (batch, ticks))
+    mask = None if mask is None else mask.contiguous()
+    with _timed('tick_free_run_layers', 2.0 * batch * ticks * (3 * (2 * layers - 1) * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_free_run_layers(ctypes.byref(ts), _ptr(gib), _ptr(ptab), _ptr(mask), float(keep_scale), batch, beats,
+                                                  ticks_per_beat, hid, vocab, _ptr(u), 1.0 / float(temperature), _ptr(tokens),
+                                                  _ptr(ws), _stream()), 'tick_free_run_layers')
+    return tokens
+
+
 def _sampling_uniforms(u, shape):
     if u.dtype != torch.float32 or tuple(u.shape) != tuple(shape):
         raise ValueError(f'sampling uniforms must be float32 of shape {tuple(shape)}, got {u.dtype} {tuple(u.shape)}')

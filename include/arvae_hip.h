@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 14  /* 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 15  /* 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -320,6 +320,31 @@ int arvae_tick_free_run_sampled(const arvae_tick_weights_t *weights, const float
                                 const float *gib, const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
                                 int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
                                 int64_t *tokens, float *ws, arvae_stream_t stream);
+
+/* The free-running pass for tick RNNs of OTHER layer counts than two (nn.GRU(num_layers = layers), measurevae/decoder.py:331-363;
+ * two layers: arvae_tick_free_run above).  The same contract: gib / ptab pre-multiplied with layer 0's input weights, the states of
+ * all layers restarted from h0[l] [beats*batch][hidden] (row = beat*batch + b, rows h0_stride floats apart) at every beat, the
+ * note projection + ReLU on the TOP layer's state (layer 0's when layers == 1), tokens [batch][beats*ticks_per_beat] the only output.
+ * mask: optional keep-masks of the layers-1 layer boundaries, [layers-1][beats*ticks_per_beat][batch][hidden], boundary (l -> l+1)
+ * at index l, scaled by keep_scale (ignored when layers == 1).  uniforms NULL: the top-1 note is fed back (lowest index on ties);
+ * else [batch][beats*ticks_per_beat] in (0, 1] and inv_temperature, the draw of arvae_tick_free_run_sampled.
+ * w_ih[0] / b_ih[0] are not read.  ws: arvae_tick_free_run_layers_ws_floats(hidden, layers) floats, 16-byte aligned, required. */
+#define ARVAE_TICK_MAX_LAYERS 4
+typedef struct arvae_tick_stack {
+    int32_t layers, reserved;
+    const float *w_ih[ARVAE_TICK_MAX_LAYERS], *w_hh[ARVAE_TICK_MAX_LAYERS];   /* rnn_tick weight_ih_l{k} / weight_hh_l{k} [3*hidden][hidden] */
+    const float *b_ih[ARVAE_TICK_MAX_LAYERS], *b_hh[ARVAE_TICK_MAX_LAYERS];
+    const float *w_out, *b_out;                /* tick_emb_to_note_emb [vocab][hidden] */
+    const float *h0[ARVAE_TICK_MAX_LAYERS];    /* initial states per layer */
+    int64_t h0_stride;                         /* 0 = hidden */
+} arvae_tick_stack_t;
+/* 1 when arvae_tick_free_run_layers is offered for (hidden, vocab, layers): the shapes of arvae_tick_free_run_supported, layers in
+ * {1, 3, 4}, and three or four layers only up to hidden 64; otherwise the caller runs the decoder tick by tick. */
+int arvae_tick_free_run_layers_supported(int32_t hidden, int32_t vocab, int32_t layers);
+int64_t arvae_tick_free_run_layers_ws_floats(int32_t hidden, int32_t layers);
+int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask,
+                               float keep_scale, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab,
+                               const float *uniforms, float inv_temperature, int64_t *tokens, float *ws, arvae_stream_t stream);
 
 /* nn.Embedding (measurevae/encoder.py:36-37,111; decoder.py:18,516): out row (b,t) = table[idx[b][t]];
  * time_major: rows ordered (t, b) instead of (b, t).  embed_bwd adds to (accumulate != 0) or overwrites dtable, in a fixed summation order, and needs
