@@ -472,7 +472,7 @@ class HierarchicalDecoder(Decoder):
         one_launch = not stepwise and (ops.tick_free_run_supported(hid, self.num_notes) if layers == 2 else
                                        ops.tick_free_run_layers_supported(hid, self.num_notes, layers))
         if one_launch:
-            # one launch (csrc/gru_seq.hip: tick_free_run_h2_kernel for two layers, tick_free_run_layers_kernel otherwise).  W_ih0
+            # one launch (csrc/tick_decoder.hip: tick_free_run_h2_kernel for two layers, tick_free_run_layers_kernel otherwise).  W_ih0
             # acts on [previous-note embedding | beat embedding]: the beat half is applied once per beat, the note half once per
             # vocabulary entry (+ x_0).
             emb_dim = self.note_embedding_dim

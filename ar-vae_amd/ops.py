@@ -803,7 +803,7 @@ def tick_free_run_supported(hidden, vocab):
 
 
 def tick_free_run(weights, h0_l0, h0_l1, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, uniforms=None, temperature=1.0):
-    """tokens (B, beats*ticks_per_beat) int64 of the free-running tick decoder; no autograd (csrc/gru_seq.hip).
+    """tokens (B, beats*ticks_per_beat) int64 of the free-running tick decoder; no autograd (csrc/tick_decoder.hip).
     weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, w_out, b_out).
     uniforms None: the top-1 note is fed back (arvae_tick_free_run).  uniforms (B, beats*ticks_per_beat) float32 in (0, 1]: the note
     drawn from softmax(logits / temperature) by inverting its CDF at that tick's uniform (arvae_tick_free_run_sampled)."""

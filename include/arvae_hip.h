@@ -294,7 +294,7 @@ int arvae_gru_seq_bwd(const arvae_gru_seq_t *seqs, int32_t nseq, int32_t steps, 
  * The layer-0 input projection arrives pre-multiplied: gib [beats*batch][3*hidden] = W_ih0[:, E:] beat_emb + b_ih0 and
  * ptab [vocab+1][3*hidden] = W_ih0[:, :E] applied to the embedding table, row `vocab` = the learned start vector x_0.
  * mask: optional keep-mask [beats*ticks_per_beat][batch][hidden] of nn.GRU's inter-layer dropout, scaled by keep_scale.
- * ws: arvae_tick_free_run_ws_floats(hidden) floats, 16-byte aligned (the recurrent weights re-laid out for streaming). */
+ * ws: arvae_tick_free_run_ws_floats(hidden) floats, 16-byte aligned, required (the recurrent weights re-laid out for streaming). */
 typedef struct arvae_tick_weights {
     const float *w_hh0, *b_hh0;     /* rnn_tick layer 0 recurrent weights */
     const float *w_ih1, *b_ih1, *w_hh1, *b_hh1;   /* layer 1 */

@@ -104,6 +104,9 @@ def test_argument_validation_without_gpu(lib):
     assert lib.arvae_gru_seq_bwd(seqs, 5, 24, 16, 128, None) == -1
     assert lib.arvae_tick_free_run(ctypes.byref(TickWeights()), None, None, 0, None, None, None, 2.0, 8, 4, 6, 128, 35, None,
                                    None, None) == -1
+    buf = ctypes.cast((ctypes.c_float * 64)(), ctypes.c_void_p)       # every pointer set but the workspace: required
+    assert lib.arvae_tick_free_run(ctypes.byref(TickWeights(*([buf] * 8))), buf, buf, 0, buf, buf, buf, 2.0, 8, 4, 6, 128, 35, buf,
+                                   None, None) == -1 and b'workspace' in lib.arvae_last_error_string()
     assert lib.arvae_tick_free_run_ws_floats(128) == 3 * 3 * 128 * 128 * 3 // 2
     assert lib.arvae_embed_bwd_ws_floats(256, 24, 10, 35) == (256 * 24 // 64) * 35 * 10
     assert lib.arvae_dense_wgrad_batch((DenseWgradJob * 1)(), 1, None) == -1

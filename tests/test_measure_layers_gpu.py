@@ -185,6 +185,17 @@ def test_tick_layers_tokens_match_stepwise(dev, monkeypatch, layers, hid, vocab,
             assert torch.equal(again['0'][1], out['0'][1])
 
 
+@pytest.mark.parametrize('b', [5, 20])
+def test_two_layer_tokens_match_stepwise_at_hidden_32(dev, monkeypatch, b):
+    """the two-layer one-launch decoder (tick_free_run_h2_kernel behind the shared weight prep) at its smallest shape, which the 35-note
+    vocabulary does not reach: hidden 32 has one k-step and nine weight groups per tick, so the register ring is 3 deep instead of 6"""
+    assert ops.tick_free_run_supported(32, 32)
+    for dropout, tau in [(dropout, tau) for dropout in (0.0, 0.5) for tau in (None, 1.0, 0.7)]:
+        model = spread_model(2, 32, 32, dropout, dev)
+        out, u = both_paths(model, 2, b, 32, 32, dropout, tau, dev, monkeypatch)
+        assert_same_tokens(out, u, tau, b, 32)
+
+
 @pytest.mark.parametrize('layers,b,dropout,hid', [(1, 64, 0.5, 128), (3, 64, 0.5, 64), (3, 45, 0.0, 64), (1, 45, 0.0, 64)])
 def test_tick_layers_tokens_match_stepwise_big(dev, monkeypatch, layers, b, dropout, hid):
     """the `big` scaling case of test_tick_free_run_tokens_match_stepwise: initial tick states of ~1e4 and recurrent tick weights of ~350,

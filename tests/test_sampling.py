@@ -124,7 +124,9 @@ def test_tick_free_run_sampled_rejects_bad_arguments(lib):
         return lib.arvae_tick_free_run_sampled(ctypes.byref(tw), p, p, 0, p, p, None, 1.0, 1, 4, 6, hidden, vocab, uniforms, inv_t,
                                                ctypes.cast(tok, ctypes.c_void_p), ws, None)
     assert call(uniforms=None) == -1 and 'null uniforms' in _err(lib)
-    assert call(ws=None) == -1 and 'workspace' in _err(lib)                    # the fp32 kernel without a workspace stays argmax only
+    assert call(ws=None) == -1 and 'workspace' in _err(lib)
+    assert lib.arvae_tick_free_run(ctypes.byref(tw), p, p, 0, p, p, None, 1.0, 1, 4, 6, 128, 35, ctypes.cast(tok, ctypes.c_void_p), None,
+                                   None) == -1 and 'workspace' in _err(lib)     # the argmax pass needs it as well
     for bad in (0.0, -1.0, math.nan):
         assert call(inv_t=bad) == -1 and 'inverse temperature' in _err(lib)
     assert call(hidden=48) == -1 and call(vocab=65) == -1 and call(hidden=32, vocab=35) == -1       # as arvae_tick_free_run

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""tools/compare_device_code.py <objdir A> <objdir B>: is the gfx950 device code of two builds the same?
+"""tools/compare_device_code.py [--by-symbol] <objdir A> <objdir B>: is the gfx950 device code of two builds the same?
 
 For every *.o of A (ar-vae_amd/csrc/build or build_diag of two trees) the gfx950 code object is taken out of the fat binary and
 disassembled with ROCm's LLVM tools; for every kernel symbol the instruction stream and the VGPR, SGPR, LDS, scratch and spill
 figures of the two builds are compared.  Prints one line per kernel that differs (the first differing line) and a count; exit
-status 1 if anything differs or a kernel or object exists on one side only."""
+status 1 if anything differs or a kernel or object exists on one side only.
+
+--by-symbol pairs the kernels by symbol across ALL objects of each side instead of object by object (kernels that moved to another
+source file still meet their counterpart); a kernel present on one side only is reported by name."""
 import os
 import re
 import subprocess
@@ -43,9 +46,43 @@ def kernels(obj, tmp):
         m = re.match(r'<(\S+)>:', line)
         if m:
             cur = streams.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != '...':      # ('...': zero padding up to the next symbol)
             cur.append(re.sub(r'\s*//.*', '', line).strip())
     return {k: (tuple((f, r.get(f)) for f in FIGURES), streams.get(k, [])) for k, r in figures.items()}
+
+
+def differs(where, k, a, b):
+    """prints what differs between kernel k's two records (figures, instructions); False if nothing does"""
+    if a[0] != b[0]:
+        print(f'{where}{k}: ' + ', '.join(f'{f} {x} != {y}' for (f, x), (_, y) in zip(a[0], b[0]) if x != y))
+    elif a[1] != b[1]:
+        i = next((i for i, (x, y) in enumerate(zip(a[1], b[1])) if x != y), min(len(a[1]), len(b[1])))
+        print(f'{where}{k}: instruction {i}: {a[1][i:i + 1]} != {b[1][i:i + 1]}')
+    else:
+        return False
+    return True
+
+
+def main_by_symbol(dir_a, dir_b):
+    sides = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for d in (dir_a, dir_b):
+            side = {}
+            for o in sorted(f for f in os.listdir(d) if f.endswith('.o')):
+                for k, rec in kernels(os.path.join(d, o), tmp).items():
+                    if side.setdefault(k, rec) != rec:
+                        sys.exit(f'{d}: {k} is defined differently in two objects')
+            sides.append(side)
+    a, b = sides
+    differing = 0
+    for k in sorted(set(a) | set(b)):
+        if k not in a or k not in b:
+            print(f'{k}: only in {dir_a if k in a else dir_b}')
+            differing += 1
+        else:
+            differing += differs('', k, a[k], b[k])
+    print(f'{len(set(a) | set(b))} kernels ({len(a)} in {dir_a}, {len(b)} in {dir_b}): {differing} differ')
+    return 1 if differing else 0
 
 
 def main(dir_a, dir_b):
@@ -64,19 +101,15 @@ def main(dir_a, dir_b):
                 total += 1
                 if k not in a or k not in b:
                     print(f'{o}: {k}: only in {dir_a if k in a else dir_b}')
-                elif a[k][0] != b[k][0]:
-                    print(f'{o}: {k}: ' + ', '.join(f'{f} {x} != {y}' for (f, x), (_, y) in zip(a[k][0], b[k][0]) if x != y))
-                elif a[k][1] != b[k][1]:
-                    i = next((i for i, (x, y) in enumerate(zip(a[k][1], b[k][1])) if x != y), min(len(a[k][1]), len(b[k][1])))
-                    print(f'{o}: {k}: instruction {i}: {a[k][1][i:i + 1]} != {b[k][1][i:i + 1]}')
+                    differing += 1
                 else:
-                    continue
-                differing += 1
+                    differing += differs(f'{o}: ', k, a[k], b[k])
     print(f'{total} kernels in {with_kernels} objects with kernels ({len(objs)} objects): {differing} differ')
     return 1 if differing else 0
 
 
 if __name__ == '__main__':
-    if len(sys.argv) != 3:
+    args = [a for a in sys.argv[1:] if a != '--by-symbol']
+    if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit((main_by_symbol if len(args) < len(sys.argv) - 1 else main)(*args))

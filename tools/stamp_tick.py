@@ -1,4 +1,4 @@
-"""Diagnostic (a build of gru_seq.hip with -DARVAE_GRU_STAMPS [-DGRU_STAMP_WAVE=w], loaded through ARVAE_LIB): cycles per phase of a
+"""Diagnostic (a build of tick_decoder.hip with -DARVAE_GRU_STAMPS [-DGRU_STAMP_WAVE=w], loaded through ARVAE_LIB): cycles per phase of a
 tick of the free-running decoder (tick_free_run_h2_kernel), B = 256, H = 128, 4 beats x 6 ticks, vocabulary 35, dropout 0.5."""
 import ctypes, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

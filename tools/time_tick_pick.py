@@ -1,4 +1,4 @@
-"""Time of one launch of the free-running tick decoder (weight prep + tick_free_run_h2_kernel), top-1 feedback and -- where the library
+"""Time of one launch of the free-running tick decoder (csrc/tick_decoder.hip: the two weight prep launches + tick_free_run_h2_kernel), top-1 feedback and -- where the library
 has it -- multinomial feedback: B = 256, H = 128, 4 beats x 6 ticks, vocabulary 35, dropout 0.5.  HIP events around every launch,
 median over --launches launches after a warm-up, --repeats times (the spread of the medians is the yardstick for a difference).
 --lib takes any build of the library (an earlier commit's too: the entry points are called through ctypes directly, whatever its ABI
