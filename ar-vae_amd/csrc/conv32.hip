@@ -10,7 +10,7 @@
 // (Generations removed on the way: the same tilings on v_mfma_f32_32x32x2_f32, 45-50 us per 16x16-layer launch; a two-term
 // bf16 experiment, 16 bits: flipped ReLU units; three-term bf16 with six products, 26-33 us per 16x16-layer launch, round 3.)
 //
-// Design rules (measured, profiles/r1_down32_phase_stamps.txt, tools/stamp_conv32.py): on gfx950 the fp32 MFMA
+// Design rules (measured, profiles/r1_down32_phase_stamps.txt, tools/stamp.py conv32): on gfx950 the fp32 MFMA
 // (64 cycles each, runs at the fp32 vector rate) does NOT co-execute with VALU work of another wave on the same
 // SIMD, so SIMD time = MFMA cycles + VALU cycles; a CU moves store data at ~16 B/clk.  Hence:
 //   * one 256-thread workgroup per CU (one wave per SIMD), persistent over tiles of 128 / 64 / 32 lo pixels
@@ -36,6 +36,7 @@
 #include "regloss.h"
 #include "down32p.h"
 #include "wgrad32r.h"
+#include "stamps.h"
 
 #include <type_traits>
 
@@ -153,25 +154,13 @@ struct PatchLoader {
     }
 };
 
-#ifdef ARVAE_STAMPS
-// diagnostic build only (tools/stamp_conv32.py): per-workgroup phase timeline, 64 slots, s_memtime + wall clock
-__device__ unsigned long long g_stamps[512 * 64 * 2];
-#define STAMP(slot)                                                                      \
-    do {                                                                                 \
-        if (LO == 16 && threadIdx.x == 0 && BID < 512 && (slot) < 64) {                  \
-            g_stamps[(BID * 64 + (slot)) * 2] = __builtin_readcyclecounter();            \
-            g_stamps[(BID * 64 + (slot)) * 2 + 1] = wall_clock64();                      \
-        }                                                                                \
-    } while (0)
-#define STAMP_WAIT() __builtin_amdgcn_s_waitcnt(0)
+#ifdef ARVAE_STAMPS_CONV32
+// diagnostic build only (stamps.h): phase timeline of the <16> kernels, one row per workgroup (thread 0)
+ARVAE_STAMP_TABLE(conv32, 512, 64, 2)
+#define STAMP(slot) do { if (LO == 16 && threadIdx.x == 0) ARVAE_STAMP(g_conv32_stamps, BID, slot); } while (0)
+#define STAMP_WAIT() stamp_wait_all()
 // up32p_kernel: row blockIdx.x = its consumers (thread 0), row 256 + blockIdx.x = its producers (thread 256)
-#define PSTAMP(role, slot)                                                               \
-    do {                                                                                 \
-        if (threadIdx.x == 256 * (role) && BID < 256 && (slot) < 64) {                   \
-            g_stamps[((BID + 256 * (role)) * 64 + (slot)) * 2] = __builtin_readcyclecounter();            \
-            g_stamps[((BID + 256 * (role)) * 64 + (slot)) * 2 + 1] = wall_clock64();                      \
-        }                                                                                \
-    } while (0)
+#define PSTAMP(role, slot) do { if (threadIdx.x == 256 * (role) && BID < 256) ARVAE_STAMP(g_conv32_stamps, BID + 256 * (role), slot); } while (0)
 #else
 #define STAMP(slot)
 #define STAMP_WAIT()
@@ -1644,18 +1633,3 @@ int conv32_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
 
 }  // namespace arvae
 
-#ifdef ARVAE_STAMPS
-extern "C" int arvae_debug_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_stamps), sizeof(unsigned long long) * count);
-}
-#endif
-#ifdef D32K_STAMPS
-extern "C" int arvae_debug_d32k_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_d32k_stamps), sizeof(unsigned long long) * count);
-}
-#endif
-#ifdef WGR_STAMPS
-extern "C" int arvae_debug_wgr_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_wgr_stamps), sizeof(unsigned long long) * count);
-}
-#endif

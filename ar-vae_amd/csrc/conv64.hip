@@ -16,6 +16,7 @@
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
 #include "conv64.h"
+#include "stamps.h"
 
 namespace arvae {
 
@@ -335,11 +336,15 @@ __global__ __launch_bounds__(256) void conv_rows_h2_kernel(ConvRows g) {
 //   * a tile is 64 consecutive output pixels of an image in row-major order (94 % of the MFMA rows at 22 x 22), workgroups walk
 //     tiles persistently, four workgroups per CU hide each other's staging round trip.
 // Arithmetic: scaled two-term fp16, three products (splitmath.h); plain sources that come with their maxima.
-#ifdef S8_STAMPS
-__device__ unsigned long long g_s8_stamps[8];
-#define S8STAMP(k) { const unsigned long long now_ = __builtin_readcyclecounter(); s8ph[k] += now_ - s8tc; s8tc = now_; }
+#ifdef ARVAE_STAMPS_S8
+ARVAE_STAMP_TABLE(s8, 1, 8, 1)                                   // diagnostic build only (stamps.h): cycles per phase of a tile + the tile count,
+#define S8STAMP_BEGIN() PhaseSums<7> s8ph                        // thread 0 of workgroup 0
+#define S8STAMP(k) s8ph.mark(k)
+#define S8STAMP_END(tiles) do { if (blockIdx.x == 0 && threadIdx.x == 0) s8ph.flush(g_s8_stamps, tiles); } while (0)
 #else
+#define S8STAMP_BEGIN()
 #define S8STAMP(k)
+#define S8STAMP_END(tiles)
 #endif
 constexpr int S8_PIX = 255;                                      // staged source pixels per tile (one per thread; 255 = the zero pixel)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_s8_h2_kernel(ConvRows g, int tiles_per_img, int n_tiles) {
@@ -403,9 +408,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         sb = buf_load4(rs_src, ok ? off + 16u : OOB);
     };
     fetch_src(blockIdx.x);
-#ifdef S8_STAMPS
-    unsigned long long s8ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s8tc = __builtin_readcyclecounter();
-#endif
+    S8STAMP_BEGIN();
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         int img, P0, sy0, nrows;
         geom(tile, img, P0, sy0, nrows);
@@ -493,12 +496,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         }
         S8STAMP(6);
     }
-#ifdef S8_STAMPS
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (int k = 0; k < 7; ++k) g_s8_stamps[k] = s8ph[k];
-        g_s8_stamps[7] = (n_tiles - 1) / gridDim.x + 1;
-    }
-#endif
+    S8STAMP_END((n_tiles - 1) / gridDim.x + 1);
     if (g.amax_out != nullptr) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
@@ -1223,8 +1221,3 @@ int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
 
 }  // namespace arvae
 
-#ifdef S8_STAMPS
-extern "C" int arvae_debug_s8_stamps(unsigned long long *out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_s8_stamps), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -1;
-}
-#endif

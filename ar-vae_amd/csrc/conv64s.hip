@@ -33,11 +33,12 @@
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
 #include "conv64.h"
+#include "stamps.h"
 
-#ifdef C64S_STAMPS
-// diagnostic build only (tools/stamp_c64s.py): phase timeline of the first 64 workgroups, 100 MHz wall clock
-namespace arvae { __device__ unsigned long long g_c64s_stamps[64 * 64]; }
-#define CSTAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 64 && (slot) < 64) ::arvae::g_c64s_stamps[blockIdx.x * 64 + (slot)] = wall_clock64(); } while (0)
+#ifdef ARVAE_STAMPS_C64S
+// diagnostic build only (stamps.h): phase timeline of the first 64 workgroups (thread 0)
+namespace arvae { ARVAE_STAMP_TABLE(c64s, 64, 64, 1) }
+#define CSTAMP(slot) do { if (threadIdx.x == 0) ARVAE_STAMP(::arvae::g_c64s_stamps, blockIdx.x, slot); } while (0)
 #else
 #define CSTAMP(slot)
 #endif
@@ -579,8 +580,3 @@ int conv64s_run(const Operand &src, int n, int sh, int sw, int oh, int ow, int q
 
 }  // namespace arvae
 
-#ifdef C64S_STAMPS
-extern "C" int arvae_debug_c64s_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_c64s_stamps), sizeof(unsigned long long) * count);
-}
-#endif

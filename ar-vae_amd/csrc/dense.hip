@@ -18,6 +18,7 @@
 #include "x3tile.h"
 #include "wgrad_c1s.h"
 #include "conv_c1.h"
+#include "stamps.h"
 
 namespace arvae {
 
@@ -342,11 +343,12 @@ struct TileLoader {
 // The product on the bf16 MFMA at fp32 accuracy: operands split into three bf16 terms when they are committed to
 // LDS ([p][r] planes, r contiguous), six partial products per multiply-add on v_mfma_f32_32x32x16_bf16, smallest first
 // (2.7x fewer MFMA cycles than the fp32 32x32x2).
-#ifdef RG_STAMPS
-// diagnostic build only (tools/stamp_rg.py): phase timeline of the first 512 workgroups of a rows-GEMM launch, 100 MHz wall clock
-__device__ unsigned long long g_rg_stamps[512 * 32];
-#define RGSTAMP(slot) do { if (threadIdx.x == 0 && (slot) < 32) { const int wg_ = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; if (wg_ < 512) g_rg_stamps[wg_ * 32 + (slot)] = wall_clock64(); } } while (0)
-#define RGWAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#ifdef ARVAE_STAMPS_RG
+// diagnostic build only (stamps.h): phase timeline of the first 512 workgroups of a rows-GEMM launch (thread 0; the slot is
+// tested before the workgroup number is worked out, as it was when profiles/r2_phase_stamps.txt was taken)
+ARVAE_STAMP_TABLE(rg, 512, 32, 1)
+#define RGSTAMP(slot) do { if (threadIdx.x == 0 && (slot) < 32) ARVAE_STAMP(g_rg_stamps, int((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x), slot); } while (0)
+#define RGWAIT() stamp_wait_loads()
 #else
 #define RGSTAMP(slot)
 #define RGWAIT()
@@ -988,12 +990,14 @@ __global__ __launch_bounds__(256) void rows_wgrad_batch_kernel(RowsGemmBatch b) 
 // operands were written a whole pass ago and come from HBM with a row pitch of 1-2 KB, so a tile lives on memory
 // latency (a single tile takes ~16 us cold, 9 us when its input was just read: measured per job).
 
-#ifdef DW_STAMPS
-// diagnostic build only (tools/stamp_dw.py): phase timeline of the first 512 weight-gradient tiles, 100 MHz wall clock
-__device__ unsigned long long g_dw_stamps[512 * 8];
-#define DW_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512) g_dw_stamps[blockIdx.x * 8 + (slot)] = wall_clock64(); } while (0)
+#ifdef ARVAE_STAMPS_DW
+// diagnostic build only (stamps.h): phase timeline of the first 512 weight-gradient tiles (thread 0)
+ARVAE_STAMP_TABLE(dw, 512, 8, 1)
+#define DW_STAMP(slot) do { if (threadIdx.x == 0) ARVAE_STAMP(g_dw_stamps, blockIdx.x, slot); } while (0)
+#define DW_STAMP_DRAINED(slot) do { stamp_wait_all(); DW_STAMP(slot); } while (0)     // the loads and stores in flight first
 #else
 #define DW_STAMP(slot)
+#define DW_STAMP_DRAINED(slot)
 #endif
 
 template <int MODE, int NWT>
@@ -1031,9 +1035,7 @@ __device__ __forceinline__ void dense_wgrad_loop(const DenseArgs &p, int ncol, i
             for (int t = 0; t < 4; ++t) bsum += a[u][t];
             mfma4(acc, a[u], b[u]);
         }
-#ifdef DW_STAMPS
-        if (q0 == wave) { __builtin_amdgcn_s_waitcnt(0); DW_STAMP(2); }
-#endif
+        if (q0 == wave) { DW_STAMP_DRAINED(2); }
     }
 }
 
@@ -1094,10 +1096,7 @@ __device__ __forceinline__ void dense_wgrad_tile(const DenseArgs &p, int bx, int
             p.dbias[n] = (p.store ? 0.f : p.dbias[n]) + tot;
         }
     }
-#ifdef DW_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);
-    DW_STAMP(6);
-#endif
+    DW_STAMP_DRAINED(6);
 }
 
 __global__ __launch_bounds__(DENSE_THREADS) void dense_wgrad_kernel(DenseArgs p) {
@@ -1477,11 +1476,6 @@ int dense_wgrad_flush_with_c1(DenseWgradBatch *b, const arvae_link_t *l, const O
 
 }  // namespace arvae
 
-#ifdef DW_STAMPS
-extern "C" int arvae_debug_dw_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_dw_stamps), sizeof(unsigned long long) * count);
-}
-#endif
 
 // Several Linear weight gradients in one launch for callers outside the whole-model executor (the MeasureVAE's autograd
 // graph queues its batch-sized ones and flushes them at the end of the backward pass).
@@ -1503,8 +1497,3 @@ extern "C" int arvae_dense_wgrad_batch(const arvae_dense_wgrad_job_t *jobs, int3
     return dense_wgrad_flush(&b, st);
 }
 
-#ifdef RG_STAMPS
-extern "C" int arvae_debug_rg_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_rg_stamps), sizeof(unsigned long long) * count);
-}
-#endif

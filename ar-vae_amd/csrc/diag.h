@@ -11,7 +11,7 @@
 //   ARVAE_GRU_WIDE, _GRU_BF16_BWD, _GRU_MASK_APART   the MeasureVAE recurrences as through round 4 (tests/test_measure_executor.py)
 //   ARVAE_MIDC_DROP_ARRIVAL               one member of the latent block's first hand-off never arrives (the hand-off tests of
 //                                         tests/test_hip_parity.py, through tests/shared_device_worker.py)
-// DESIGN.md section 5 lists them.  The phase stamps (ARVAE_STAMPS, *_STAMPS: tools/stamp_*.py) are compile-time instruments.
+// DESIGN.md section 5 lists them.  The phase stamps (stamps.h: -DARVAE_STAMPS_<FAMILY>, tools/stamp.py) are compile-time instruments.
 #pragma once
 #include <stdlib.h>
 

@@ -19,14 +19,15 @@
 #pragma once
 #include "common.h"
 #include "conv32_common.h"
+#include "stamps.h"
 
 namespace arvae {
 
-#ifdef D32K_STAMPS
-// diagnostic build only (tools/stamp_d32p.py): phase timeline of the first 32 workgroups, 100 MHz wall clock
-__device__ unsigned long long g_d32k_stamps[64 * 64];
-// down32p_kernel<16, *>: rows 0..31 = the consumers of workgroups 0..31 (thread 0), rows 32..63 = their producers (thread 256)
-#define DSTAMP(role, slot) do { if (LO == 16 && threadIdx.x == 256 * (role) && BID < 32 && (slot) < 64) g_d32k_stamps[(BID + 32 * (role)) * 64 + (slot)] = wall_clock64(); } while (0)
+#ifdef ARVAE_STAMPS_D32K
+// diagnostic build only (stamps.h): phase timeline of the first 32 workgroups of down32p_kernel<16, *>:
+// rows 0..31 = the consumers of workgroups 0..31 (thread 0), rows 32..63 = their producers (thread 256)
+ARVAE_STAMP_TABLE(d32k, 64, 64, 1)
+#define DSTAMP(role, slot) do { if (LO == 16 && threadIdx.x == 256 * (role) && BID < 32) ARVAE_STAMP(g_d32k_stamps, BID + 32 * (role), slot); } while (0)
 #else
 #define DSTAMP(role, slot)
 #endif
@@ -48,7 +49,7 @@ template <int LO> struct DownK {
 // wave issued 12 MFMAs and ~90 vector instructions of loading, splitting and LDS writing between them, and one wave per SIMD hides
 // at most ~5 per MFMA: the step took 1.5x its MFMA issue time (stamps: 2.3 us per tile for 1.54 us of MFMA; 29-33 us per 16x16
 // launch).  Here, as in wgrad32r_kernel, the two jobs live in different waves of the same SIMD (same-box A/B, three boxes:
-// 1.5 / 3.5 / 7.4 us per training step in favour of this form; stamps: tools/stamp_d32p.py, profiles/r3_phase_stamps.txt): waves 0-3 (consumers, wave = kernel row) keep the weights, read their
+// 1.5 / 3.5 / 7.4 us per training step in favour of this form; stamps: tools/stamp.py d32k, profiles/r3_phase_stamps.txt): waves 0-3 (consumers, wave = kernel row) keep the weights, read their
 // operands from LDS and issue MFMAs -- 6 LDS reads per 12 MFMAs and nothing else in the reduction loop; waves 4-7 (producers)
 // fetch tile t+1 .. t+3, scale and split (single-issue instructions: they co-issue beside the partner's MFMAs) and write
 // tile t+1's LDS image while tile t is multiplied.  (Round 3 measured this with six bf16 products per multiply-add: 1.9-2.1 us

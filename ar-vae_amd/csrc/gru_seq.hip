@@ -23,6 +23,7 @@
 #include "splitmath.h"
 #include "gru_common.h"
 #include "gru_mask.h"
+#include "stamps.h"
 
 namespace arvae {
 
@@ -64,8 +65,20 @@ struct GruSeqBatch {
     GruSeq seq[GRU_SEQ_MAX];
 };
 
-#ifdef ARVAE_GRU_STAMPS
-__device__ unsigned long long g_gru_stamps[8];
+#ifdef ARVAE_STAMPS_GRU
+// diagnostic build only (stamps.h): cycles per phase of a step + the step count, of the LAST forward or backward launch: thread 0 /
+ARVAE_STAMP_TABLE(gru, 1, 5, 1)                                // wave GRU_STAMP_WAVE of the first workgroup
+#define GSTAMP_BEGIN() PhaseSums<4> ph
+#define GSTAMP(k) ph.mark(k)
+#define GSTAMP_DEPEND(v) stamp_depend(v)
+#define GSTAMP_WAIT(what) stamp_wait_##what()
+#define GSTAMP_END(wave, steps) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 64 * (wave)) ph.flush(g_gru_stamps, steps); } while (0)
+#else
+#define GSTAMP_BEGIN()
+#define GSTAMP(k)
+#define GSTAMP_DEPEND(v)
+#define GSTAMP_WAIT(what)
+#define GSTAMP_END(wave, steps)
 #endif
 // ------------------------------------------------------------------------------------------------------------------
 // The forward recurrence on the fp16 MFMA with SCALED TWO-TERM operands (the arithmetic of splitmath.h): s x = h + l with
@@ -190,12 +203,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
     f32x4 keep_sv[E];                        // results of the previous step, stored after the barrier
     float keep_h[E];
     int keep_t = -1;
-#ifdef ARVAE_GRU_STAMPS
-    unsigned long long ph[4] = {0, 0, 0, 0}, tc = __builtin_readcyclecounter();
-#define GSTAMP(k) { const unsigned long long now = __builtin_readcyclecounter(); ph[k] += now - tc; tc = now; }
-#else
-#define GSTAMP(k)
-#endif
+    GSTAMP_BEGIN();
 
     for (int step = 0; step < T; ++step) {
         const int t = s.reverse ? T - 1 - step : step;
@@ -210,7 +218,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         const unsigned short *hb = &hbuf[cur][gru_arow<E>(col) * HP + 8 * quad];
         // Row i's share of the step's memory traffic (next step's three input projections in, the previous step's h and saved
         // gates out) is issued BEHIND the MFMAs of k-step i, with a scheduling barrier pinning it there: as one block in front
-        // of the MFMAs it was 1200 of the step's 6000 cycles (tools/stamp_gru.py), all of it issue time of an in-order wave
+        // of the MFMAs it was 1200 of the step's 6000 cycles (tools/stamp.py gru), all of it issue time of an in-order wave
         // while the matrix pipe sat idle.
         // next step's projections (the last step reads its own again); the previous step's results (none in step 0: the empty range)
         const int tn = step + 1 < T ? (reverse ? t - 1 : t + 1) : t;
@@ -238,9 +246,8 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         }
 #pragma unroll
         for (int i = KS; i < E; ++i) row_traffic(i);
-#ifdef ARVAE_GRU_STAMPS
-        { float dep = acc[0][0] + acc[1][0] + acc[2][3]; asm volatile("" :: "v"(dep)); __builtin_amdgcn_s_waitcnt(0); }
-#endif
+        GSTAMP_DEPEND(acc[0][0] + acc[1][0] + acc[2][3]);
+        GSTAMP_WAIT(all);
         GSTAMP(1);
         float av[3][E];                      // the gates' products of this lane's elements
 #pragma unroll
@@ -264,19 +271,12 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
             store_split2<false>(&hbuf[cur ^ 1][quad * HP + unit], PLANE, h[0], h_s);
         }
         keep_t = t;
-#ifdef ARVAE_GRU_STAMPS
-        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the LDS writes are done
-#endif
+        GSTAMP_WAIT(lds);                        // the LDS writes are done
         GSTAMP(2);
         lds_barrier();
         GSTAMP(3);
     }
-#ifdef ARVAE_GRU_STAMPS
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        for (int k = 0; k < 4; ++k) g_gru_stamps[k] = ph[k];
-        g_gru_stamps[4] = T;
-    }
-#endif
+    GSTAMP_END(0, T);
 #pragma unroll
     for (int i = 0; i < E; ++i)
         if (live[i]) {
@@ -356,17 +356,14 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
         }
     };
     fetch(0);
-#ifdef ARVAE_GRU_STAMPS
-    unsigned long long ph[4] = {0, 0, 0, 0}, tc = __builtin_readcyclecounter();
-#endif
+    GSTAMP_BEGIN();
 
     for (int step = 0; step < T; ++step) {
         const int t = reverse ? step : T - 1 - step;
         const int cur = step & 1;
         float gz[E], o_gi[E][3], o_hn[E], o_hp[E];
-#ifdef ARVAE_GRU_STAMPS
-        { float dep = nx[0][0] + nx[E - 1][5] + nx[E / 2][3]; asm volatile("" :: "v"(dep)); __builtin_amdgcn_s_waitcnt(0); }
-#endif
+        GSTAMP_DEPEND(nx[0][0] + nx[E - 1][5] + nx[E / 2][3]);
+        GSTAMP_WAIT(all);
         GSTAMP(0);
 #pragma unroll
         for (int i = 0; i < E; ++i) {
@@ -393,9 +390,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
             store_split3(d + H, PLANE, o_gi[0][1]);
             store_split3(d + 2 * H, PLANE, o_hn[0]);
         }
-#ifdef ARVAE_GRU_STAMPS
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-#endif
+        GSTAMP_WAIT(lds);
         GSTAMP(1);
         if (step + 1 < T) fetch(step + 1);
         lds_barrier();
@@ -434,20 +429,10 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
 #pragma unroll
             for (int i = 0; i < E; ++i) carry[i] = gz[i] + cs[i];
         }
-#ifdef ARVAE_GRU_STAMPS
-        { float dep = carry[0] + carry[E - 1]; asm volatile("" :: "v"(dep)); }
-#endif
+        GSTAMP_DEPEND(carry[0] + carry[E - 1]);
         GSTAMP(3);
     }
-#ifdef ARVAE_GRU_STAMPS
-#ifndef GRU_STAMP_WAVE
-#define GRU_STAMP_WAVE 0
-#endif
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 64 * GRU_STAMP_WAVE) {
-        for (int q = 0; q < 4; ++q) g_gru_stamps[q] = ph[q];
-        g_gru_stamps[4] = T;
-    }
-#endif
+    GSTAMP_END(GRU_STAMP_WAVE, T);
     if (s.dh0 != nullptr)
 #pragma unroll
         for (int i = 0; i < E; ++i)
@@ -745,8 +730,3 @@ int arvae::gru_seq_bwd_masked(const arvae_gru_seq_t *seqs, const GruSeqMask *mas
     return check_launch("gru_seq_bwd_kernel");
 }
 
-#ifdef ARVAE_GRU_STAMPS
-extern "C" int arvae_debug_gru_stamps(unsigned long long *out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_gru_stamps), sizeof(unsigned long long) * 8);
-}
-#endif

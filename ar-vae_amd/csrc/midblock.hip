@@ -22,6 +22,7 @@
 #include "amax.h"
 #include "conv32.h"
 #include "midblock.h"
+#include "stamps.h"
 
 namespace arvae {
 
@@ -255,9 +256,9 @@ __device__ __forceinline__ void mid_amax(const float *rows, int ld, int n, float
     }
 }
 
-#ifdef MID_STAMPS
-__device__ unsigned long long g_mid_stamps[128 * 16];
-#define MID_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 128) g_mid_stamps[blockIdx.x * 16 + (slot)] = wall_clock64(); } while (0)
+#ifdef ARVAE_STAMPS_MID
+ARVAE_STAMP_TABLE(mid, 128, 16, 1)                             // diagnostic build only (stamps.h): one row per workgroup (thread 0)
+#define MID_STAMP(slot) do { if (threadIdx.x == 0) ARVAE_STAMP(g_mid_stamps, blockIdx.x, slot); } while (0)
 #else
 #define MID_STAMP(slot)
 #endif
@@ -483,7 +484,7 @@ bool mid_fusable(const arvae_image_vae_t *m, int *ne_out, int *nd_out) {
     // ON by default since the end of round 2 (ARVAE_MIDBLOCK=0 selects the twelve per-layer launches).  At B = 512 on MI355X:
     // forward 32 us, backward 39 us, prep 8 us against ~87 us for the launches it replaces -- the kernel time is a wash, but
     // the step has nine launches fewer and is 2.2 % faster in a same-box A/B (it measured equal while the step still had 44
-    // launches).  Phase stamps (tools/stamp_mid.py): every layer of the chain costs >= 3.3 us however small (the 10 -> 256
+    // launches).  Phase stamps (tools/stamp.py mid): every layer of the chain costs >= 3.3 us however small (the 10 -> 256
     // layer included): a dependent round trip to the freshly written weights, two barriers and the saved-activation store per
     // layer, on 128 of the 256 CUs.
     static const bool off = diag_env("ARVAE_MIDBLOCK") != nullptr && diag_env("ARVAE_MIDBLOCK")[0] == '0';
@@ -1139,8 +1140,3 @@ extern "C" int arvae_wide_dense(const arvae_link_t *l, int32_t mode, const float
     return wide_partial_sum(partial, q.slice_floats, slices, out, s);
 }
 
-#ifdef MID_STAMPS
-extern "C" int arvae_debug_mid_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_mid_stamps), sizeof(unsigned long long) * count);
-}
-#endif

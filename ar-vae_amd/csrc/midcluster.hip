@@ -27,6 +27,7 @@
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
 #include "midcluster.h"
+#include "stamps.h"
 
 namespace arvae {
 namespace {
@@ -39,9 +40,9 @@ constexpr int RED_FLOATS = 4 * MC_R * 20; // partial tiles: 4 k-quarters x 32 ro
 constexpr int LDS_FLOATS = MC_R * PA + MC_R * PB + RED_FLOATS + MC_R * PZ + MC_R * PO;
 constexpr int AUX_SC1 = 16;               // cache-policy bit of the raw buffer intrinsics: sc1 (agent scope: bypass L1 / write through)
 
-#ifdef MIDC_STAMPS
-__device__ unsigned long long g_midc_stamps[2 * 256 * 16];     // [pass][workgroup][slot]: wall clock (100 MHz) at phase boundaries
-#define MC_STAMP(pass, slot) do { if (threadIdx.x == 0 && blockIdx.x < 256) g_midc_stamps[((pass) * 256 + blockIdx.x) * 16 + (slot)] = wall_clock64(); } while (0)
+#ifdef ARVAE_STAMPS_MIDC
+ARVAE_STAMP_TABLE_ONLY(midc, 512, 16, 1)                       // diagnostic build only (stamps.h): row = 256 * pass + workgroup (thread 0)
+#define MC_STAMP(pass, slot) do { if (threadIdx.x == 0 && blockIdx.x < 256) ARVAE_STAMP(g_midc_stamps, (pass) * 256 + blockIdx.x, slot); } while (0)
 #else
 #define MC_STAMP(pass, slot)
 #endif
@@ -1004,6 +1005,10 @@ void allow_lds() {
 
 }  // namespace
 
+#ifdef ARVAE_STAMPS_MIDC
+ARVAE_STAMP_READER(midc)
+#endif
+
 int64_t midc_counter_words(int) { return MC_COUNTER_WORDS; }
 unsigned long long midc_wait_ticks() { return MC_WAIT_TICKS; }
 
@@ -1045,8 +1050,3 @@ extern "C" int arvae_debug_midc_failures(unsigned *out /* [1 + 64 * 8] */) {
 }
 #endif
 
-#ifdef MIDC_STAMPS
-extern "C" int arvae_debug_midc_stamps(unsigned long long *out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_midc_stamps), sizeof(unsigned long long) * count);
-}
-#endif

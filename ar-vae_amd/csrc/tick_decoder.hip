@@ -19,11 +19,22 @@
 #include "common.h"
 #include "splitmath.h"
 #include "gru_common.h"
+#include "stamps.h"
 
 namespace arvae {
 
-#ifdef ARVAE_GRU_STAMPS
-__device__ unsigned long long g_tick_stamps[9];
+#ifdef ARVAE_STAMPS_TICK
+// diagnostic build only (stamps.h): cycles per phase of a tick + the tick count, wave GRU_STAMP_WAVE of workgroup 0; a mark waits for
+ARVAE_STAMP_TABLE(tick, 1, 9, 1)                               // the wave's LDS traffic first
+#define TSTAMP_BEGIN() PhaseSums<8> tph
+#define TSTAMP(k) do { stamp_wait_lds(); tph.mark(k); } while (0)
+#define TSTAMP_DEPEND(v) stamp_depend(v)
+#define TSTAMP_END(ticks) do { if (blockIdx.x == 0 && threadIdx.x == 64 * GRU_STAMP_WAVE) tph.flush(g_tick_stamps, ticks); } while (0)
+#else
+#define TSTAMP_BEGIN()
+#define TSTAMP(k)
+#define TSTAMP_DEPEND(v)
+#define TSTAMP_END(ticks)
 #endif
 
 struct TickFreeRun {
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     auto elems = [&](const f32x4 &acc, float (&out)[E]) __attribute__((always_inline)) { gru_elems<E>(acc, out); };
     // layer 0's recurrent product W_hh0 h0 of a tick does not wait for the tick's token: it is multiplied at the END of the previous
     // tick, under the logits and the argmax (three waves' latency chain of ~3500 cycles, during which the workgroup's weight
-    // stream -- what bounds the layers: 590 KB per tick at the CU's 64 bytes per clock -- stood still; tools/stamp_tick.py).
+    // stream -- what bounds the layers: 590 KB per tick at the CU's 64 bytes per clock -- stood still; tools/stamp.py tick).
     // A beat's first tick starts from the beat's own state and multiplies at its top, as every tick did.
     f32x4 acc0[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     // the 3 KS weight groups of matrix 0 against the state image `ab`; piece(g) runs behind group g
@@ -244,13 +255,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
         }
     };
     auto no_piece = [](int) __attribute__((always_inline)) {};
-#ifdef ARVAE_GRU_STAMPS
-    // diagnostic build (tools/stamp_tick.py): cycles per phase of a tick, wave GRU_STAMP_WAVE of workgroup 0
-    unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ttc = __builtin_readcyclecounter();
-#define TSTAMP(k) { __builtin_amdgcn_s_waitcnt(0xc07f); const unsigned long long now = __builtin_readcyclecounter(); tph[k] += now - ttc; ttc = now; }
-#else
-#define TSTAMP(k)
-#endif
+    TSTAMP_BEGIN();
     for (int t = 0; t < ticks; ++t) {
         const int cur = t & 1;
         const int beat = t / p.tpb;
@@ -304,9 +309,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
         // ---- layer 0: matrix 0 (multiplied at the end of the previous tick unless a beat starts)
         {
             if (beat_start) layer0(&hA0[cur][aoff], no_piece);
-#ifdef ARVAE_GRU_STAMPS
-            { float dep = acc0[0][0] + acc0[1][1] + acc0[2][3]; asm volatile("" :: "v"(dep)); }
-#endif
+            TSTAMP_DEPEND(acc0[0][0] + acc0[1][1] + acc0[2][3]);
             TSTAMP(1);                                         // layer 0 at the top (a beat's first tick only)
             float ar[E], az[E], an[E];
             elems(acc0[0], ar); elems(acc0[1], az); elems(acc0[2], an);
@@ -342,9 +345,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                     }
                 }
             }
-#ifdef ARVAE_GRU_STAMPS
-            { float dep = a1[0][0] + a1[1][1] + a1[2][3] + a1[3][2]; asm volatile("" :: "v"(dep)); }
-#endif
+            TSTAMP_DEPEND(a1[0][0] + a1[1][1] + a1[2][3] + a1[3][2]);
             TSTAMP(4);                                         // layer 1: operand reads + MFMAs behind the weight stream
             float ar[E], az[E], ai[E], ah[E];
             elems(a1[0], ar); elems(a1[1], az); elems(a1[2], ai); elems(a1[3], ah);
@@ -427,9 +428,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
             } else if (pre) {
                 layer0(ab_next, no_piece);
             }
-#ifdef ARVAE_GRU_STAMPS
-            { float dep = acc0[0][0] + acc0[1][1] + acc0[2][3]; asm volatile("" :: "v"(dep)); }
-#endif
+            TSTAMP_DEPEND(acc0[0][0] + acc0[1][1] + acc0[2][3]);
         }
         TSTAMP(6);                                             // barrier + logits / argmax (first waves) + the next tick's layer 0
         lds_barrier();
@@ -493,15 +492,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
         }
         TSTAMP(7);                                             // barrier + the tiles' candidates -> token
     }
-#ifdef ARVAE_GRU_STAMPS
-#ifndef GRU_STAMP_WAVE
-#define GRU_STAMP_WAVE 0
-#endif
-    if (blockIdx.x == 0 && threadIdx.x == 64 * GRU_STAMP_WAVE) {
-        for (int q = 0; q < 8; ++q) g_tick_stamps[q] = tph[q];
-        g_tick_stamps[8] = ticks;
-    }
-#endif
+    TSTAMP_END(ticks);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1037,8 +1028,3 @@ extern "C" int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const
     return check_launch("tick_free_run_layers_kernel");
 }
 
-#ifdef ARVAE_GRU_STAMPS
-extern "C" int arvae_debug_tick_stamps(unsigned long long *out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(arvae::g_tick_stamps), sizeof(unsigned long long) * 9);
-}
-#endif

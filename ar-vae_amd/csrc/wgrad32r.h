@@ -21,6 +21,7 @@
 #include "common.h"
 #include "conv32_common.h"
 #include "reduce.h"
+#include "stamps.h"
 
 namespace arvae {
 
@@ -39,16 +40,10 @@ template <int LO> struct RowStream {
     static constexpr int STEPS_PER_IMG = LO * LO / 32;
 };
 
-#ifdef WGR_STAMPS
-// diagnostic build only (tools/stamp_wgr.py): [workgroup][role 0 consumer / 1 producer][slot][cycle counter, 100 MHz wall clock]
-__device__ unsigned long long g_wgr_stamps[256 * 2 * 64 * 2];
-#define WGR_STAMP(role, slot)                                                                             \
-    do {                                                                                                  \
-        if ((threadIdx.x & 255) == 0 && BID < 256 && (slot) < 64) {                                \
-            g_wgr_stamps[((BID * 2 + (role)) * 64 + (slot)) * 2] = __builtin_readcyclecounter();   \
-            g_wgr_stamps[((BID * 2 + (role)) * 64 + (slot)) * 2 + 1] = wall_clock64();             \
-        }                                                                                                 \
-    } while (0)
+#ifdef ARVAE_STAMPS_WGR
+// diagnostic build only (stamps.h): per-step timeline, row = 2 * workgroup + role (0 consumer / 1 producer, the first thread of each)
+ARVAE_STAMP_TABLE(wgr, 512, 64, 2)
+#define WGR_STAMP(role, slot) do { if ((threadIdx.x & 255) == 0 && BID < 256) ARVAE_STAMP(g_wgr_stamps, BID * 2 + (role), slot); } while (0)
 #else
 #define WGR_STAMP(role, slot)
 #endif
