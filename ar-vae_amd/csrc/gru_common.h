@@ -15,6 +15,13 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x));
 }
 
+// GRU_ROUNDING: every batch row is an independent recurrence, so a row's results must not depend on the rows-per-workgroup
+// instantiation that happens to run it.  The element arithmetic of gru_seq.hip therefore leaves no rounding to the compiler:
+// `#pragma clang fp contract(off)` heads each element loop and the fused operations are written as __builtin_fmaf.  Left to the
+// compiler, gru_seq_fwd_h2_kernel<H, 4> computed the new state as round((1 - z) n) + round(z h) (one packed multiply, one add)
+// and <H, 8> as fma(z, h, round((1 - z) n)): the same rows one ulp apart between a 256-row and a 261-row batch
+// (tests/test_gru_recurrences_float64.py holds the widths to each other bit for bit).
+//
 // Addressing of the recurrences' per-step memory operations: raw buffer operations, byte offset = a SCALAR part (the step's
 // t * R * row pitch: one s_mul per array and step) + a per-lane part (row * pitch + unit: one v_mad_u32_u24 per operation).  With
 // 64-bit pointer arithmetic each of a step's ~40 loads and stores cost 6-10 vector instructions -- half of what a wave executes

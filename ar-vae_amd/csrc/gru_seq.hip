@@ -254,11 +254,12 @@ __global__ __launch_bounds__(H * 4) void gru_seq_fwd_h2_kernel(GruSeqBatch batch
         for (int g = 0; g < 3; ++g) gru_elems<E>(acc[g], av[g]);
 #pragma unroll
         for (int i = 0; i < E; ++i) {
-            const float r = fast_sigmoid(gi[i][0] + av[0][i] * unscale + bh_r);
-            const float z = fast_sigmoid(gi[i][1] + av[1][i] * unscale + bh_z);
-            const float ghn = av[2][i] * unscale + bh_n;
-            const float n = fast_tanh(gi[i][2] + r * ghn);
-            const float hn = (1.f - z) * n + z * h[i];
+#pragma clang fp contract(off)               // GRU_ROUNDING (gru_common.h): the fused operations are the ones written as such
+            const float r = fast_sigmoid(__builtin_fmaf(av[0][i], unscale, gi[i][0]) + bh_r);
+            const float z = fast_sigmoid(__builtin_fmaf(av[1][i], unscale, gi[i][1]) + bh_z);
+            const float ghn = __builtin_fmaf(av[2][i], unscale, bh_n);
+            const float n = fast_tanh(__builtin_fmaf(r, ghn, gi[i][2]));
+            const float hn = __builtin_fmaf(z, h[i], (1.f - z) * n);
             h[i] = hn;
             keep_h[i] = hn;
             keep_hm[i] = mk_cur[i] != 0 ? keep_scale * hn : 0.f;
@@ -367,9 +368,10 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_x3_kernel(GruSeqBatch batch
         GSTAMP(0);
 #pragma unroll
         for (int i = 0; i < E; ++i) {
+#pragma clang fp contract(off)               // GRU_ROUNDING (gru_common.h)
             const float g = live[i] ? nx[i][0] + carry[i] : 0.f;
             const float r = nx[i][1], z = nx[i][2], n = nx[i][3], ghn = nx[i][4], hp = nx[i][5];
-            const float dpn = g * (1.f - z) * (1.f - n * n);
+            const float dpn = g * (1.f - z) * __builtin_fmaf(-n, n, 1.f);
             const float dpz = g * (hp - n) * z * (1.f - z);
             const float dpr = dpn * ghn * r * (1.f - r);
             const float dhn = dpn * r;
@@ -538,10 +540,11 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
         float gz[E], o_gi[E][3], o_hn[E], o_hp[E];
 #pragma unroll
         for (int i = 0; i < E; ++i) {
+#pragma clang fp contract(off)               // GRU_ROUNDING (gru_common.h)
             const float dh = masked ? (mk_nx[i] != 0 ? keep_scale * nx[i][0] : 0.f) : nx[i][0];
             const float g = live[i] ? dh + carry[i] : 0.f;
             const float r = nx[i][1], z = nx[i][2], n = nx[i][3], ghn = nx[i][4], hp = nx[i][5];
-            const float dpn = g * (1.f - z) * (1.f - n * n);
+            const float dpn = g * (1.f - z) * __builtin_fmaf(-n, n, 1.f);
             const float dpz = g * (hp - n) * z * (1.f - z);
             const float dpr = dpn * ghn * r * (1.f - r);
             const float dhn = dpn * r;
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(H * 4) void gru_seq_bwd_h2_kernel(GruSeqBatch batch
             float cs[E];
             gru_elems<E>(sum, cs);
 #pragma unroll
-            for (int i = 0; i < E; ++i) carry[i] = gz[i] + cs[i] * unscale[i];
+            for (int i = 0; i < E; ++i) carry[i] = __builtin_fmaf(cs[i], unscale[i], gz[i]);
         }
     }
     if (s.dh0 != nullptr)

@@ -967,12 +967,21 @@ def test_measure_sequence_path_matches_stepwise(dev, monkeypatch):
 
 
 @pytest.mark.parametrize('b,dropout,hid,big', [(256, 0.5, 128, False), (21, 0.0, 128, False), (37, 0.5, 64, False), (1501, 0.5, 128, False),
-                                               (2101, 0.0, 64, False), (64, 0.5, 128, True), (45, 0.0, 64, True)])
+                                               (2101, 0.0, 64, False), (64, 0.5, 128, True), (45, 0.0, 64, True),
+                                               (2053, 0.5, 128, False), (1029, 0.0, 64, False)])
 def test_tick_free_run_tokens_match_stepwise(dev, monkeypatch, b, dropout, hid, big):
     """the one-launch free-running tick decoder feeds itself the same notes as the launch-per-tick pass.
     big: initial tick states of ~1e4 and recurrent tick weights of ~350 -- beyond what the FIXED fp16 operand scales of round 4 could
-    hold (4094 / 255: inf, then nan); the kernel takes its scales from the data since round 5."""
+    hold (4094 / 255: inf, then nan); the kernel takes its scales from the data since round 5.
+    (2053 rows at hidden 128 and 1029 at hidden 64 are the kernel's 16 and 8 rows per workgroup, five rows in the last one: with
+    1501 / 128, 2101 / 64 and the small batches, all three widths at both hidden sizes; hidden 32: test_measure_layers_gpu.py)"""
     from arvae_amd.measure_vae import MeasureVAE
+    from gru_cases import rows_per_wg
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if b in (2053, 1029):                                     # the cases named for a width run it, on this device
+        want = 16 if b == 2053 else 8
+        assert rows_per_wg(b, 1, cus) == want and b % want == 5, \
+            f'{b} rows on {cus} CUs run {rows_per_wg(b, 1, cus)} rows per workgroup: this case is written for {want} (256 CUs)'
     torch.manual_seed(23)
     ds = _FolkDataset()
     model = MeasureVAE(ds, 10, 2, 2, hid, dropout, 32, 2, hid, dropout, False, 'folk').cuda().train()

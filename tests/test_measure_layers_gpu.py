@@ -17,6 +17,7 @@ from oracle import attributes as o_attr
 from oracle import philox
 
 import layer_stack_ref as ref
+from gru_cases import rows_per_wg
 from test_measure_layers import CASE_IDS, LAYER_CASES, _FolkDataset, golden_case, golden_state
 from test_sampling import pick64
 
@@ -185,11 +186,16 @@ def test_tick_layers_tokens_match_stepwise(dev, monkeypatch, layers, hid, vocab,
             assert torch.equal(again['0'][1], out['0'][1])
 
 
-@pytest.mark.parametrize('b', [5, 20])
+@pytest.mark.parametrize('b', [5, 20, 1029, 2053])
 def test_two_layer_tokens_match_stepwise_at_hidden_32(dev, monkeypatch, b):
     """the two-layer one-launch decoder (tick_free_run_h2_kernel behind the shared weight prep) at its smallest shape, which the 35-note
-    vocabulary does not reach: hidden 32 has one k-step and nine weight groups per tick, so the register ring is 3 deep instead of 6"""
+    vocabulary does not reach: hidden 32 has one k-step and nine weight groups per tick, so the register ring is 3 deep instead of 6.
+    1029 and 2053 rows: 8 and 16 rows per workgroup (gru_rows_per_wg for one sequence), five rows in the last workgroup"""
     assert ops.tick_free_run_supported(32, 32)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    want = {5: 4, 20: 4, 1029: 8, 2053: 16}[b]
+    assert rows_per_wg(b, 1, cus) == want, \
+        f'{b} rows on {cus} CUs run {rows_per_wg(b, 1, cus)} rows per workgroup: this case is written for {want} (256 CUs)'
     for dropout, tau in [(dropout, tau) for dropout in (0.0, 0.5) for tau in (None, 1.0, 0.7)]:
         model = spread_model(2, 32, 32, dropout, dev)
         out, u = both_paths(model, 2, b, 32, 32, dropout, tau, dev, monkeypatch)
