@@ -10,7 +10,7 @@ import threading
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libarvae_hip.so')
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_i32, c_i64, c_f32, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
@@ -95,6 +95,20 @@ class DenseWgradJob(ctypes.Structure):
     """arvae_dense_wgrad_job_t"""
     _fields_ = [('g', OperandDesc), ('x', c_vp), ('dw', c_vp), ('dbias', c_vp), ('rows', c_i32), ('n_in', c_i32),
                 ('n_out', c_i32), ('reserved', c_i32)]
+
+
+class ResnetConvDesc(ctypes.Structure):
+    """arvae_resnet18_conv_t"""
+    _fields_ = [(n, c_i32) for n in ('hin', 'win', 'cin', 'hout', 'wout', 'cout', 'ksize', 'stride', 'pad', 'reserved')]
+
+
+RESNET_CONVS = 19
+
+
+class ResnetWeights(ctypes.Structure):
+    """arvae_resnet18_weights_t"""
+    _fields_ = ([('stem_w', c_vp), ('stem_bn', c_vp * 4)] +
+                [(n, c_vp * RESNET_CONVS) for n in ('conv_w', 'bn_w', 'bn_b', 'bn_mean', 'bn_var')] + [('fc_w', c_vp), ('fc_b', c_vp)])
 
 
 _P = ctypes.POINTER
@@ -194,6 +208,19 @@ SIGNATURES = {
     'arvae_comm_group_end': (c_i32, []),
     'arvae_ksg_ws_bytes': (c_i64, [c_i64, c_i32]),
     'arvae_ksg_mi': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_resnet18_live_taps': (c_i32, [_P(ResnetConvDesc), _P(c_i32)]),
+    'arvae_resnet18_conv_prep_floats': (c_i64, [_P(ResnetConvDesc)]),
+    'arvae_resnet18_conv_prepare': (c_i32, [_P(ResnetConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_resnet18_conv': (c_i32, [_P(ResnetConvDesc), c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    'arvae_resnet18_stem_prep_floats': (c_i64, []),
+    'arvae_resnet18_stem_prepare': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_resnet18_stem': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    'arvae_resnet18_maxpool': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'arvae_resnet18_head': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_resnet18_prep_floats': (c_i64, []),
+    'arvae_resnet18_prepare': (c_i32, [_P(ResnetWeights), c_vp, c_vp]),
+    'arvae_resnet18_ws_floats': (c_i64, [c_i32]),
+    'arvae_resnet18_forward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lock = threading.Lock()

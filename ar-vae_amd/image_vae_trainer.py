@@ -238,9 +238,78 @@ class ImageVAETrainer(Trainer):
         self.metrics = {'representations': rep_fp}
         self.metrics.update(eval_metrics_or_warn(codes, attrs, names, random_state=random_state))
         self.metrics.update(self.test_model(batch_size=batch_size))
+        if self.dataset_type == 'mnist' and 'interpretability' in self.metrics:
+            from .mnist_resnet import MnistResNet
+            if os.path.exists(MnistResNet().filepath):     # (the reference fails without the classifier; here the key is left out)
+                self.metrics.update(self.get_resnet_accuracy(batch_size=batch_size))
         with open(results_fp, 'w') as f:
             json.dump(self.metrics, f, indent=2)
         return self.metrics
+
+    def get_resnet_accuracy(self, batch_size=128, resnet_model=None, record=None):
+        """{'digit_pred_acc': {'inputs', 'recons', 'interp'}} of the reference (image_vae_trainer.py:319-368): the share of the
+        evaluation digits that the ResNet-18 classifier (arvae_amd.mnist_resnet, HIP) recognises as given, after reconstruction,
+        and after each latent dimension of self.metrics['interpretability'] has been swept over linspace(-4, 4, 10) in the
+        decoder (z.repeat(10, 1) with that dimension overwritten; labels digit_labels.repeat(10)).  Each figure is the mean over
+        the batches of per-batch accuracies; 'interp' is also averaged over the keys.
+        The reference's quirk is kept, so that the number compares with its own: the keys include the metric's 'mean' entry
+        (-1, m), i.e. the LAST latent dimension is swept as a seventh "attribute" and the divisor is 7, not 6.
+        None unless the dataset is Morpho-MNIST.  resnet_model None: MnistResNet() loaded from its checkpoint.  record: a list
+        that receives (kind, images, labels, predictions) for every classified batch, kind in 'inputs' | 'recons' | 'interp:<key>'.
+        Accuracies accumulate on the device: one host sync at the end."""
+        if self.dataset_type != 'mnist':
+            return None
+        dev = next(self.model.parameters()).device
+        if resnet_model is None:
+            from .mnist_resnet import MnistResNet
+            resnet_model = MnistResNet()
+            if not os.path.exists(resnet_model.filepath):
+                raise FileNotFoundError(
+                    f'{resnet_model.filepath}: the digit classifier\'s checkpoint is missing; the reference publishes it as '
+                    'MnistRESNET.pt (its README, "Downloading Models"): put it there or set ARVAE_MODEL_DIR')
+            resnet_model.load(cpu=True)
+            resnet_model.to(dev)
+        if 'interpretability' not in self.metrics:
+            self.compute_eval_metrics(batch_size=batch_size)
+        if 'interpretability' not in self.metrics:
+            raise RuntimeError('digit_pred_acc sweeps the dimensions of the interpretability metric, which this evaluation split '
+                               'was too small to compute')
+        interp_dict = self.metrics['interpretability']
+        _, _, loader = self.dataset.data_loaders(batch_size=batch_size)
+        num_interps = 10
+        sums = torch.zeros(3, device=dev)
+        count = 0
+        self.model.eval()
+
+        def accuracy(kind, images, labels):
+            pred = self.compute_mnist_digit_identity(resnet_model, images)
+            if record is not None:
+                record.append((kind, images, labels, pred))
+            return self.mean_accuracy_pred(pred, labels)
+
+        with torch.no_grad():
+            for batch in loader:
+                inputs, digit_labels = batch[0], batch[1]
+                inputs = inputs.to(dev, torch.float32).contiguous()
+                digit_labels = digit_labels.to(dev, torch.int64)
+                out = self.model(inputs)
+                recons, z = torch.sigmoid(out[0]), out[3]
+                sums[0] += accuracy('inputs', inputs, digit_labels)
+                sums[1] += accuracy('recons', recons.view(inputs.shape), digit_labels)
+                b = z.size(0)
+                z_rep = z.repeat(num_interps, 1)
+                sweep = torch.linspace(-4.0, 4.0, num_interps, device=dev).repeat_interleave(b)
+                labels_rep = digit_labels.repeat(num_interps)
+                per_key = torch.zeros((), device=dev)
+                for key, entry in interp_dict.items():
+                    z_copy = z_rep.clone()
+                    z_copy[:, int(entry[0])] = sweep
+                    outputs = torch.sigmoid(self.model.decode(z_copy.contiguous())).view(num_interps * b, 1, 28, 28)
+                    per_key += accuracy(f'interp:{key}', outputs, labels_rep)
+                sums[2] += per_key / len(interp_dict)
+                count += 1
+        inputs_acc, recons_acc, interp_acc = (sums / max(count, 1)).tolist()
+        return {'digit_pred_acc': {'inputs': inputs_acc, 'recons': recons_acc, 'interp': interp_acc}}
 
     def loss_and_acc_test(self, data_loader):
         """mean RECONSTRUCTION loss (no KL / regulariser terms) and mean pixel accuracy over the loader's batches
@@ -272,6 +341,21 @@ class ImageVAETrainer(Trainer):
         if dist not in ('bernoulli', 'gaussian'):
             raise AttributeError('invalid dist')
         return ops.image_recon(x_recons, x, dist)[0]
+
+    @staticmethod
+    def mean_accuracy_pred(pred_labels, gt_labels):
+        """share of equal labels, a device scalar (image_vae_trainer.py:657-660)"""
+        return (pred_labels.long() == gt_labels.long()).float().mean()
+
+    @staticmethod
+    def compute_mnist_digit_identity(resnet_model, outputs):
+        """argmax labels (int64, on the device) of the classifier in evaluation mode (image_vae_trainer.py:662-666); MnistResNet
+        returns the head kernel's argmax, any other module's probabilities go through torch.max"""
+        resnet_model.eval()
+        with torch.no_grad():
+            if hasattr(resnet_model, 'predict'):
+                return resnet_model.predict(outputs)
+            return torch.max(resnet_model(outputs), 1)[1]
 
     @staticmethod
     def mean_accuracy(weights, targets):

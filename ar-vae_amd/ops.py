@@ -1281,3 +1281,159 @@ def measure_attributes(score, tables, rhythm_weights, rhythm_norm):
                                             midi.numel(), _ptr(rhythm_weights), float(rhythm_norm), _ptr(out), _stream()),
                'measure_attributes')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the Morpho-MNIST digit classifier (csrc/resnet18.hip): inference only, no autograd
+# ------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class ResnetConv:
+    """Geometry of one convolution of the classifier (arvae_resnet18_conv_t): square maps, 3x3 pad 1 or 1x1 pad 0."""
+    hin: int
+    cin: int
+    cout: int
+    ksize: int = 3
+    stride: int = 1
+
+    @property
+    def pad(self):
+        return 1 if self.ksize == 3 else 0
+
+    @property
+    def hout(self):
+        return (self.hin + 2 * self.pad - self.ksize) // self.stride + 1
+
+    def desc(self):
+        return _lib.ResnetConvDesc(self.hin, self.hin, self.cin, self.hout, self.hout, self.cout, self.ksize, self.stride, self.pad, 0)
+
+    def label(self):
+        return f'resnet18_conv<{self.hin}->{self.hout},{self.cin}->{self.cout},k{self.ksize}s{self.stride}>'
+
+
+def resnet18_live_taps(geom: ResnetConv):
+    """indices ky * ksize + kx of the taps that read a pixel inside the input for some output pixel (host only)"""
+    taps = (ctypes.c_int32 * 9)()
+    d = geom.desc()
+    n = _lib.load().arvae_resnet18_live_taps(ctypes.byref(d), taps)
+    if n < 0:
+        _lib.check(n, 'resnet18_live_taps')
+    return [int(taps[i]) for i in range(n)]
+
+
+def _bn_ptrs(bn):
+    if bn is None:
+        return (None,) * 4
+    _dev(*bn)
+    return tuple(_ptr(t) for t in bn)
+
+
+def resnet18_conv_prepare(geom: ResnetConv, weight, bn=None):
+    """the convolution's operand planes and folded bias; bn = (weight, bias, running_mean, running_var) or None"""
+    _dev(weight)
+    if tuple(weight.shape) != (geom.cout, geom.cin, geom.ksize, geom.ksize):
+        raise ValueError(f'weight {tuple(weight.shape)} does not match {geom}')
+    lib = _lib.load()
+    d = geom.desc()
+    n = lib.arvae_resnet18_conv_prep_floats(ctypes.byref(d))
+    if n < 0:
+        _lib.check(n, 'resnet18_conv_prep_floats')
+    prep = torch.empty(n, device=weight.device, dtype=torch.float32)
+    _lib.check(lib.arvae_resnet18_conv_prepare(ctypes.byref(d), _ptr(weight), *_bn_ptrs(bn), _ptr(prep), _stream()),
+               'resnet18_conv_prepare')
+    return prep
+
+
+def resnet18_conv(geom: ResnetConv, prep, x, residual=None, relu=False):
+    """x (n, hin, hin, cin) NHWC -> (n, hout, hout, cout): conv + folded bias [+ residual] [ReLU]"""
+    _dev(prep, x, residual)
+    n = x.shape[0]
+    if tuple(x.shape) != (n, geom.hin, geom.hin, geom.cin):
+        raise ValueError(f'input {tuple(x.shape)} does not match {geom}')
+    out = torch.empty(n, geom.hout, geom.hout, geom.cout, device=x.device, dtype=torch.float32)
+    if residual is not None and tuple(residual.shape) != tuple(out.shape):
+        raise ValueError(f'residual {tuple(residual.shape)} does not match the output {tuple(out.shape)}')
+    d = geom.desc()
+    taps = len(resnet18_live_taps(geom)) if _PROFILE is not None else 0
+    with _timed(geom.label(), 2.0 * n * geom.hout * geom.hout * geom.cout * geom.cin * taps, 0.0):
+        _lib.check(_lib.load().arvae_resnet18_conv(ctypes.byref(d), _ptr(prep), _ptr(x), n, _ptr(residual), int(bool(relu)), _ptr(out),
+                                                   _stream()), 'resnet18_conv')
+    return out
+
+
+def resnet18_stem_prepare(weight, bn=None):
+    _dev(weight)
+    if tuple(weight.shape) != (64, 1, 7, 7):
+        raise ValueError(f'stem weight {tuple(weight.shape)}, expected (64, 1, 7, 7)')
+    lib = _lib.load()
+    prep = torch.empty(lib.arvae_resnet18_stem_prep_floats(), device=weight.device, dtype=torch.float32)
+    _lib.check(lib.arvae_resnet18_stem_prepare(_ptr(weight), *_bn_ptrs(bn), _ptr(prep), _stream()), 'resnet18_stem_prepare')
+    return prep
+
+
+def resnet18_stem(prep, x, relu=True):
+    """x (n, 1, 28, 28) -> (n, 14, 14, 64) NHWC"""
+    _dev(prep, x)
+    n = x.shape[0]
+    if tuple(x.shape) != (n, 1, 28, 28):
+        raise ValueError(f'the classifier takes (B, 1, 28, 28) images, got {tuple(x.shape)}')
+    out = torch.empty(n, 14, 14, 64, device=x.device, dtype=torch.float32)
+    with _timed('resnet18_stem', 2.0 * n * 14 * 14 * 64 * 49, 0.0):
+        _lib.check(_lib.load().arvae_resnet18_stem(_ptr(prep), _ptr(x), n, int(bool(relu)), _ptr(out), _stream()), 'resnet18_stem')
+    return out
+
+
+def resnet18_maxpool(x):
+    """max-pool 3x3 stride 2 pad 1 of an NHWC tensor (padding = -inf)"""
+    _dev(x)
+    n, h, w, c = x.shape
+    out = torch.empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, device=x.device, dtype=torch.float32)
+    with _timed('resnet18_maxpool'):
+        _lib.check(_lib.load().arvae_resnet18_maxpool(_ptr(x), n, h, w, c, _ptr(out), _stream()), 'resnet18_maxpool')
+    return out
+
+
+def resnet18_head(fc_w, fc_b, feat):
+    """feat (n, 512) -> (logits (n, 10), softmax probabilities (n, 10), argmax (n,) int64)"""
+    _dev(fc_w, fc_b, feat)
+    n = feat.shape[0]
+    if tuple(feat.shape) != (n, 512) or tuple(fc_w.shape) != (10, 512) or tuple(fc_b.shape) != (10,):
+        raise ValueError('resnet18_head: feat (n, 512), fc_w (10, 512), fc_b (10,)')
+    logits = torch.empty(n, 10, device=feat.device, dtype=torch.float32)
+    probs = torch.empty_like(logits)
+    pred = torch.empty(n, device=feat.device, dtype=torch.int64)
+    with _timed('resnet18_head', 2.0 * n * 512 * 10, 0.0):
+        _lib.check(_lib.load().arvae_resnet18_head(_ptr(fc_w), _ptr(fc_b), _ptr(feat), n, _ptr(logits), _ptr(probs), _ptr(pred), _stream()),
+                   'resnet18_head')
+    return logits, probs, pred
+
+
+def resnet18_prepare(weights, device):
+    """weights: a filled _lib.ResnetWeights over device tensors the caller keeps alive -> the prepared block of the whole network"""
+    lib = _lib.load()
+    prep = torch.empty(lib.arvae_resnet18_prep_floats(), device=device, dtype=torch.float32)
+    _lib.check(lib.arvae_resnet18_prepare(ctypes.byref(weights), _ptr(prep), _stream()), 'resnet18_prepare')
+    return prep
+
+
+RESNET18_FLOP_PER_IMAGE = 2.0 * (196 * 64 * 49 + 4 * 49 * 64 * 64 * 9 + 16 * 64 * 128 * (9 + 1) + 3 * 16 * 128 * 128 * 9 +
+                                 4 * 128 * 256 * (9 + 1) + 3 * 4 * 256 * 256 * 9 + 256 * 512 * (9 + 1) + 3 * 512 * 512 * 9 + 512 * 10)
+
+
+def resnet18_forward(prep, x):
+    """x (n, 1, 28, 28) -> (logits (n, 10), softmax probabilities (n, 10), argmax (n,) int64) in 22 launches"""
+    _dev(prep, x)
+    n = x.shape[0]
+    if tuple(x.shape) != (n, 1, 28, 28):
+        raise ValueError(f'the classifier takes (B, 1, 28, 28) images, got {tuple(x.shape)}')
+    lib = _lib.load()
+    size = lib.arvae_resnet18_ws_floats(n)
+    if size < 0:
+        _lib.check(size, 'resnet18_ws_floats')
+    ws = torch.empty(size, device=x.device, dtype=torch.float32)
+    logits = torch.empty(n, 10, device=x.device, dtype=torch.float32)
+    probs = torch.empty_like(logits)
+    pred = torch.empty(n, device=x.device, dtype=torch.int64)
+    with _timed('resnet18_forward', RESNET18_FLOP_PER_IMAGE * n, 0.0):       # (the reference network's FLOP: every tap counted)
+        _lib.check(lib.arvae_resnet18_forward(_ptr(prep), _ptr(x), n, _ptr(logits), _ptr(probs), _ptr(pred), _ptr(ws), _stream()),
+                   'resnet18_forward')
+    return logits, probs, pred

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 15  /* 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 16  /* 16: arvae_resnet18_* (inference of the Morpho-MNIST ResNet-18 digit classifier: digit_pred_acc of imagevae/image_vae_trainer.py:319-368); 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -738,6 +738,58 @@ int arvae_comm_group_end(void);
 int64_t arvae_ksg_ws_bytes(int64_t n, int32_t p);
 int arvae_ksg_mi(const double *x, int64_t ldx, int32_t p, const double *y, int64_t n, int32_t k, void *ws, double *mi_out,
                  double *radius_out, int32_t *nx_out, int32_t *ny_out, arvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The Morpho-MNIST digit classifier: inference of a torchvision ResNet-18 (BasicBlock, [2,2,2,2], 10 classes, 1-channel 7x7
+ * stem, AvgPool2d(1)) at 28 x 28, batch-norm in evaluation mode (eps 1e-5, running statistics) folded into the convolutions.
+ * Replaces: imagevae/mnist_resnet.py:18-19 as called by imagevae/image_vae_trainer.py:657-666 (digit_pred_acc).
+ * Activations are NHWC; weights keep the state_dict layout [C_out, C_in, K, K].  csrc/resnet18.hip.
+ *
+ * One convolution: cin, cout in {64, 128, 256, 512}; (ksize 3, pad 1) or (ksize 1, pad 0); stride 1 or 2; hin, win <= 64;
+ * hout = (hin + 2 pad - ksize) / stride + 1.  out = [relu](conv(x, w') + b' [+ residual]) with w' = w gamma / sqrt(var + eps),
+ * b' = beta - mean gamma / sqrt(var + eps) computed in float64 (all four bn pointers NULL: w' = w, b' = 0).  Only the LIVE taps --
+ * those that read a pixel inside the input for some output pixel -- are packed and multiplied; arvae_resnet18_live_taps returns
+ * their number and writes their indices ky * ksize + kx to taps[<= 9] (host memory, may be NULL).
+ * prep: arvae_resnet18_conv_prep_floats(geom) floats, 16-byte aligned, written by _conv_prepare and read by _conv.
+ * residual (optional) and out: [n, hout, wout, cout]; out aliases neither input.  Products on the three-term bf16 MFMA arithmetic,
+ * fp32 accumulation in a fixed order: the same input gives the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t hin, win, cin, hout, wout, cout, ksize, stride, pad, reserved;
+} arvae_resnet18_conv_t;
+int32_t arvae_resnet18_live_taps(const arvae_resnet18_conv_t *geom /* host */, int32_t *taps /* host */);
+int64_t arvae_resnet18_conv_prep_floats(const arvae_resnet18_conv_t *geom /* host */);
+int arvae_resnet18_conv_prepare(const arvae_resnet18_conv_t *geom /* host */, const float *w, const float *bn_w, const float *bn_b,
+                                const float *bn_mean, const float *bn_var, float *prep, arvae_stream_t stream);
+int arvae_resnet18_conv(const arvae_resnet18_conv_t *geom /* host */, const float *prep, const float *x, int32_t n,
+                        const float *residual, int32_t relu, float *out, arvae_stream_t stream);
+/* the stem: conv 7x7 stride 2 pad 3 of x[n,1,28,28] with w[64,1,7,7], BN folded as above, + b', optional ReLU -> out[n,14,14,64] */
+int64_t arvae_resnet18_stem_prep_floats(void);
+int arvae_resnet18_stem_prepare(const float *w, const float *bn_w, const float *bn_b, const float *bn_mean, const float *bn_var,
+                                float *prep, arvae_stream_t stream);
+int arvae_resnet18_stem(const float *prep, const float *x, int32_t n, int32_t relu, float *out, arvae_stream_t stream);
+/* max-pool 3x3 stride 2 pad 1 of x[n,h,w,c] (c a multiple of 4) -> out[n,(h-1)/2+1,(w-1)/2+1,c]; padding counts as -inf */
+int arvae_resnet18_maxpool(const float *x, int32_t n, int32_t h, int32_t w, int32_t c, float *out, arvae_stream_t stream);
+/* logits = feat[n,512] fc_w[10,512]^T + fc_b; probs = softmax(logits); pred = argmax (lowest index on an exact tie).
+ * logits, probs, pred: each optional */
+int arvae_resnet18_head(const float *fc_w, const float *fc_b, const float *feat, int32_t n, float *logits, float *probs, int64_t *pred,
+                        arvae_stream_t stream);
+/* The whole network.  The 19 convolutions after the stem in execution order: layerL.B.conv1, [layerL.0.downsample.0,] layerL.B.conv2
+ * for L = 1..4, B = 0, 1 (the downsample where L >= 2, B = 0), each with the batch-norm that follows it; stem_bn and the bn_*
+ * tables are weight, bias, running_mean, running_var.
+ * arvae_resnet18_prepare writes arvae_resnet18_prep_floats() floats (call it again after ANY change of a weight or statistic);
+ * arvae_resnet18_forward runs x[n,1,28,28] through 22 launches with ws of arvae_resnet18_ws_floats(n) floats and writes
+ * logits[n,10], probs[n,10] and pred[n] (each optional, one required). */
+typedef struct {
+    const float *stem_w, *stem_bn[4];
+    const float *conv_w[19], *bn_w[19], *bn_b[19], *bn_mean[19], *bn_var[19];
+    const float *fc_w, *fc_b;
+} arvae_resnet18_weights_t;
+int64_t arvae_resnet18_prep_floats(void);
+int arvae_resnet18_prepare(const arvae_resnet18_weights_t *weights /* host */, float *prep, arvae_stream_t stream);
+int64_t arvae_resnet18_ws_floats(int32_t n);
+int arvae_resnet18_forward(const float *prep, const float *x, int32_t n, float *logits, float *probs, int64_t *pred, float *ws,
+                           arvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,10 @@ Differences a user can observe: the dataset lives in HBM (arvae_amd.data), a sin
 reference indexes its attribute table with the whole tuple there and raises KeyError), `--no_log` survives the
 second epoch, and after training the script prints a representation summary computed on the device (latent codes /
 attributes of the evaluation split, test loss and accuracy); `--metrics` adds the reference's disentanglement metrics
-(Interpretability, SCC, Modularity, MIG, SAP: arvae_amd.evaluation, KSG estimator in HIP) to it.  The GIF plots and the
-Morpho-MNIST ResNet accuracy stay outside this build's scope.
+(Interpretability, SCC, Modularity, MIG, SAP: arvae_amd.evaluation, KSG estimator in HIP) to it, and `--digit_acc` (Morpho-MNIST
+only) the reference's digit_pred_acc: the accuracy of the ResNet-18 digit classifier (arvae_amd.mnist_resnet, HIP) on the
+inputs, the reconstructions and the latent sweeps; it needs the classifier's checkpoint, models/MnistRESNET/MnistRESNET.pt.  The
+GIF plots stay outside this build's scope.
 """
 import json
 import os
@@ -55,12 +57,16 @@ METRICS_FLAG = '--metrics'
 METRICS_HELP = (f'{METRICS_FLAG}: add the disentanglement metrics (Interpretability, SCC, Modularity, MIG, SAP; '
                 'arvae_amd.evaluation) to the evaluation summary.')
 with_metrics = False
+DIGIT_ACC_FLAG = '--digit_acc'
+DIGIT_ACC_HELP = (f'{DIGIT_ACC_FLAG}: (mnist only) add digit_pred_acc, the ResNet-18 digit classifier\'s accuracy on inputs, '
+                  'reconstructions and latent sweeps, to the evaluation summary; needs models/MnistRESNET/MnistRESNET.pt.')
+with_digit_acc = False
 
 
 def with_options(fn):
     for names, kwargs in reversed(IMAGE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP)(fn)
+    return click.command(epilog=METRICS_HELP + '\n\n' + DIGIT_ACC_HELP)(fn)
 
 
 @with_options
@@ -122,17 +128,24 @@ def main(dataset_type, batch_size, num_epochs, lr, beta, capacity, gamma, delta,
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'latent_mean_abs': [float(v) for v in abs(codes).mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
+        metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or (with_digit_acc and dataset_type == 'mnist') else {}
         if with_metrics:
-            summary.update(eval_metrics_or_warn(codes, attrs, names))
+            summary.update(metrics)
+        if with_digit_acc and dataset_type != 'mnist':
+            print(f'{DIGIT_ACC_FLAG}: the digit classifier applies to mnist only; skipped for {dataset_type}')
+        elif with_digit_acc:
+            trainer.metrics = dict(metrics)              # the sweeps run over the interpretability metric's dimensions
+            summary.update(trainer.get_resnet_accuracy(batch_size=eval_bs))
         print(json.dumps(summary, indent=2))
 
 
 def run(argv=None):
-    """the command line: the reference's flags (main) plus this build's opt-in --metrics"""
-    global with_metrics
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics and --digit_acc"""
+    global with_metrics, with_digit_acc
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
-    main(args=[a for a in argv if a != METRICS_FLAG])
+    with_digit_acc = DIGIT_ACC_FLAG in argv
+    main(args=[a for a in argv if a not in (METRICS_FLAG, DIGIT_ACC_FLAG)])
 
 
 if __name__ == '__main__':
