@@ -25,9 +25,8 @@
 //     16-byte reads for stride-1/2 pixel walks);
 //   * epilogues are 16-byte stores of a lane's consecutive channels, in the Up kernels spread between the next
 //     tile's MFMAs with the waves staggered.
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "conv32_common.h"
 #include "conv32.h"
 #include "reduce.h"
@@ -1192,10 +1191,6 @@ bool conv32_fits(const arvae_link_t *l) {
            l->lo_perm_c == 0 && (int64_t)l->n * l->hh * l->hw * PIXB < (1ll << 31) - (1ll << 20);
 }
 
-template <class K> static void allow_lds(K kernel, int bytes) {
-    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 template <int A, int B> struct MaxOf { static constexpr int value = A > B ? A : B; };
 
 constexpr int LDS_DOWN_S = (PatchLoader<4, 2, 32>::BUF2_DW + 4 * 16 * 64) * 4;
@@ -1206,23 +1201,17 @@ static int down_small_grid(int tiles) {                          // two workgrou
 
 template <int MODE> static void launch_down_small(const Operand &hi, const Ep32 &ep, int n, hipStream_t s) {
     const int tiles = tiles_for<4, 32>(n);
-    static std::once_flag attr;
-    std::call_once(attr, [&] { allow_lds(down32s_kernel<4, MODE>, LDS_DOWN_S); });
-    ARVAE_LAUNCH((down32s_kernel<4, MODE>), dim3(down_small_grid(tiles)), dim3(256), LDS_DOWN_S, s, hi.v, ep, n, tiles);
+    launch_lds<down32s_kernel<4, MODE>>(dim3(down_small_grid(tiles)), dim3(256), LDS_DOWN_S, s, hi.v, ep, n, tiles);
 }
 template <int LO, int MODE, int PX>
 static void launch_up_px(const Operand &lo, const Ep32 &ep, int n, hipStream_t s) {
     const int tiles = tiles_for<LO, PX>(n), grid = grid_for_tiles(tiles);
     if constexpr (LO == 16 && PX == 128 && MODE != EP_GATE_F) {   // compute / store waves
         constexpr int LDSP = (2 * 2 * PatchLoader<16, 1, 128>::PLANE_DW) * 4 + 4 * 4 * 4 * 64 * 16;
-        static std::once_flag attrp;
-        std::call_once(attrp, [&] { allow_lds(up32p_kernel<MODE>, LDSP); });
-        ARVAE_LAUNCH((up32p_kernel<MODE>), dim3(grid), dim3(512), LDSP, s, lo.v, ep, n, tiles);
+        launch_lds<up32p_kernel<MODE>>(dim3(grid), dim3(512), LDSP, s, lo.v, ep, n, tiles);
     } else {
         constexpr int LDSX = 2 * PatchLoader<LO, 1, PX>::PLANE_DW * 4;
-        static std::once_flag attrx;
-        std::call_once(attrx, [&] { allow_lds(up32x_kernel<LO, MODE, PX>, LDSX); });
-        ARVAE_LAUNCH((up32x_kernel<LO, MODE, PX>), dim3(grid), dim3(256), LDSX, s, lo.v, ep, n, tiles);
+        launch_lds<up32x_kernel<LO, MODE, PX>>(dim3(grid), dim3(256), LDSX, s, lo.v, ep, n, tiles);
     }
 }
 // 128-pixel tiles, or 32-pixel tiles when the former give a CU at most one tile (nothing to pipeline, or idle CUs:
@@ -1241,22 +1230,13 @@ static int ep_mode(const Ep32 &ep, int relu) {
 // the four-way reduction-split producer / consumer kernel of the 16x16 / 8x8 layers (down32p.h)
 template <int LO, int MODE> static void launch_down_p(const float *hi, const Ep32 &ep, int n, hipStream_t s) {
     constexpr int LDS = DownK<LO>::LDS_DW * 4;
-    static std::once_flag attr;
-    std::call_once(attr, [&] { allow_lds(down32p_kernel<LO, MODE>, LDS); });
     const int tiles = n * DownK<LO>::TILES_PER_IMG;
-    ARVAE_LAUNCH((down32p_kernel<LO, MODE>), dim3(grid_for_tiles(tiles)), dim3(512), LDS, s, hi, ep, n, tiles);
+    launch_lds<down32p_kernel<LO, MODE>>(dim3(grid_for_tiles(tiles)), dim3(512), LDS, s, hi, ep, n, tiles);
 }
-template <int LO> static void launch_down_p_mode(const float *hi, const Ep32 &ep, int mode, int n, hipStream_t s) {
-    switch (mode) {
-        case EP_GATE_B: launch_down_p<LO, EP_GATE_B>(hi, ep, n, s); break;
-        case EP_GATE_F: launch_down_p<LO, EP_GATE_F>(hi, ep, n, s); break;
-        case EP_RELU: launch_down_p<LO, EP_RELU>(hi, ep, n, s); break;
-        default: launch_down_p<LO, EP_PLAIN>(hi, ep, n, s); break;
-    }
-}
-static void conv32_down_ksplit(const arvae_link_t *l, const float *hi, const Ep32 &ep, int mode, hipStream_t s) {
-    if (l->lh == 16) launch_down_p_mode<16>(hi, ep, mode, l->n, s);
-    else launch_down_p_mode<8>(hi, ep, mode, l->n, s);
+// an epilogue mode as a constant; false: not one of the four (ep_mode() returns no other)
+template <class F> static bool with_ep_mode(int mode, F &&f) { return with_int<EP_GATE_B, EP_GATE_F, EP_RELU, EP_PLAIN>(mode, f); }
+template <int LO> static bool launch_down_p_mode(const float *hi, const Ep32 &ep, int mode, int n, hipStream_t s) {
+    return with_ep_mode(mode, [&](auto MODE) { launch_down_p<LO, decltype(MODE)::value>(hi, ep, n, s); });
 }
 
 // The operands of every entry point below: plain fp32 tensors that come with the AMAX array of their values (amax.h;
@@ -1269,17 +1249,11 @@ int conv32_down(const arvae_link_t *l, const Operand &hi, const float *bias, int
     ARVAE_REQUIRE(wprep != nullptr && amax_in != nullptr, "conv32_down: prepared weights and the input's maxima are needed");
     Ep32 ep{bias, gate, gate_bits, bits_out, out, reinterpret_cast<const uint4 *>(wprep), amax_in, amax_out};
     const int mode = ep_mode(ep, relu);
-    if (l->lh != 4) {
-        conv32_down_ksplit(l, hi.v, ep, mode, s);
-        return check_launch(l->lh == 16 ? "down32_kernel<16>" : "down32_kernel<8>");
-    }
-    switch (mode) {
-        case EP_GATE_B: launch_down_small<EP_GATE_B>(hi, ep, l->n, s); break;
-        case EP_GATE_F: launch_down_small<EP_GATE_F>(hi, ep, l->n, s); break;
-        case EP_RELU: launch_down_small<EP_RELU>(hi, ep, l->n, s); break;
-        default: launch_down_small<EP_PLAIN>(hi, ep, l->n, s); break;
-    }
-    return check_launch("down32_kernel<4>");
+    const bool known = l->lh == 16  ? launch_down_p_mode<16>(hi.v, ep, mode, l->n, s)
+                       : l->lh == 8 ? launch_down_p_mode<8>(hi.v, ep, mode, l->n, s)
+                                    : with_ep_mode(mode, [&](auto MODE) { launch_down_small<decltype(MODE)::value>(hi, ep, l->n, s); });
+    ARVAE_REQUIRE(known, "conv32_down: epilogue mode %d", mode);
+    return check_launch(l->lh == 16 ? "down32_kernel<16>" : l->lh == 8 ? "down32_kernel<8>" : "down32_kernel<4>");
 }
 
 // ---- two stacked ReLU DOWN layers of the forward pass (16x16 then 8x8 output) in ONE launch (round 6) ---------------------------
@@ -1319,20 +1293,15 @@ int conv32_down_chain(const arvae_link_t *a, const arvae_link_t *b, const float 
     Ep32 ep_a{bias_a, nullptr, nullptr, bits_a, out_a, reinterpret_cast<const uint4 *>(wprep_a), amax_in, amax_a};
     Ep32 ep_b{bias_b, nullptr, nullptr, bits_b, out_b, reinterpret_cast<const uint4 *>(wprep_b), nullptr, amax_b};
     constexpr int LDS = (MaxOf<DownK<16>::LDS_DW, DownK<8>::LDS_DW>::value + 4) * 4;
-    static std::once_flag attr;
-    std::call_once(attr, [&] { allow_lds(chain_down_kernel<EP_RELU>, LDS); });
-    ARVAE_LAUNCH((chain_down_kernel<EP_RELU>), dim3(chain_grid(a, b)), dim3(512), LDS, s, hi, ep_a, ep_b, a->n, a->n * DownK<16>::TILES_PER_IMG,
-                 b->n * DownK<8>::TILES_PER_IMG);
+    launch_lds<chain_down_kernel<EP_RELU>>(dim3(chain_grid(a, b)), dim3(512), LDS, s, hi, ep_a, ep_b, a->n, a->n * DownK<16>::TILES_PER_IMG,
+                                           b->n * DownK<8>::TILES_PER_IMG);
     return check_launch("chain(down32<16> + down32<8>)");
 }
 
 template <int LO> static int launch_up(const arvae_link_t *l, const Operand &lo, const Ep32 &ep, int relu, hipStream_t s) {
-    switch (ep_mode(ep, relu)) {
-        case EP_GATE_B: launch_up_v<LO, EP_GATE_B>(lo, ep, l->n, s); break;
-        case EP_GATE_F: launch_up_v<LO, EP_GATE_F>(lo, ep, l->n, s); break;
-        case EP_RELU: launch_up_v<LO, EP_RELU>(lo, ep, l->n, s); break;
-        default: launch_up_v<LO, EP_PLAIN>(lo, ep, l->n, s); break;
-    }
+    const int mode = ep_mode(ep, relu);
+    const bool known = with_ep_mode(mode, [&](auto MODE) { launch_up_v<LO, decltype(MODE)::value>(lo, ep, l->n, s); });
+    ARVAE_REQUIRE(known, "conv32_up: epilogue mode %d", mode);
     return check_launch(LO == 16 ? "up32_kernel<16>" : LO == 8 ? "up32_kernel<8>" : "up32_kernel<4>");
 }
 
@@ -1351,16 +1320,12 @@ int conv32_up_reg(const arvae_link_t *l, const Operand &lo, const float *bias, u
     if (l->lh == 8) {
         const int tiles = tiles_for<8, 32>(l->n), grid_up = grid_for_tiles(tiles);
         constexpr int LDSX8 = MaxOf<2 * PatchLoader<8, 1, 32>::PLANE_DW, 2 * REG_CHUNK>::value * 4;
-        static std::once_flag attr8;
-        std::call_once(attr8, [&] { allow_lds(up32x_reg_kernel<8, EP_RELU>, LDSX8); });
-        ARVAE_LAUNCH((up32x_reg_kernel<8, EP_RELU>), dim3(grid_up + reg_bx * r), dim3(256), LDSX8, s, lo.v, ep, l->n, tiles, grid_up, reg, reg_bx);
+        launch_lds<up32x_reg_kernel<8, EP_RELU>>(dim3(grid_up + reg_bx * r), dim3(256), LDSX8, s, lo.v, ep, l->n, tiles, grid_up, reg, reg_bx);
         return check_launch("up32_kernel<8>(+ reg_loss)");
     }
     const int tiles = tiles_for<4, 32>(l->n), grid_up = grid_for_tiles(tiles);
     constexpr int LDSX = MaxOf<2 * PatchLoader<4, 1, 32>::PLANE_DW, 2 * REG_CHUNK>::value * 4;
-    static std::once_flag attr;
-    std::call_once(attr, [&] { allow_lds(up32x_reg_kernel<4, EP_RELU>, LDSX); });
-    ARVAE_LAUNCH((up32x_reg_kernel<4, EP_RELU>), dim3(grid_up + reg_bx * r), dim3(256), LDSX, s, lo.v, ep, l->n, tiles, grid_up, reg, reg_bx);
+    launch_lds<up32x_reg_kernel<4, EP_RELU>>(dim3(grid_up + reg_bx * r), dim3(256), LDSX, s, lo.v, ep, l->n, tiles, grid_up, reg, reg_bx);
     return check_launch("up32_kernel<4>(+ reg_loss)");
 }
 
@@ -1434,15 +1399,10 @@ template <int LO> static int launch_stream(const arvae_link_t *l, const float *l
     constexpr int LDS = RowStream<LO>::LDS_DW * 4;
     int total, spw, grid;
     stream_geometry(l, cu_count(), total, spw, grid);
-    static std::once_flag attr;
-    std::call_once(attr, [&] {
-        allow_lds(wgrad32r_kernel<LO, 0>, LDS);
-        allow_lds(wgrad32r_kernel<LO, 1>, LDS);
-        allow_lds(wgrad32r_kernel<LO, 2>, LDS);
+    const bool known = with_int<0, 1, 2>(bias_mode, [&](auto BIAS) {
+        launch_lds<wgrad32r_kernel<LO, decltype(BIAS)::value>>(dim3(grid), dim3(512), LDS, s, lo, hi, slab, l->n, total, spw, amax_lo, amax_hi);
     });
-    if (bias_mode == 1) ARVAE_LAUNCH((wgrad32r_kernel<LO, 1>), dim3(grid), dim3(512), LDS, s, lo, hi, slab, l->n, total, spw, amax_lo, amax_hi);
-    else if (bias_mode == 2) ARVAE_LAUNCH((wgrad32r_kernel<LO, 2>), dim3(grid), dim3(512), LDS, s, lo, hi, slab, l->n, total, spw, amax_lo, amax_hi);
-    else ARVAE_LAUNCH((wgrad32r_kernel<LO, 0>), dim3(grid), dim3(512), LDS, s, lo, hi, slab, l->n, total, spw, amax_lo, amax_hi);
+    ARVAE_REQUIRE(known, "conv32_wgrad: bias mode %d", bias_mode);
     return check_launch(LO == 16 ? "wgrad32_kernel<16>" : "wgrad32_kernel<8>");
 }
 static int conv32_wgrad_stream(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *slab, int bias_mode, const unsigned *amax_lo,
@@ -1465,18 +1425,10 @@ constexpr int LDS_WGRAD_X4 = 2 * (PatchLoader<4, 2, 64>::PLANE_DW / PSB * WGRAD_
 static int launch_wgrad_x4(const arvae_link_t *l, const Operand &lo, const Operand &hi, float *slab, int bias_mode, int grid,
                            const unsigned *amax_lo, const unsigned *amax_hi, hipStream_t s) {
     const int tiles = tiles_for<4, 64>(l->n);
-    static std::once_flag attr;
-    std::call_once(attr, [&] {
-        allow_lds(wgrad32x_kernel<4, 0>, LDS_WGRAD_X4);
-        allow_lds(wgrad32x_kernel<4, 1>, LDS_WGRAD_X4);
-        allow_lds(wgrad32x_kernel<4, 2>, LDS_WGRAD_X4);
+    const bool known = with_int<0, 1, 2>(bias_mode, [&](auto BIAS) {
+        launch_lds<wgrad32x_kernel<4, decltype(BIAS)::value>>(dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
     });
-    if (bias_mode == 1)
-        ARVAE_LAUNCH((wgrad32x_kernel<4, 1>), dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
-    else if (bias_mode == 2)
-        ARVAE_LAUNCH((wgrad32x_kernel<4, 2>), dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
-    else
-        ARVAE_LAUNCH((wgrad32x_kernel<4, 0>), dim3(grid), dim3(256), LDS_WGRAD_X4, s, lo.v, hi.v, slab, l->n, tiles, amax_lo, amax_hi);
+    ARVAE_REQUIRE(known, "conv32_wgrad: bias mode %d", bias_mode);
     return check_launch("wgrad32_kernel<4>");
 }
 
@@ -1548,34 +1500,24 @@ template <int LO> static int launch_pair_big(const arvae_link_t *l, bool up, con
     const dim3 grid(grid_a + grid_b);
     if (up) {                                                    // DOWN map of g (hi side); weight gradient: lo = layer input, hi = g
         constexpr int LDS = MaxOf<LDS_W, DownK<LO>::LDS_DW * 4>::value;
-        static std::once_flag attr;
-        std::call_once(attr, [&] { allow_lds(pair_down_wgrad_kernel<LO, EP_GATE_B, 2>, LDS); });
-        ARVAE_LAUNCH((pair_down_wgrad_kernel<LO, EP_GATE_B, 2>), grid, dim3(512), LDS, s, g, ep, l->n, tiles_a, grid_a, x_in, g, slab, total, spw,
-                     amax_x, amax_g);
+        launch_lds<pair_down_wgrad_kernel<LO, EP_GATE_B, 2>>(grid, dim3(512), LDS, s, g, ep, l->n, tiles_a, grid_a, x_in, g, slab, total, spw, amax_x, amax_g);
         return check_launch(LO == 16 ? "pair(down32<16> + wgrad32<16>)" : "pair(down32<8> + wgrad32<8>)");
     }
     if constexpr (LO == 16) {                                    // UP map of g (lo side); weight gradient: lo = g, hi = layer input
         constexpr int LDS_U = (2 * 2 * PatchLoader<16, 1, 128>::PLANE_DW) * 4 + 4 * 4 * 4 * 64 * 16;
         constexpr int LDS = MaxOf<LDS_W, LDS_U>::value;
-        static std::once_flag attr;
         if (c1 != nullptr) {                                     // + the first layer's weight gradient in the Up half's store waves
             constexpr int LDS_C = MaxOf<LDS_W, LDS_U + 4 * C1W_WAVE_DW * 4>::value;
-            static std::once_flag attr_c;
-            std::call_once(attr_c, [&] { allow_lds(pair_up16_wgrad_kernel<EP_GATE_B, 1, true>, LDS_C); });
-            ARVAE_LAUNCH((pair_up16_wgrad_kernel<EP_GATE_B, 1, true>), grid, dim3(512), LDS_C, s, g, ep, l->n, tiles_a, grid_a, g, x_in,
-                         slab, total, spw, amax_g, amax_x, *c1);
+            launch_lds<pair_up16_wgrad_kernel<EP_GATE_B, 1, true>>(grid, dim3(512), LDS_C, s, g, ep, l->n, tiles_a, grid_a, g, x_in, slab, total, spw,
+                                                                   amax_g, amax_x, *c1);
             return check_launch("pair(up32<16> + wgrad32<16> + wgrad_c1)");
         }
-        std::call_once(attr, [&] { allow_lds(pair_up16_wgrad_kernel<EP_GATE_B, 1>, LDS); });
-        ARVAE_LAUNCH((pair_up16_wgrad_kernel<EP_GATE_B, 1>), grid, dim3(512), LDS, s, g, ep, l->n, tiles_a, grid_a, g, x_in, slab,
-                     total, spw, amax_g, amax_x, C1Wgrad{nullptr, nullptr});
+        launch_lds<pair_up16_wgrad_kernel<EP_GATE_B, 1>>(grid, dim3(512), LDS, s, g, ep, l->n, tiles_a, grid_a, g, x_in, slab, total, spw, amax_g,
+                                                         amax_x, C1Wgrad{nullptr, nullptr});
         return check_launch("pair(up32<16> + wgrad32<16>)");
     } else {
         constexpr int LDS = MaxOf<LDS_W, 2 * PatchLoader<8, 1, 32>::PLANE_DW * 4>::value;
-        static std::once_flag attr;
-        std::call_once(attr, [&] { allow_lds(pair_up8_wgrad_kernel<EP_GATE_B, 1>, LDS); });
-        ARVAE_LAUNCH((pair_up8_wgrad_kernel<EP_GATE_B, 1>), grid, dim3(512), LDS, s, g, ep, l->n, tiles_a, grid_a, g, x_in, slab, total,
-                     spw, amax_g, amax_x);
+        launch_lds<pair_up8_wgrad_kernel<EP_GATE_B, 1>>(grid, dim3(512), LDS, s, g, ep, l->n, tiles_a, grid_a, g, x_in, slab, total, spw, amax_g, amax_x);
         return check_launch("pair(up32<8> + wgrad32<8>)");
     }
 }
@@ -1605,21 +1547,16 @@ int conv32_pair(const arvae_link_t *l, bool up, const float *g, const float *x_i
     constexpr int LDS_U = 2 * PatchLoader<4, 1, 32>::PLANE_DW * 4;
     constexpr int LDS = MaxOf<LDS_WGRAD_X4, MaxOf<LDS_DOWN_S, LDS_U>::value>::value;
     const int wg_tiles = tiles_for<4, 64>(l->n), dg_tiles = tiles_for<4, 32>(l->n), grid_a = (dg_tiles + 1) / 2;
-    static std::once_flag attr;
-    std::call_once(attr, [&] {
-        allow_lds(pair4_down_kernel<EP_GATE_F, 2>, LDS);
-        allow_lds(pair4_down_kernel<EP_GATE_B, 2>, LDS);
-        allow_lds(pair4_up_kernel<EP_GATE_F, 1>, LDS);
-        allow_lds(pair4_up_kernel<EP_GATE_B, 1>, LDS);
-    });
     const dim3 grid(grid_a + wg_tiles);
-    if (up) {                                                    // DOWN map of g (hi side); weight gradient: lo = layer input, hi = g
-        if (gate_bits) ARVAE_LAUNCH((pair4_down_kernel<EP_GATE_B, 2>), grid, dim3(256), LDS, s, g, ep, x_in, g, slab, l->n, dg_tiles, wg_tiles, grid_a, amax_x, amax_g);
-        else ARVAE_LAUNCH((pair4_down_kernel<EP_GATE_F, 2>), grid, dim3(256), LDS, s, g, ep, x_in, g, slab, l->n, dg_tiles, wg_tiles, grid_a, amax_x, amax_g);
-    } else {                                                     // UP map of g (lo side); weight gradient: lo = g, hi = layer input
-        if (gate_bits) ARVAE_LAUNCH((pair4_up_kernel<EP_GATE_B, 1>), grid, dim3(256), LDS, s, g, ep, g, x_in, slab, l->n, dg_tiles, wg_tiles, grid_a, amax_g, amax_x);
-        else ARVAE_LAUNCH((pair4_up_kernel<EP_GATE_F, 1>), grid, dim3(256), LDS, s, g, ep, g, x_in, slab, l->n, dg_tiles, wg_tiles, grid_a, amax_g, amax_x);
-    }
+    with_bool(up, [&](auto UP) {
+        with_bool(gate_bits == nullptr, [&](auto FLOAT_GATE) {
+            constexpr int MODE = decltype(FLOAT_GATE)::value ? EP_GATE_F : EP_GATE_B;
+            if constexpr (decltype(UP)::value)                   // DOWN map of g (hi side); weight gradient: lo = layer input, hi = g
+                launch_lds<pair4_down_kernel<MODE, 2>>(grid, dim3(256), LDS, s, g, ep, x_in, g, slab, l->n, dg_tiles, wg_tiles, grid_a, amax_x, amax_g);
+            else                                                 // UP map of g (lo side); weight gradient: lo = g, hi = layer input
+                launch_lds<pair4_up_kernel<MODE, 1>>(grid, dim3(256), LDS, s, g, ep, g, x_in, slab, l->n, dg_tiles, wg_tiles, grid_a, amax_g, amax_x);
+        });
+    });
     *job = SlabJob{slab, dwt, dbias, wg_tiles, SLAB_C32, up ? 2 : 1};
     return check_launch(up ? "pair4(down32 + wgrad32)" : "pair4(up32 + wgrad32)");
 }

@@ -9,9 +9,8 @@
 // with the activation derivative / dropout keep-mask of a gradient operand folded into the gather, and bias, activation
 // and keep-mask in the epilogue.  The weight gradient is the same tile machinery with both operands "K x rows" (pixels
 // are the reduction axis), sliced over pixels into a workspace and summed in fixed order.
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "x3tile.h"
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
@@ -1155,13 +1154,6 @@ int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
         const int ipw = (wr_img_per_wg(l) + 1) / 2, slices = (l->n + ipw - 1) / ipw;      // two workgroups per CU
         const dim3 grid((l->chi + 31) / 32, slices);
         const size_t lds = (2 * WP_APLANE + WP_RING * 2 * WP_HPLANE) * sizeof(unsigned short);
-        static std::once_flag attr;
-        std::call_once(attr, [&] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_pairs_h2_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_pairs_h2_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_pairs_h2_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_pairs_h2_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        });
         // maxima of the operands AS MULTIPLIED: the caller's (plain tensors only) or taken here, behind the partial sums in ws
         unsigned *am = reinterpret_cast<unsigned *>(ws + conv64_wgrad_ws_floats(l) - 2 * AMAX_N);
         // the bias gradient (column sums of lo or of hi) rides in the kernel: both tensors pass through its registers anyway
@@ -1180,10 +1172,11 @@ int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
             if (int rc = conv64_operand_amax(g.hi, (int64_t)l->n * l->hh * l->hw * l->chi, am + AMAX_N, s)) return rc;
             amax_hi = am + AMAX_N;
         }
-        if (pl && ph) ARVAE_LAUNCH((conv_wgrad_pairs_h2_kernel<true, true>), grid, dim3(256), lds, s, g, ipw, amax_lo, amax_hi);
-        else if (pl) ARVAE_LAUNCH((conv_wgrad_pairs_h2_kernel<true, false>), grid, dim3(256), lds, s, g, ipw, amax_lo, amax_hi);
-        else if (ph) ARVAE_LAUNCH((conv_wgrad_pairs_h2_kernel<false, true>), grid, dim3(256), lds, s, g, ipw, amax_lo, amax_hi);
-        else ARVAE_LAUNCH((conv_wgrad_pairs_h2_kernel<false, false>), grid, dim3(256), lds, s, g, ipw, amax_lo, amax_hi);
+        with_bool(pl, [&](auto PL) {
+            with_bool(ph, [&](auto PH) {
+                launch_lds<conv_wgrad_pairs_h2_kernel<decltype(PL)::value, decltype(PH)::value>>(grid, dim3(256), lds, s, g, ipw, amax_lo, amax_hi);
+            });
+        });
         const int count = taps * l->clo * l->chi, nbias = ride ? (bias_side == 1 ? l->clo : l->chi) : 0;
         ARVAE_LAUNCH(conv64_wgrad_reduce_kernel, dim3(((count + nbias) * 4 + 255) / 256), dim3(256), 0, s, ws, slices, taps, l->clo, l->chi, dwt,
                      g.bias_ws, nbias, dbias);
@@ -1193,27 +1186,20 @@ int conv64_wgrad(const arvae_link_t *l, const Operand &lo, const Operand &hi, fl
         const int ipw = wr_img_per_wg(l), slices = (l->n + ipw - 1) / ipw;
         const dim3 grid((l->chi + 31) / 32, slices);
         const size_t lds = (2 * 3 * WR_APLANE + WR_RING * 3 * WR_HPLANE) * sizeof(unsigned short);
-        static std::once_flag attr;
-        std::call_once(attr, [&] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_rows_x3_kernel<true, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_rows_x3_kernel<true, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_rows_x3_kernel<false, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_rows_x3_kernel<false, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        with_bool(pl, [&](auto PL) {
+            with_bool(ph, [&](auto PH) {
+                launch_lds<conv_wgrad_rows_x3_kernel<decltype(PL)::value, decltype(PH)::value, 4>>(grid, dim3(256), lds, s, g, ipw);
+            });
         });
-        if (pl && ph) ARVAE_LAUNCH((conv_wgrad_rows_x3_kernel<true, true, 4>), grid, dim3(256), lds, s, g, ipw);
-        else if (pl) ARVAE_LAUNCH((conv_wgrad_rows_x3_kernel<true, false, 4>), grid, dim3(256), lds, s, g, ipw);
-        else if (ph) ARVAE_LAUNCH((conv_wgrad_rows_x3_kernel<false, true, 4>), grid, dim3(256), lds, s, g, ipw);
-        else ARVAE_LAUNCH((conv_wgrad_rows_x3_kernel<false, false, 4>), grid, dim3(256), lds, s, g, ipw);
         const int count = taps * l->clo * l->chi;
         ARVAE_LAUNCH(conv64_wgrad_reduce_kernel, dim3((count * 4 + 255) / 256), dim3(256), 0, s, ws, slices, taps, l->clo, l->chi, dwt);
         return check_launch("conv64_wgrad(rows)");
     }
     const int slices = (int)(((int64_t)l->n * l->lh * l->lw + C64_WG_SLICE - 1) / C64_WG_SLICE);
     const dim3 grid(taps, slices);
-    if (pl && ph) ARVAE_LAUNCH((conv_wgrad_x3_kernel<true, true>), grid, dim3(256), 0, s, g);
-    else if (pl) ARVAE_LAUNCH((conv_wgrad_x3_kernel<true, false>), grid, dim3(256), 0, s, g);
-    else if (ph) ARVAE_LAUNCH((conv_wgrad_x3_kernel<false, true>), grid, dim3(256), 0, s, g);
-    else ARVAE_LAUNCH((conv_wgrad_x3_kernel<false, false>), grid, dim3(256), 0, s, g);
+    with_bool(pl, [&](auto PL) {
+        with_bool(ph, [&](auto PH) { ARVAE_LAUNCH((conv_wgrad_x3_kernel<decltype(PL)::value, decltype(PH)::value>), grid, dim3(256), 0, s, g); });
+    });
     const int count = taps * l->clo * l->chi;
     ARVAE_LAUNCH(conv64_wgrad_reduce_kernel, dim3((count * 4 + 255) / 256), dim3(256), 0, s, ws, slices, taps, l->clo, l->chi, dwt);
     return check_launch("conv64_wgrad");

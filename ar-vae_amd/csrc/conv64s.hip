@@ -27,9 +27,8 @@
 //     gradient operand is applied at that point -- once per value instead of once per tap.
 //   * padding: source columns outside [0, sw) are not stored; a lane whose tap falls there reads one shared zero pixel
 //     (a select on the LDS address).  Source rows outside the image are staged as zeros.
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
 #include "conv64.h"
@@ -513,18 +512,11 @@ bool conv64s_fits(const arvae_link_t *l, bool up) {
            (int64_t)l->n * (up ? l->lh : l->hh) * sw * 64 * 4 < ((int64_t)1 << 31) - (1 << 20);   // buffer resources (32-bit byte offsets)
 }
 
-template <int MT, int NT> static void launch_stage(const ConvStage &g, int grid, hipStream_t s) {
+// false: a source mode other than 0, 1, 2 (Operand::mode() returns no other)
+template <int MT, int NT> static bool launch_stage(const ConvStage &g, int grid, hipStream_t s) {
     constexpr int LDS = 2 * S_BUF * 4;
-    static std::once_flag attr;
-    std::call_once(attr, [&] {
-        (void)hipFuncSetAttribute((const void *)conv64s_kernel<MT, NT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void *)conv64s_kernel<MT, NT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void *)conv64s_kernel<MT, NT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
     const int mode = (g.src.y == nullptr || (g.src.act == ARVAE_ACT_NONE && g.src.mask == nullptr)) ? 0 : g.src.mode();
-    if (mode == 0) ARVAE_LAUNCH((conv64s_kernel<MT, NT, 0>), dim3(grid), dim3(256), LDS, s, g);
-    else if (mode == 1) ARVAE_LAUNCH((conv64s_kernel<MT, NT, 1>), dim3(grid), dim3(256), LDS, s, g);
-    else ARVAE_LAUNCH((conv64s_kernel<MT, NT, 2>), dim3(grid), dim3(256), LDS, s, g);
+    return with_int<0, 1, 2>(mode, [&](auto MODE) { launch_lds<conv64s_kernel<MT, NT, decltype(MODE)::value>>(dim3(grid), dim3(256), LDS, s, g); });
 }
 
 // src [n][sh][sw][64] -> out [n][oh][ow][q]; source coordinate = output coordinate + sgn * k + off
@@ -571,10 +563,13 @@ int conv64s_run(const Operand &src, int n, int sh, int sw, int oh, int ow, int q
     g.amax_out = amax_out;
     const int tiles = n * g.groups, cus = cu_count_s() < AMAX_N / 4 ? cu_count_s() : AMAX_N / 4;
     const int grid = tiles < cus ? tiles : cus;
-    if (mt == 4 && nt == 2) launch_stage<4, 2>(g, grid, s);
-    else if (mt == 3 && nt == 2) launch_stage<3, 2>(g, grid, s);
-    else if (mt == 4) launch_stage<4, 1>(g, grid, s);
-    else launch_stage<3, 1>(g, grid, s);
+    bool mt_known = false, mode_known = false;
+    with_bool(nt == 2, [&](auto WIDE) {
+        mt_known = with_int<4, 3>(mt, [&](auto MT) {             // (stage_geometry() gives 4 or 3)
+            mode_known = launch_stage<decltype(MT)::value, decltype(WIDE)::value ? 2 : 1>(g, grid, s);
+        });
+    });
+    ARVAE_REQUIRE(mt_known && mode_known, "%s: no row-staged kernel for %d M tiles or for this source operand", what, mt);
     return check_launch(what);
 }
 

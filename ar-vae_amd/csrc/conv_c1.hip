@@ -8,9 +8,8 @@
 //                 producing its 2x2 output pixels from the 3x3 lo neighbourhood staged in LDS, weights
 //                 from scalar registers
 //   wgrad_c1 : dwt[c][0][ky][kx] += sum_pixels lo[pix][c] * img[pix @ tap]; bias sums ride along
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "reduce.h"
 #include "prep32.h"
 #include "wgrad_c1s.h"
@@ -454,6 +453,9 @@ int conv_c1_down_with_prep(const arvae_link_t *l, const Operand &img, const floa
     return check_launch("down_c1_kernel(+ weight prep)");
 }
 
+// the GATE argument of down_c1s_kernel / pair_c1_kernel: 1 sign bits, 2 a float activation, 0 none
+static int gate_mode(const float *gate, const uint16_t *gate_bits) { return gate_bits != nullptr ? 1 : gate != nullptr ? 2 : 0; }
+
 int conv_c1_down(const arvae_link_t *l, const Operand &img, const float *wt, const float *bias, int relu,
                  const float *gate, const uint16_t *gate_bits, uint16_t *bits_out, float *out, hipStream_t s, unsigned *amax_out) {
     Ep1 ep{bias, gate, gate_bits, bits_out, out, relu, amax_out};
@@ -461,9 +463,10 @@ int conv_c1_down(const arvae_link_t *l, const Operand &img, const float *wt, con
     int grid = 256 * 16 / 4;                                     // 16 waves per CU, in workgroups of four independent waves
     if (grid > (n_rows + 3) / 4) grid = (n_rows + 3) / 4;
     if (amax_out != nullptr && grid > AMAX_N) grid = AMAX_N;     // one AMAX writer unit per workgroup
-    if (gate_bits != nullptr) ARVAE_LAUNCH(down_c1s_kernel<1>, dim3(grid), dim3(256), 0, s, img, wt, ep, n_rows);
-    else if (gate != nullptr) ARVAE_LAUNCH(down_c1s_kernel<2>, dim3(grid), dim3(256), 0, s, img, wt, ep, n_rows);
-    else ARVAE_LAUNCH(down_c1s_kernel<0>, dim3(grid), dim3(256), 0, s, img, wt, ep, n_rows);
+    const bool known = with_int<1, 2, 0>(gate_mode(gate, gate_bits), [&](auto GATE) {
+        ARVAE_LAUNCH(down_c1s_kernel<decltype(GATE)::value>, dim3(grid), dim3(256), 0, s, img, wt, ep, n_rows);
+    });
+    ARVAE_REQUIRE(known, "conv_c1_down: gate mode");
     return check_launch("down_c1_kernel");
 }
 
@@ -478,16 +481,10 @@ static int up_c1_grid(int tiles) {
     return tiles < 2 * cached ? tiles : 2 * cached;
 }
 
-template <class K> static void up_c1_lds(K kernel) {
-    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * T_FLOATS * 4);
-}
-
 int conv_c1_up(const arvae_link_t *l, const float *lo, const float *wt, const float *bias, float *out, hipStream_t s) {
     const int tiles = l->n * (LO1 / TRU);
-    static std::once_flag attr;
-    std::call_once(attr, [&] { up_c1_lds(up_c1_kernel<ARVAE_RECON_BERNOULLI, false>); });
-    ARVAE_LAUNCH((up_c1_kernel<ARVAE_RECON_BERNOULLI, false>), dim3(up_c1_grid(tiles)), dim3(256), 2 * T_FLOATS * 4, s, lo,
-                       wt, bias, out, nullptr, 0.f, nullptr, nullptr, l->n, tiles);
+    launch_lds<up_c1_kernel<ARVAE_RECON_BERNOULLI, false>>(dim3(up_c1_grid(tiles)), dim3(256), 2 * T_FLOATS * 4, s, lo, wt, bias, out, nullptr, 0.f,
+                                                           nullptr, nullptr, l->n, tiles, VaeFinishArgs{}, nullptr);   // (no finishing step)
     return check_launch("up_c1_kernel");
 }
 
@@ -502,17 +499,11 @@ int conv_c1_up_recon(const arvae_link_t *l, const float *lo, const float *wt, co
     const float inv_b = 1.f / (float)l->n;
     const VaeFinishArgs fa = fin != nullptr ? *fin : VaeFinishArgs{};
     if (fin == nullptr) fin_dst = nullptr;
-    static std::once_flag attr;
-    std::call_once(attr, [&] {
-        up_c1_lds(up_c1_kernel<ARVAE_RECON_BERNOULLI, true>);
-        up_c1_lds(up_c1_kernel<ARVAE_RECON_GAUSSIAN, true>);
+    const bool known = with_int<ARVAE_RECON_BERNOULLI, ARVAE_RECON_GAUSSIAN>(dist, [&](auto DIST) {
+        launch_lds<up_c1_kernel<decltype(DIST)::value, true>>(dim3(grid), dim3(256), 2 * T_FLOATS * 4, s, lo, wt, bias, out, x, inv_b, partial, dlogits,
+                                                              l->n, tiles, fa, fin_dst);
     });
-    if (dist == ARVAE_RECON_BERNOULLI)
-        ARVAE_LAUNCH((up_c1_kernel<ARVAE_RECON_BERNOULLI, true>), dim3(grid), dim3(256), 2 * T_FLOATS * 4, s, lo, wt, bias,
-                           out, x, inv_b, partial, dlogits, l->n, tiles, fa, fin_dst);
-    else
-        ARVAE_LAUNCH((up_c1_kernel<ARVAE_RECON_GAUSSIAN, true>), dim3(grid), dim3(256), 2 * T_FLOATS * 4, s, lo, wt, bias,
-                           out, x, inv_b, partial, dlogits, l->n, tiles, fa, fin_dst);
+    ARVAE_REQUIRE(known, "conv_c1_up_recon: reconstruction distribution %d", dist);
     *nb_out = grid;
     return check_launch("up_c1_kernel(recon)");
 }
@@ -556,9 +547,10 @@ int conv_c1_pair(const arvae_link_t *l, const Operand &g_img, const float *wt, c
     const int rider = finish != nullptr ? 1 : 0;                // (+ the deferred finishing step's workgroup; finish: DEVICE pointer)
     const int n_rows = l->n * LO1, grid_a = 256, grid_b = wgrad_c1_groups(l) - rider;
     const dim3 grid(rider + grid_a + grid_b);
-    if (gate_bits != nullptr) ARVAE_LAUNCH(pair_c1_kernel<1>, grid, dim3(64 * WGS_WAVES), 0, s, g_img, wt, ep, n_rows, w_lo, g_img, slab, n_rows, grid_a, rider, finish);
-    else if (gate != nullptr) ARVAE_LAUNCH(pair_c1_kernel<2>, grid, dim3(64 * WGS_WAVES), 0, s, g_img, wt, ep, n_rows, w_lo, g_img, slab, n_rows, grid_a, rider, finish);
-    else ARVAE_LAUNCH(pair_c1_kernel<0>, grid, dim3(64 * WGS_WAVES), 0, s, g_img, wt, ep, n_rows, w_lo, g_img, slab, n_rows, grid_a, rider, finish);
+    const bool known = with_int<1, 2, 0>(gate_mode(gate, gate_bits), [&](auto GATE) {
+        ARVAE_LAUNCH(pair_c1_kernel<decltype(GATE)::value>, grid, dim3(64 * WGS_WAVES), 0, s, g_img, wt, ep, n_rows, w_lo, g_img, slab, n_rows, grid_a, rider, finish);
+    });
+    ARVAE_REQUIRE(known, "conv_c1_pair: gate mode");
     *job = SlabJob{slab, dwt, dbias, grid_b, SLAB_C1, bias_mode};
     return check_launch("pair_c1(down_c1 + wgrad_c1)");
 }

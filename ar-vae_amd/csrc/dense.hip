@@ -9,9 +9,8 @@
 //
 // Channel permutations (hi_perm / lo_perm of arvae_link_t: the NCHW flatten between conv and dense
 // stacks over channels-last activations) are index remaps on the feature axis.
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "amax.h"
 #include "dense.h"
 #include "reduce.h"
@@ -815,10 +814,7 @@ int wide_wgrad(const WideWgradJob *jobs, int count, hipStream_t s) {
         b.wg_end[i] = total;
     }
     typedef WideLds<WideF32<RG_KROWS, 64>, WidePlanes<RG_KROWS, 64>> Lds;
-    constexpr size_t lds_bytes = Lds::BYTES;
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void *)wide_wgrad_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lds::BYTES); });
-    ARVAE_LAUNCH(wide_wgrad_x3_kernel, dim3(total), dim3(256), lds_bytes, s, b);
+    launch_lds<wide_wgrad_x3_kernel>(dim3(total), dim3(256), Lds::BYTES, s, b);
     return check_launch("wide_wgrad");
 }
 
@@ -848,15 +844,6 @@ bool wide_gemm_fits(const WideGemm &g, int slices) {
            a_bytes < ((int64_t)1 << 31) && b_bytes < ((int64_t)1 << 31) && slices >= 1 && slices <= WIDE_MAX_SLICES &&
            (g.amax_out == nullptr || tiles <= AMAX_N);
 }
-template <class SA, class SB, int EP>
-static void launch_wide(const WideGemm &g, dim3 grid, hipStream_t s) {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void *)wide_gemm_x3_kernel<SA, SB, EP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideLds<SA, SB>::BYTES);
-    });
-    constexpr size_t lds_bytes = WideLds<SA, SB>::BYTES;
-    ARVAE_LAUNCH((wide_gemm_x3_kernel<SA, SB, EP, 1>), grid, dim3(256), lds_bytes, s, g);
-}
 // slices > 1 (or partial): g.out = workspace of `slices` x slice_floats, the consumer sums them; else the finished product
 int wide_gemm(WideGemm g, int slices, bool partial, hipStream_t s) {
     ARVAE_REQUIRE(wide_gemm_fits(g, slices), "wide_gemm: operand shapes / alignment");
@@ -868,16 +855,16 @@ int wide_gemm(WideGemm g, int slices, bool partial, hipStream_t s) {
     typedef WidePlanes<RG_ROWSK, WIDE_T> AP;
     typedef WidePlanes<RG_ROWSK, WIDE_T> BR;
     typedef WidePlanes<RG_KROWS, WIDE_T> BK;
-    switch ((g.a_planes ? 4 : 0) + (g.b_krows ? 2 : 0) + (partial ? 0 : 1)) {
-        case 0: launch_wide<AF, BR, WG_EP_PARTIAL>(g, grid, s); break;
-        case 1: launch_wide<AF, BR, WG_EP_FULL>(g, grid, s); break;
-        case 2: launch_wide<AF, BK, WG_EP_PARTIAL>(g, grid, s); break;
-        case 3: launch_wide<AF, BK, WG_EP_FULL>(g, grid, s); break;
-        case 4: launch_wide<AP, BR, WG_EP_PARTIAL>(g, grid, s); break;
-        case 5: launch_wide<AP, BR, WG_EP_FULL>(g, grid, s); break;
-        case 6: launch_wide<AP, BK, WG_EP_PARTIAL>(g, grid, s); break;
-        default: launch_wide<AP, BK, WG_EP_FULL>(g, grid, s); break;
-    }
+    with_bool(g.a_planes == 0, [&](auto A_F32) {
+        with_bool(g.b_krows == 0, [&](auto B_ROWSK) {
+            with_bool(partial, [&](auto PARTIAL) {
+                using SA = std::conditional_t<decltype(A_F32)::value, AF, AP>;
+                using SB = std::conditional_t<decltype(B_ROWSK)::value, BR, BK>;
+                constexpr int EP = decltype(PARTIAL)::value ? WG_EP_PARTIAL : WG_EP_FULL;
+                launch_lds<wide_gemm_x3_kernel<SA, SB, EP, 1>>(grid, dim3(256), WideLds<SA, SB>::BYTES, s, g);   // (one N tile per wave only)
+            });
+        });
+    });
     return check_launch(partial ? "wide_gemm(partial)" : "wide_gemm(full)");
 }
 
@@ -1278,10 +1265,9 @@ static void launch_rows_gemm(const RowsGemm &g, int slices, hipStream_t s) {
     };
     const bool va = vec_ok(g.a, g.lda, LA, g.P), vb = vec_ok(g.b, g.ldb, LB, g.Q);
     const dim3 grid((g.P + RG_TP - 1) / RG_TP, (g.Q + RG_TQ - 1) / RG_TQ, slices);
-    if (va && vb) ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, true, true>), grid, dim3(256), 0, s, g);
-    else if (va) ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, true, false>), grid, dim3(256), 0, s, g);
-    else if (vb) ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, false, true>), grid, dim3(256), 0, s, g);
-    else ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, false, false>), grid, dim3(256), 0, s, g);
+    with_bool(va, [&](auto VA) {
+        with_bool(vb, [&](auto VB) { ARVAE_LAUNCH((rows_gemm_x3_kernel<LA, LB, EP, decltype(VA)::value, decltype(VB)::value>), grid, dim3(256), 0, s, g); });
+    });
 }
 
 // the operand needs no per-element work (no activation derivative, no keep-mask)
@@ -1313,8 +1299,10 @@ int dense_fwd(const arvae_link_t *l, const float *x, const float *w, const float
         return check_launch("rows_gemm_kernel<fwd>");
     }
     const dim3 grid((p.batch + 31) / 32, (p.n_out + 31) / 32);
-    if (dense_short_k(p.n_in, (int)(grid.x * grid.y))) ARVAE_LAUNCH(dense_fwd_kernel<4>, grid, dim3(256), 0, s, p);
-    else ARVAE_LAUNCH(dense_fwd_kernel<16>, grid, dim3(1024), 0, s, p);
+    with_bool(dense_short_k(p.n_in, (int)(grid.x * grid.y)), [&](auto SHORT) {
+        constexpr int WAVES = decltype(SHORT)::value ? 4 : 16;
+        ARVAE_LAUNCH(dense_fwd_kernel<WAVES>, grid, dim3(64 * WAVES), 0, s, p);
+    });
     return check_launch("dense_fwd_kernel");
 }
 
@@ -1329,8 +1317,10 @@ int dense_dgrad(const arvae_link_t *l, const Operand &g, const float *w, const f
         return check_launch("rows_gemm_kernel<dgrad>");
     }
     const dim3 grid((p.batch + 31) / 32, (p.n_in + 31) / 32);
-    if (dense_short_k(p.n_out, (int)(grid.x * grid.y))) ARVAE_LAUNCH(dense_dgrad_kernel<4>, grid, dim3(256), 0, s, p);
-    else ARVAE_LAUNCH(dense_dgrad_kernel<16>, grid, dim3(1024), 0, s, p);
+    with_bool(dense_short_k(p.n_out, (int)(grid.x * grid.y)), [&](auto SHORT) {
+        constexpr int WAVES = decltype(SHORT)::value ? 4 : 16;
+        ARVAE_LAUNCH(dense_dgrad_kernel<WAVES>, grid, dim3(64 * WAVES), 0, s, p);
+    });
     return check_launch("dense_dgrad_kernel");
 }
 

@@ -17,9 +17,9 @@
 // over all T*R rows afterwards (ops.py).
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 #include "diag.h"
 #include "common.h"
+#include "dispatch.h"
 #include "splitmath.h"
 #include "gru_common.h"
 #include "gru_mask.h"
@@ -638,20 +638,13 @@ static int fill_batch(GruSeqBatch *b, const arvae_gru_seq_t *seqs, int nseq, int
 
 using namespace arvae;
 
-// launch KERNEL<hidden, ..., rows per workgroup> for the hidden size and row width at hand
-#define GRU_LAUNCH_RW(KERNEL, HH, RWV, ...)                                                                                       \
-    {                                                                                                                            \
-        const dim3 g_((rows + (RWV) - 1) / (RWV), nseq);                                                                          \
-        if ((RWV) == 4) ARVAE_LAUNCH((KERNEL<HH, 4>), g_, dim3(4 * HH), 0, st, __VA_ARGS__);                                      \
-        else if ((RWV) == 8) ARVAE_LAUNCH((KERNEL<HH, 8>), g_, dim3(4 * HH), 0, st, __VA_ARGS__);                                 \
-        else ARVAE_LAUNCH((KERNEL<HH, 16>), g_, dim3(4 * HH), 0, st, __VA_ARGS__);                                                \
-    }
-#define GRU_LAUNCH(KERNEL, RWV, ...)                                                                                             \
-    {                                                                                                                            \
-        if (hidden == 128) GRU_LAUNCH_RW(KERNEL, 128, RWV, __VA_ARGS__)                                                           \
-        else if (hidden == 64) GRU_LAUNCH_RW(KERNEL, 64, RWV, __VA_ARGS__)                                                        \
-        else GRU_LAUNCH_RW(KERNEL, 32, RWV, __VA_ARGS__)                                                                          \
-    }
+// f(hidden size, rows per workgroup) as constants; false: a hidden size that is not built (arvae_gru_seq_supported) or a row width
+// gru_rows_per_wg() does not return
+template <class F> static bool gru_with_shape(int hidden, int rw, F &&f) {
+    bool rw_known = false;
+    const bool h_known = with_int<128, 64, 32>(hidden, [&](auto HH) { rw_known = with_int<4, 8, 16>(rw, [&](auto RW) { f(HH, RW); }); });
+    return h_known && rw_known;
+}
 
 // ARVAE_GRU_BF16_BWD=1 (diagnostic build): the backward recurrence on the three-term bf16 split, as through round 4
 static bool gru_bf16_backward() {
@@ -697,7 +690,11 @@ int arvae::gru_seq_fwd_masked(const arvae_gru_seq_t *seqs, const GruSeqMask *mas
     }
     hipStream_t st = as_stream(stream);
     const int rw = gru_rows_per_wg(rows, nseq);
-    GRU_LAUNCH(gru_seq_fwd_h2_kernel, rw, b, steps, rows)
+    const bool known = gru_with_shape(hidden, rw, [&](auto HH, auto RW) {
+        constexpr int H = decltype(HH)::value, R = decltype(RW)::value;
+        ARVAE_LAUNCH((gru_seq_fwd_h2_kernel<H, R>), dim3((rows + R - 1) / R, nseq), dim3(4 * H), 0, st, b, steps, rows);
+    });
+    ARVAE_REQUIRE(known, "gru_seq_fwd: no kernel for hidden size %d at %d rows per workgroup", hidden, rw);
     return check_launch("gru_seq_fwd_kernel");
 }
 
@@ -728,8 +725,14 @@ int arvae::gru_seq_bwd_masked(const arvae_gru_seq_t *seqs, const GruSeqMask *mas
     }
     hipStream_t st = as_stream(stream);
     const int rw = gru_rows_per_wg(rows, nseq);
-    if (gru_bf16_backward()) GRU_LAUNCH(gru_seq_bwd_x3_kernel, rw, b, steps, rows)
-    else GRU_LAUNCH(gru_seq_bwd_h2_kernel, rw, b, steps, rows)
+    const bool known = gru_bf16_backward() ? gru_with_shape(hidden, rw, [&](auto HH, auto RW) {
+        constexpr int H = decltype(HH)::value, R = decltype(RW)::value;
+        ARVAE_LAUNCH((gru_seq_bwd_x3_kernel<H, R>), dim3((rows + R - 1) / R, nseq), dim3(4 * H), 0, st, b, steps, rows);
+    }) : gru_with_shape(hidden, rw, [&](auto HH, auto RW) {
+        constexpr int H = decltype(HH)::value, R = decltype(RW)::value;
+        ARVAE_LAUNCH((gru_seq_bwd_h2_kernel<H, R>), dim3((rows + R - 1) / R, nseq), dim3(4 * H), 0, st, b, steps, rows);
+    });
+    ARVAE_REQUIRE(known, "gru_seq_bwd: no kernel for hidden size %d at %d rows per workgroup", hidden, rw);
     return check_launch("gru_seq_bwd_kernel");
 }
 

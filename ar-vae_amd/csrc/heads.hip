@@ -4,9 +4,8 @@
 // d_hidden = W_mu^T d_mu + W_ls^T d_ls (gated by the hidden layer's ReLU).  The heads are [zdim <= 16] x [h] GEMVs
 // per sample: a few MFLOP per batch, so the cost is the number of launches; plain FMA loops, 8 batch rows per
 // 256-thread workgroup.
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "rng.h"
 #include "heads.h"
 
@@ -247,12 +246,7 @@ int heads_latent_fwd(const arvae_layer_t *hm, const arvae_layer_t *hl, int batch
     p.eps = eps; p.mu = mu; p.log_std = log_std; p.sigma = sigma; p.z = z;
     p.batch = batch; p.h = hm->link.chi; p.zdim = zdim;
     const size_t lds = (size_t)(HEAD_ROWS * p.h + 2 * HEAD_ZMAX * (p.h + 4) + HEAD_ROWS * 32) * sizeof(float);
-    static std::once_flag attr;
-    std::call_once(attr, [&] {
-        (void)hipFuncSetAttribute((const void *)heads_latent_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (HEAD_ROWS * HEAD_HMAX + 2 * HEAD_ZMAX * (HEAD_HMAX + 4) + HEAD_ROWS * 32) * (int)sizeof(float));
-    });
-    ARVAE_LAUNCH(heads_latent_fwd_kernel, dim3((batch + HEAD_ROWS - 1) / HEAD_ROWS), dim3(256), lds, s, p);
+    launch_lds<heads_latent_fwd_kernel>(dim3((batch + HEAD_ROWS - 1) / HEAD_ROWS), dim3(256), lds, s, p);
     return check_launch("heads_latent_fwd");
 }
 

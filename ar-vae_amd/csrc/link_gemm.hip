@@ -12,7 +12,7 @@
 // gathered global -> registers (prefetched one K-tile ahead so the loads fly under the MFMAs) ->
 // LDS in k-major order [BK][BM+1], from where each lane reads the single A and B value the
 // 32x32x2 MFMA wants (lane = (row|col) + 32 * k-parity) with conflict-free ds_read_b32.
-#include "common.h"
+#include "launch.h"
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
 #include "dense.h"
@@ -908,8 +908,9 @@ extern "C" int arvae_link_up(const arvae_link_t *link, const arvae_operand_t *lo
         Epilogue ep{bias, out_mask, hi, out_act};
         const size_t t_bytes = sizeof(float) * 17 * link->lh * link->lw;
         if ((link->clo == 64 || link->clo == 32) && link->kh * link->kw <= 16 && t_bytes <= 96 * 1024) {
-            if (link->clo == 64) ARVAE_LAUNCH(up_single_channel_mfma_kernel<4>, dim3(link->n), dim3(256), t_bytes, st, p.g, lo->v, wt, ep);
-            else ARVAE_LAUNCH(up_single_channel_mfma_kernel<2>, dim3(link->n), dim3(256), t_bytes, st, p.g, lo->v, wt, ep);
+            with_bool(link->clo == 64, [&](auto WIDE) {            // KQ = clo / 16
+                launch_lds<up_single_channel_mfma_kernel<decltype(WIDE)::value ? 4 : 2>>(dim3(link->n), dim3(256), t_bytes, st, p.g, lo->v, wt, ep);
+            });
             return check_launch("link_up(single channel, mfma)");
         }
         const int blocks = min((total + 255) / 256, 256 * 8);

@@ -3,6 +3,7 @@
 // wavefront (64-lane) shuffle reductions, per-workgroup partials in a caller-provided workspace and a
 // fixed-order finishing pass (bitwise reproducible: no float atomics on the loss values).
 #include "common.h"
+#include "dispatch.h"
 #include "attributes.h"
 #include "regloss.h"
 #include "vae_finish.h"
@@ -425,12 +426,10 @@ int recon_partials(const float *logits, const float *x, int64_t count, int64_t b
                    float *dlogits, hipStream_t s, int *nb_out) {
     const int nb = grid_for(count, 8, RECON_MAX_BLOCKS);
     const float inv_b = 1.f / (float)batch;
-    if (dist == ARVAE_RECON_BERNOULLI)
-        ARVAE_LAUNCH(image_recon_kernel<ARVAE_RECON_BERNOULLI>, dim3(nb), dim3(256), 0, s, logits, x, count,
-                           inv_b, ws, dlogits);
-    else
-        ARVAE_LAUNCH(image_recon_kernel<ARVAE_RECON_GAUSSIAN>, dim3(nb), dim3(256), 0, s, logits, x, count,
-                           inv_b, ws, dlogits);
+    const bool known = with_int<ARVAE_RECON_BERNOULLI, ARVAE_RECON_GAUSSIAN>(dist, [&](auto DIST) {
+        ARVAE_LAUNCH(image_recon_kernel<decltype(DIST)::value>, dim3(nb), dim3(256), 0, s, logits, x, count, inv_b, ws, dlogits);
+    });
+    ARVAE_REQUIRE(known, "image_recon: reconstruction distribution %d", dist);
     *nb_out = nb;
     return check_launch("image_recon");
 }

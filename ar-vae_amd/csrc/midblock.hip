@@ -12,9 +12,8 @@
 // reduce-major for the direction that uses it ([k][n] for the forward product, [n][k] for the backward one), with the
 // NCHW-flatten permutations of the first / last layer folded in.  Exact fp32 FMA chains (no MFMA: at 4 rows a matrix tile
 // would be three quarters padding and the weight stream, not the arithmetic, sets the pace).
-#include <mutex>
 #include "diag.h"
-#include "common.h"
+#include "launch.h"
 #include "dense.h"
 #include "rng.h"
 #include "midprep.h"
@@ -783,19 +782,17 @@ static void midc_common(McArgs &c, const MidArgs &a, int batch) {
     c.g_e0 = a.enc[0].gpre; c.g_e1 = a.enc[1].gpre; c.g_d0 = a.dec[0].gpre; c.g_d1 = a.dec[1].gpre; c.g_d2 = a.dec[2].gpre;
 }
 
-static void mid_allow_lds() {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const int bytes4 = (2 * 4 * (MID_MAX_W + 4) + mid_red(4) + 4 * 32) * (int)sizeof(float), bytes8 = 120 * 1024;
-        static_assert((2 * 4 * (MID_MAX_W + 4) + mid_red(4) + 4 * 32) * sizeof(float) <= 160 * 1024, "the 4-row block must fit the LDS");
-        (void)hipFuncSetAttribute((const void *)mid_forward_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes4);
-        (void)hipFuncSetAttribute((const void *)mid_backward_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes4);
-        (void)hipFuncSetAttribute((const void *)mid_forward_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes4);
-        (void)hipFuncSetAttribute((const void *)mid_backward_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes4);
-        (void)hipFuncSetAttribute((const void *)mid_forward_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes4);
-        (void)hipFuncSetAttribute((const void *)mid_backward_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes4);
-        (void)hipFuncSetAttribute((const void *)mid_forward_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes8);
-        (void)hipFuncSetAttribute((const void *)mid_backward_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes8);
+// (the widest block mid_describe() can size: pl.lds_bytes at four rows and MID_MAX_W)
+static_assert((2 * 4 * (MID_MAX_W + 4) + mid_red(4) + 4 * 32) * sizeof(float) <= 160 * 1024, "the 4-row block must fit the LDS");
+
+// the row kernel of either pass for pl.rows batch rows per workgroup; false: a row count that is not built (mid_describe picks 1, 2, 4)
+static bool mid_launch_rows(const MidPlan &pl, bool backward, hipStream_t s) {
+    const MidArgs &a = pl.args;
+    return with_int<4, 1, 2, 8>(pl.rows, [&](auto ROWS) {
+        constexpr int R = decltype(ROWS)::value;
+        const dim3 grid((a.batch + R - 1) / R);
+        if (!backward) launch_lds<mid_forward_kernel<R>>(grid, dim3(MID_T), pl.lds_bytes, s, a);
+        else launch_lds<mid_backward_kernel<R>>(grid, dim3(MID_T), pl.lds_bytes, s, a);
     });
 }
 
@@ -874,7 +871,6 @@ int mid_forward(const arvae_image_vae_t *m, int batch, const float *params, floa
         a.warm_ptr[nw] = a.hf; a.warm_lines[nw++] = lines((int64_t)a.h * 2 * a.zdim);
         for (int i = 0; i < a.nd - (wide_d ? 1 : 0); ++i) { a.warm_ptr[nw] = a.dec[i].mf; a.warm_lines[nw++] = lines((int64_t)a.dec[i].k * a.dec[i].n); }
     }
-    mid_allow_lds();
     if (!prep_done) {
         ARVAE_LAUNCH(mid_prep_kernel, dim3(mid_prep_blocks(pl.prep)), dim3(256), 0, s, pl.prep);
         if (int rc = check_launch("mid_prep_kernel")) return rc;
@@ -896,10 +892,7 @@ int mid_forward(const arvae_image_vae_t *m, int batch, const float *params, floa
         return midc_forward(c, s);
     }
     ARVAE_REQUIRE(fold == nullptr, "mid_forward: folded conv layers need the clustered kernels");
-    if (pl.rows == 1) ARVAE_LAUNCH(mid_forward_kernel<1>, dim3(batch), dim3(MID_T), pl.lds_bytes, s, a);
-    else if (pl.rows == 2) ARVAE_LAUNCH(mid_forward_kernel<2>, dim3((batch + 1) / 2), dim3(MID_T), pl.lds_bytes, s, a);
-    else if (pl.rows == 8) ARVAE_LAUNCH(mid_forward_kernel<8>, dim3((batch + 7) / 8), dim3(MID_T), pl.lds_bytes, s, a);
-    else ARVAE_LAUNCH(mid_forward_kernel<4>, dim3((batch + 3) / 4), dim3(MID_T), pl.lds_bytes, s, a);
+    ARVAE_REQUIRE(mid_launch_rows(pl, false, s), "mid_forward: no row kernel for %d rows per workgroup", pl.rows);
     if (int rc = check_launch("mid_forward_kernel")) return rc;
     if (wide_d) {
         if (int rc = wide_gemm(f2, 1, false, s)) return rc;
@@ -973,7 +966,6 @@ int mid_backward(const arvae_image_vae_t *m, int batch, const float *params, flo
         a.warm_ptr[nw] = a.hb; a.warm_lines[nw++] = lines((int64_t)a.h * 2 * a.zdim);
         for (int i = a.ne - 1; i >= (wide_e ? 1 : 0); --i) { a.warm_ptr[nw] = a.enc[i].mb; a.warm_lines[nw++] = lines((int64_t)a.enc[i].kb * a.enc[i].n); }
     }
-    mid_allow_lds();
     if (wide_d)
         if (int rc = wide_gemm(b1, b1_slices, true, s)) return rc;
     if (midc_use(pl.cluster, batch, m->flags)) {
@@ -993,10 +985,7 @@ int mid_backward(const arvae_image_vae_t *m, int batch, const float *params, flo
         return midc_backward(c, s);
     }
     ARVAE_REQUIRE(fold == nullptr, "mid_backward: folded conv layers need the clustered kernels");
-    if (pl.rows == 1) ARVAE_LAUNCH(mid_backward_kernel<1>, dim3(batch), dim3(MID_T), pl.lds_bytes, s, a);
-    else if (pl.rows == 2) ARVAE_LAUNCH(mid_backward_kernel<2>, dim3((batch + 1) / 2), dim3(MID_T), pl.lds_bytes, s, a);
-    else if (pl.rows == 8) ARVAE_LAUNCH(mid_backward_kernel<8>, dim3((batch + 7) / 8), dim3(MID_T), pl.lds_bytes, s, a);
-    else ARVAE_LAUNCH(mid_backward_kernel<4>, dim3((batch + 3) / 4), dim3(MID_T), pl.lds_bytes, s, a);
+    ARVAE_REQUIRE(mid_launch_rows(pl, true, s), "mid_backward: no row kernel for %d rows per workgroup", pl.rows);
     if (int rc = check_launch("mid_backward_kernel")) return rc;
     if (wide_e) {
         if (int rc = wide_gemm(b2, 1, false, s)) return rc;

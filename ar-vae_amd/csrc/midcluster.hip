@@ -21,9 +21,8 @@
 // every cluster: a hang.)  What is left -- fewer than 16 places can ever be resident -- ends in mc_wait's bound: the poll gives
 // up after MC_WAIT_TICKS (1 s) of its own running time, ORs a code into the caller's status word (arvae_image_vae_t.status) and the
 // workgroup leaves; the host raises on that word where it synchronises anyway and stays on the row kernels (midblock.hip).
-#include <mutex>
-
 #include "diag.h"
+#include "launch.h"
 #include "amax.h"
 #include "conv32_common.h"       // raw buffer access
 #include "midcluster.h"
@@ -995,14 +994,6 @@ __global__ __launch_bounds__(MC_T) void midc_backward_kernel(McArgs p) {
     else midc_backward_body<false>(p, place);
 }
 
-std::once_flag g_lds_once;
-void allow_lds() {
-    std::call_once(g_lds_once, [] {
-        (void)hipFuncSetAttribute((const void *)midc_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FLOATS * 4);
-        (void)hipFuncSetAttribute((const void *)midc_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FLOATS * 4);
-    });
-}
-
 }  // namespace
 
 #ifdef ARVAE_STAMPS_MIDC
@@ -1017,7 +1008,8 @@ unsigned long long midc_wait_ticks() { return MC_WAIT_TICKS; }
 // a question of speed since the tickets (a grid that does not fit still completes, cluster after cluster).
 int midc_resident_capacity() {
     static const int cap = [] {
-        allow_lds();
+        allow_lds<midc_forward_kernel>(LDS_FLOATS * sizeof(float));      // (the occupancy is asked before any launch)
+        allow_lds<midc_backward_kernel>(LDS_FLOATS * sizeof(float));
         int fwd = 0, bwd = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fwd, (const void *)midc_forward_kernel, MC_T, LDS_FLOATS * sizeof(float)) != hipSuccess ||
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&bwd, (const void *)midc_backward_kernel, MC_T, LDS_FLOATS * sizeof(float)) != hipSuccess) {
@@ -1030,14 +1022,12 @@ int midc_resident_capacity() {
 }
 
 int midc_forward(const McArgs &a, hipStream_t s) {
-    allow_lds();
-    ARVAE_LAUNCH(midc_forward_kernel, dim3(a.clusters * MC_S), dim3(MC_T), LDS_FLOATS * sizeof(float), s, a);
+    launch_lds<midc_forward_kernel>(dim3(a.clusters * MC_S), dim3(MC_T), LDS_FLOATS * sizeof(float), s, a);
     return check_launch(a.fold ? "midc_forward_kernel(+ conv4, deconv1)" : "midc_forward_kernel");
 }
 
 int midc_backward(const McArgs &a, hipStream_t s) {
-    allow_lds();
-    ARVAE_LAUNCH(midc_backward_kernel, dim3(a.clusters * MC_S), dim3(MC_T), LDS_FLOATS * sizeof(float), s, a);
+    launch_lds<midc_backward_kernel>(dim3(a.clusters * MC_S), dim3(MC_T), LDS_FLOATS * sizeof(float), s, a);
     return check_launch(a.fold ? "midc_backward_kernel(+ conv4, deconv1)" : "midc_backward_kernel");
 }
 

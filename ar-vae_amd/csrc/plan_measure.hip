@@ -11,8 +11,7 @@
 // Reference graph: measurevae/encoder.py:8-124, measurevae/decoder.py:309-525, measurevae/measure_vae.py:97-131,
 // measurevae/measure_vae_trainer.py:85-140 (loss), utils/trainer.py:140 (backward).
 #include "diag.h"
-#include "common.h"
-#include <mutex>
+#include "launch.h"
 #include "dense.h"
 #include "regloss.h"
 #include "gru_mask.h"
@@ -433,9 +432,7 @@ extern "C" int arvae_measure_vae_forward(const arvae_measure_vae_t *m, int32_t b
         MeasureHeadsFwd hf{w.h12, P + m->mean_w2, P + m->mean_b2, P + m->lstd_w2, P + m->lstd_b2, eps, w.hmu, w.hls, mu, w.log_std, sigma, z,
                            d.b, 2 * He, d.z};
         const int lds = (MH_ROWS * 4 * He + 2 * d.z * (2 * He + 4) + MH_ROWS * 64) * 4;
-        static std::once_flag attr;
-        std::call_once(attr, [] { (void)hipFuncSetAttribute((const void *)measure_heads_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); });
-        ARVAE_LAUNCH(measure_heads_fwd_kernel, dim3((d.b + MH_ROWS - 1) / MH_ROWS), dim3(256), lds, s, hf);
+        launch_lds<measure_heads_fwd_kernel>(dim3((d.b + MH_ROWS - 1) / MH_ROWS), dim3(256), lds, s, hf);
         MV_TRY(check_launch("measure_heads_fwd_kernel"));
     } else {
         MV_TRY(arvae_split_cols(w.h12, d.b, 2 * He, 2 * He, w.hmu, w.hls, 0, stream));

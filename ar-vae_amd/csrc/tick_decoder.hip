@@ -14,9 +14,9 @@
 // Two kernels: tick_free_run_h2_kernel for the reference's two layers, tick_free_run_layers_kernel behind it for one, three and four.
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 #include "diag.h"
 #include "common.h"
+#include "dispatch.h"
 #include "splitmath.h"
 #include "gru_common.h"
 #include "stamps.h"
@@ -871,23 +871,17 @@ static void tick_prep_launch(const TickPrep &tp, float *ws, hipStream_t st) {
     ARVAE_LAUNCH(tick_prep_kernel<HH>, dim3((items + 255) / 256), dim3(256), 0, st, tp, wmax);
 }
 
-// f(the rows per workgroup gru_rows_per_wg chose, as a compile-time constant)
-template <class F>
-static void tick_with_rw(int rw, F f) {
-    if (rw == 4) f(std::integral_constant<int, 4>{});
-    else if (rw == 8) f(std::integral_constant<int, 8>{});
-    else f(std::integral_constant<int, 16>{});
-}
-
+// false (here and in tick_stack_launch): a row width gru_rows_per_wg() does not return
 template <int HH, bool MM>
-static void tick_h2_launch(const TickFreeRun &p, const TickPrep &tp, float *ws, int rw, const TickSample &smp, hipStream_t st) {
+static bool tick_h2_launch(const TickFreeRun &p, const TickPrep &tp, float *ws, int rw, const TickSample &smp, hipStream_t st) {
     const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
     const dim3 gr((p.batch + rw - 1) / rw);
     tick_prep_launch<HH>(tp, ws, st);
-    tick_with_rw(rw, [&](auto rwc) {
-        constexpr int RW = decltype(rwc)::value;
-        if (smp.u != nullptr) ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, RW, PICK_MULTINOMIAL>), gr, dim3(4 * HH), 0, st, p, packed, smp);
-        else ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, RW, PICK_ARGMAX>), gr, dim3(4 * HH), 0, st, p, packed, smp);
+    return with_int<4, 8, 16>(rw, [&](auto RW) {
+        with_bool(smp.u != nullptr, [&](auto DRAW) {
+            constexpr int PICK = decltype(DRAW)::value ? PICK_MULTINOMIAL : PICK_ARGMAX;
+            ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, MM, decltype(RW)::value, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);
+        });
     });
 }
 
@@ -916,10 +910,11 @@ static int tick_free_run_launch(const arvae_tick_weights_t *wts, const float *h0
     hipStream_t st = as_stream(stream);
     const int rw = gru_rows_per_wg(batch, 1);
     const TickSample smp{uniforms, inv_temperature};
-    const bool m = mask != nullptr;
-    if (hidden == 128) (m ? tick_h2_launch<128, true> : tick_h2_launch<128, false>)(p, tp, ws, rw, smp, st);
-    else if (hidden == 64) (m ? tick_h2_launch<64, true> : tick_h2_launch<64, false>)(p, tp, ws, rw, smp, st);
-    else (m ? tick_h2_launch<32, true> : tick_h2_launch<32, false>)(p, tp, ws, rw, smp, st);
+    bool rw_known = false;
+    const bool h_known = with_int<128, 64, 32>(hidden, [&](auto HH) {
+        with_bool(mask != nullptr, [&](auto MM) { rw_known = tick_h2_launch<decltype(HH)::value, decltype(MM)::value>(p, tp, ws, rw, smp, st); });
+    });
+    ARVAE_REQUIRE(h_known && rw_known, "tick_free_run: no kernel for hidden size %d at %d rows per workgroup", hidden, rw);
     return check_launch("tick_free_run_h2_kernel");
 }
 
@@ -961,14 +956,15 @@ extern "C" int64_t arvae_tick_free_run_layers_ws_floats(int32_t hidden, int32_t 
 }
 
 template <int HH, int LL>
-static void tick_stack_launch(const TickStack &p, const TickPrep &tp, float *ws, int rw, const TickSample &smp, hipStream_t st) {
+static bool tick_stack_launch(const TickStack &p, const TickPrep &tp, float *ws, int rw, const TickSample &smp, hipStream_t st) {
     const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
     const dim3 gr((p.batch + rw - 1) / rw);
     tick_prep_launch<HH>(tp, ws, st);
-    tick_with_rw(rw, [&](auto rwc) {
-        constexpr int RW = decltype(rwc)::value;
-        if (smp.u != nullptr) ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, RW, PICK_MULTINOMIAL>), gr, dim3(4 * HH), 0, st, p, packed, smp);
-        else ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, RW, PICK_ARGMAX>), gr, dim3(4 * HH), 0, st, p, packed, smp);
+    return with_int<4, 8, 16>(rw, [&](auto RW) {
+        with_bool(smp.u != nullptr, [&](auto DRAW) {
+            constexpr int PICK = decltype(DRAW)::value ? PICK_MULTINOMIAL : PICK_ARGMAX;
+            ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, decltype(RW)::value, PICK>), gr, dim3(4 * HH), 0, st, p, packed, smp);
+        });
     });
 }
 
@@ -1015,16 +1011,15 @@ extern "C" int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const
     hipStream_t st = as_stream(stream);
     const int rw = gru_rows_per_wg(batch, 1);
     const TickSample smp{uniforms, uniforms != nullptr ? inv_temperature : 1.f};
-#define TICK_STACK_H(LL)                                                                                                          \
-    {                                                                                                                            \
-        if (hidden == 128) { if constexpr (LL == 1) tick_stack_launch<128, 1>(p, tp, ws, rw, smp, st); }                         \
-        else if (hidden == 64) tick_stack_launch<64, LL>(p, tp, ws, rw, smp, st);                                                \
-        else tick_stack_launch<32, LL>(p, tp, ws, rw, smp, st);                                                                  \
-    }
-    if (layers == 1) TICK_STACK_H(1)
-    else if (layers == 3) TICK_STACK_H(3)
-    else TICK_STACK_H(4)
-#undef TICK_STACK_H
+    bool launched = false;
+    with_int<1, 3, 4>(layers, [&](auto LL) {
+        with_int<128, 64, 32>(hidden, [&](auto HH) {
+            constexpr int H = decltype(HH)::value, L = decltype(LL)::value;
+            // (hidden 128 with three or four layers is not built: arvae_tick_free_run_layers_supported)
+            if constexpr (H != 128 || L == 1) launched = tick_stack_launch<H, L>(p, tp, ws, rw, smp, st);
+        });
+    });
+    ARVAE_REQUIRE(launched, "tick_free_run_layers: no kernel for %d layers of hidden size %d at %d rows per workgroup", layers, hidden, rw);
     return check_launch("tick_free_run_layers_kernel");
 }
 

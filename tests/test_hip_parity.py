@@ -1836,6 +1836,61 @@ def test_latent_block_experiment_matches_the_per_layer_path(dev):
                 close(res[flag][kind]['gn'][k], v, rtol=1e-4, atol=1e-9)
 
 
+def test_latent_block_row_kernel_grows_its_lds_within_one_process(dev):
+    """One instantiation of the latent block's row kernels (csrc/midblock.hip) launched with a smaller and then a larger dynamic
+    LDS in ONE process: csrc/launch.h keeps the largest size allowed per instantiation and has to raise it for the second model.
+    Two Morpho-MNIST-shaped models that differ only in the hidden width, 32 and then 64, whole forward and backward at B = 8.
+    mid_describe(): rows per workgroup = 1 for any batch <= the CU count, whatever the width; the 2888-wide layers go to the tile
+    GEMMs, so the row pitch is max(hidden, 2 zdim = 32) + 4 floats: 36 and 68, two row buffers each, so
+    mid_forward_kernel<1> / mid_backward_kernel<1> ask for 256 bytes more the second time.  32 and 64 are the two smallest widths with different sizes whose wide layers
+    stay on the tile GEMMs (their narrow side is a multiple of 32 there).  Each run against the per-layer path (ARVAE_MIDBLOCK=0),
+    tolerances of test_latent_block_experiment_matches_the_per_layer_path."""
+    code = (
+        "import sys, json; sys.path.insert(0, %r)\n"
+        "import numpy as np, torch\n"
+        "from collections import OrderedDict\n"
+        "from tests.test_hip_parity import MorphoMnistDataset\n"
+        "from arvae_amd import synthetic as syn, image_vae as iv\n"
+        "from arvae_amd.image_vae_trainer import ImageVAETrainer\n"
+        "from oracle import image_vae as o_vae\n"
+        "def model_of(width):\n"
+        "    m = iv.MnistVAE()\n"
+        "    m.enc_lin = iv.LayerStack([(0, iv._dense(2888, width))])\n"
+        "    m.enc_mean, m.enc_log_std = iv._dense(width, 16), iv._dense(width, 16)\n"
+        "    m.dec_lin = iv.LayerStack([(0, iv._dense(16, width)), (2, iv._dense(width, 2888))])\n"
+        "    m.enc_lin_plan = [(0, iv.Link.dense(2888, width, in_perm=(8, 361)))]\n"
+        "    m.dec_lin_plan = [(0, iv.Link.dense(16, width)), (2, iv.Link.dense(width, 2888, out_perm=(8, 361)))]\n"
+        "    m.head_link = iv.Link.dense(width, 16)\n"
+        "    return m\n"
+        "out = {}\n"
+        "b = 8\n"
+        "x, lab = syn.mnist_batch(b, seed=5)\n"
+        "eps = syn.normal_noise((b, 16), seed=6)\n"
+        "for width in (32, 64):\n"
+        "    shapes = OrderedDict((k, tuple(width if d == 256 else d for d in s)) for k, s in o_vae.MNIST_SHAPES.items())\n"
+        "    model = model_of(width)\n"
+        "    model.load_state_dict({k: torch.from_numpy(v) for k, v in syn.synth_state(shapes, 9, 0.7).items()})\n"
+        "    trainer = ImageVAETrainer(MorphoMnistDataset(), model, lr=1e-4, reg_type=('all',), reg_dim=(1, 2, 3, 4, 5, 6), dec_dist='bernoulli',\n"
+        "                              beta=4.0, gamma=10.0, capacity=0.0, rand=0, delta=1.0)\n"
+        "    trainer.cuda()\n"
+        "    model.eval()\n"
+        "    model.push_noise(torch.from_numpy(eps))\n"
+        "    trainer.zero_grad()\n"
+        "    loss, acc = trainer.loss_and_acc_for_batch((torch.from_numpy(x).cuda(), torch.from_numpy(lab).cuda()), 0, 0, False)\n"
+        "    loss.backward()\n"
+        "    out[str(width)] = {'loss': float(loss), 'gn': {k: float(np.linalg.norm(p.grad.detach().cpu().numpy())) for k, p in model.named_parameters()}}\n"
+        "print(json.dumps(out))\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    res = {}
+    for flag, env in (('0', {'ARVAE_MIDBLOCK': '0', 'ARVAE_LIB': DIAG_LIB}), ('1', {})):
+        r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
+        assert r.returncode == 0, r.stderr[-2000:]
+        res[flag] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    for width in ('32', '64'):
+        close(res['1'][width]['loss'], res['0'][width]['loss'], rtol=1e-6)
+        for k, v in res['0'][width]['gn'].items():
+            close(res['1'][width]['gn'][k], v, rtol=1e-4, atol=1e-9)
+
+
 # ---------------------------------------------------------------- the epoch loop itself (Trainer.train_model) vs the oracle's trajectory
 def _close_after_adam(got, want, steps):
     """weights after `steps` Adam updates (lr 1e-4): atol 1e-5 for all but a handful of entries.  Adam moves an entry by up
