@@ -72,6 +72,11 @@ class TickStack(ctypes.Structure):
                 [('w_out', c_vp), ('b_out', c_vp), ('h0', c_vp * TICK_MAX_LAYERS), ('h0_stride', c_i64)])
 
 
+class SampleFilter(ctypes.Structure):
+    """arvae_sample_filter_t"""
+    _fields_ = [('top_k', c_i32), ('top_p', c_f32), ('allow', c_vp)]
+
+
 class MeasureVaeDesc(ctypes.Structure):
     """arvae_measure_vae_t"""
     _fields_ = ([(n, c_i32) for n in ('vocab', 'emb', 'enc_hidden', 'dec_hidden', 'zdim', 'steps', 'beats', 'ticks_per_beat')] +
@@ -152,10 +157,14 @@ SIGNATURES = {
                                     c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_sampled': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                             c_vp, c_f32, c_vp, c_vp, c_vp]),
+    'arvae_tick_free_run_filtered': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                             c_vp, c_f32, _P(SampleFilter), c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_layers_supported': (c_i32, [c_i32, c_i32, c_i32]),
     'arvae_tick_free_run_layers_ws_floats': (c_i64, [c_i32, c_i32]),
     'arvae_tick_free_run_layers': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp,
                                            c_vp, c_vp]),
+    'arvae_tick_free_run_layers_filtered': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
+                                                    _P(SampleFilter), c_vp, c_vp, c_vp]),
     'arvae_embed_fwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'arvae_embed_bwd_ws_floats': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     'arvae_embed_bwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
@@ -166,6 +175,7 @@ SIGNATURES = {
     'arvae_tick_gi_bwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'arvae_row_argmax': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     'arvae_row_sample': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
+    'arvae_row_sample_filtered': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, _P(SampleFilter), c_vp, c_vp]),
     'arvae_concat_cols': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     'arvae_split_cols': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     'arvae_scale_mask': (c_i32, [c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp]),

@@ -29,6 +29,18 @@ bool profiling_active();   // arvae_profile_begin() is recording: keep every ker
         if (!(cond)) return ::arvae::fail(ARVAE_E_INVALID, __VA_ARGS__); \
     } while (0)
 
+// what the filtered sampling entry points check first (`who`: the entry point's name in the message; `vocab`: the notes of a row).
+// k_eff = top_k with 0 (off) as vocab; active = some cut or a mask applies (otherwise the unfiltered kernels serve the call)
+static inline int sample_filter_check(const char *who, const arvae_sample_filter_t *filter, int32_t vocab, int *k_eff, bool *active) {
+    ARVAE_REQUIRE(filter != nullptr, "%s: null filter", who);
+    ARVAE_REQUIRE(filter->top_k >= 0 && filter->top_k <= vocab, "%s: top_k %d is outside [0, %d] (0 = off)", who, filter->top_k, vocab);
+    ARVAE_REQUIRE(filter->top_p > 0.f && filter->top_p <= 1.f, "%s: top_p %f is not in (0, 1] (1 = off)", who,   // (a NaN compares false)
+                  (double)filter->top_p);
+    *k_eff = filter->top_k == 0 ? vocab : filter->top_k;
+    *active = *k_eff < vocab || filter->top_p < 1.f || filter->allow != nullptr;
+    return ARVAE_OK;
+}
+
 // stream of the ABI call in progress on this thread (lets check_launch() timestamp kernels when profiling)
 extern thread_local hipStream_t g_cur_stream;
 static inline hipStream_t as_stream(arvae_stream_t s) {

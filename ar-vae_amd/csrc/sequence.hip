@@ -350,6 +350,60 @@ __global__ __launch_bounds__(256) void row_sample_kernel(const float *__restrict
     }
 }
 
+// row_sample_kernel's draw over the notes a filter leaves (arvae_sample_filter_t; the semantics of PICK_FILTERED in tick_decoder.hip on
+// given logits, any cols).  The allowed notes are ordered by descending logit, ties to the lower index; a note survives iff fewer than
+// top_k notes are ordered before it and the e of those notes sums to less than top_p * S, S = the sum of e over the notes top_k leaves
+// (top_p >= 1: no such cut).  The sums grow along the order, so the survivors are a leading run of it: (cut_l, cut_i) is its last
+// note, and a note survives iff it is not ordered behind that one.  Two walks of cols^2 steps per row (S, then the cut), one thread per
+// row: this is the tick-by-tick path.  No allowed note: index 0.
+__global__ __launch_bounds__(256) void row_sample_filtered_kernel(const float *__restrict__ w, int rows, int cols, const float *__restrict__ u,
+                                                                   float inv_t, int top_k, float top_p, const uint8_t *__restrict__ allow,
+                                                                   int64_t *__restrict__ idx) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) {
+        const float *row = w + (int64_t)r * cols;
+        auto on = [&](int j) { return allow == nullptr || allow[j] != 0; };
+        float mx = -INFINITY;
+        for (int j = 0; j < cols; ++j)
+            if (on(j)) mx = fmaxf(mx, row[j]);
+        float s = 0.f;
+        for (int j = 0; j < cols; ++j) {
+            if (!on(j)) continue;
+            int rank = 0;
+            for (int n = 0; n < cols; ++n) rank += on(n) && (row[n] > row[j] || (row[n] == row[j] && n < j)) ? 1 : 0;
+            if (rank < top_k) s += expf((row[j] - mx) * inv_t);
+        }
+        const float cut = top_p * s;
+        float cut_l = INFINITY;
+        int cut_i = -1;
+        for (int j = 0; j < cols; ++j) {
+            if (!on(j)) continue;
+            int rank = 0;
+            float before = 0.f;
+            for (int n = 0; n < cols; ++n) {
+                const bool first = on(n) && (row[n] > row[j] || (row[n] == row[j] && n < j));
+                rank += first ? 1 : 0;
+                before += first ? expf((row[n] - mx) * inv_t) : 0.f;
+            }
+            const bool keep = rank < top_k && (top_p >= 1.f || before < cut);
+            if (keep && (row[j] < cut_l || (row[j] == cut_l && j > cut_i))) { cut_l = row[j]; cut_i = j; }
+        }
+        auto kept = [&](int j) { return on(j) && (row[j] > cut_l || (row[j] == cut_l && j <= cut_i)); };
+        float total = 0.f;
+        for (int j = 0; j < cols; ++j)
+            if (kept(j)) total += expf((row[j] - mx) * inv_t);
+        const float target = u[r] * total;
+        float c = 0.f;
+        int arg = 0;
+        for (int j = 0; j < cols; ++j) {
+            if (!kept(j)) continue;
+            c += expf((row[j] - mx) * inv_t);
+            arg = j;                                           // (the walk repeats the total's additions: it ends on a survivor)
+            if (c >= target) break;
+        }
+        idx[r] = arg;
+    }
+}
+
 // out[r] = [a[r] | b[r]]  and the adjoint split
 __global__ __launch_bounds__(256) void concat_cols_kernel(const float *__restrict__ a, const float *__restrict__ b, int64_t rows,
                                                            int ca, int cb, float *__restrict__ out) {
@@ -553,6 +607,21 @@ extern "C" int arvae_row_sample(const float *w, int32_t rows, int32_t cols, cons
                   (double)inv_temperature);
     ARVAE_LAUNCH(row_sample_kernel, dim3(blocks_for(rows)), dim3(256), 0, as_stream(stream), w, rows, cols, u, inv_temperature, idx);
     return check_launch("row_sample_kernel");
+}
+
+extern "C" int arvae_row_sample_filtered(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature,
+                                         const arvae_sample_filter_t *filter, int64_t *idx, arvae_stream_t stream) {
+    int top_k = 0;
+    bool active = false;
+    if (const int rc = sample_filter_check("row_sample_filtered", filter, cols, &top_k, &active)) return rc;
+    ARVAE_REQUIRE(u != nullptr, "row_sample_filtered: null uniforms");
+    if (!active) return arvae_row_sample(w, rows, cols, u, inv_temperature, idx, stream);
+    ARVAE_REQUIRE(w && idx && rows > 0 && cols > 0, "row_sample_filtered: bad argument");
+    ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
+                  "row_sample_filtered: inverse temperature %f is not a positive finite number", (double)inv_temperature);
+    ARVAE_LAUNCH(row_sample_filtered_kernel, dim3(blocks_for(rows)), dim3(256), 0, as_stream(stream), w, rows, cols, u, inv_temperature, top_k,
+                 filter->top_p, filter->allow, idx);
+    return check_launch("row_sample_filtered_kernel");
 }
 
 extern "C" int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,

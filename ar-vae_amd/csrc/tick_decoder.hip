@@ -8,7 +8,8 @@
 //   layer 0: gh0 = W_hh0 h0 -> gates -> h0' ; mid = h0' * keep-mask * scale
 //   layer 1: r,z: W_ih1 mid + W_hh1 h1 in one accumulator each; n: the two products apart -> gates -> h1'
 //   logits = relu(W_out h1' + b_out) on waves 0..ceil(V/16)-1, the row's pick (PICK_ARGMAX: lowest index on ties) through DPP rows
-//            and LDS -> token, fed back.
+//            and LDS -> token, fed back.  (PICK_MULTINOMIAL: a drawn note; PICK_FILTERED: drawn among the notes a mask, a top-k and a
+//            nucleus cut leave -- tick_filtered_pick.)
 // The products run on the fp16 MFMA with the scaled two-term operands of gru_seq_fwd_h2_kernel (splitmath.h); the recurrent matrices
 // are split and laid out for streaming by one prep pair per call (tick_amax_kernel, tick_prep_kernel) into the caller's workspace.
 // Two kernels: tick_free_run_h2_kernel for the reference's two layers, tick_free_run_layers_kernel behind it for one, three and four.
@@ -73,12 +74,111 @@ __device__ __forceinline__ float row16_prefix(float v) {
 }
 
 // what the free-running kernel feeds back (measurevae/decoder.py:502-516): the top-1 note, or a note drawn from softmax(logits / T)
-constexpr int PICK_ARGMAX = 0, PICK_MULTINOMIAL = 1;
+// PICK_FILTERED: the multinomial draw over the notes a mask, a top-k and a nucleus (top-p) cut leave (generation only: no keep-masks)
+constexpr int PICK_ARGMAX = 0, PICK_MULTINOMIAL = 1, PICK_FILTERED = 2;
 // the draws of PICK_MULTINOMIAL: u [batch][ticks] in (0, 1] and 1 / T (null and unused for PICK_ARGMAX)
 struct TickSample {
     const float *u;
     float inv_t;
 };
+// PICK_FILTERED's: the draws, top_k in [1, vocab] (the entry points turn 0 = off into vocab), top_p in (0, 1] (1 = off) and the allowed
+// notes' bytes [vocab] (null: all).  A type of its own, so that the other picks' kernel arguments stay what they were.
+struct TickFilter {
+    const float *u;
+    float inv_t;
+    int top_k;
+    float top_p;
+    const uint8_t *allow;
+};
+template <int PICK> struct TickPick { using type = TickSample; };
+template <> struct TickPick<PICK_FILTERED> { using type = TickFilter; };
+
+// sum over the 16 lanes of a DPP row by the pairings of row16_max: both lanes of a pair add the same two values, so every lane ends
+// with the same bits
+template <int CTRL> __device__ __forceinline__ float dpp_pair_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float row16_sum(float v) {
+    v = dpp_pair_add<0xB1>(v);
+    v = dpp_pair_add<0x4E>(v);
+    v = dpp_pair_add<0x141>(v);
+    return dpp_pair_add<0x140>(v);
+}
+
+// PICK_FILTERED behind the barrier.  The tile waves have published the row's logits to LDS: `lg` = the row's FLT_LS floats, banned
+// notes and notes past the vocabulary as -1 (below every relu output), columns past the last tile -1 from the kernel's start.  The 16
+// lanes of a DPP row share the row; lane `col` owns notes col, 16 + col, 32 + col, 48 + col.  Order: descending logit, ties to the
+// lower index (the argmax pick's rule), on the logits' bits as integers (non-negative floats order as their bits; the sign bit is
+// cleared, so that a -0 is a 0).  One walk over the row's `nnote` notes (LDS broadcast reads, 16 bytes each) gives each owned note
+// v its rank (how many notes are ordered before it) and the sum of e_n = exp((l_n - M) / T) over those notes; v survives iff it is
+// allowed, rank < top_k and that sum < top_p * S, S = the sum of e over the notes top_k leaves (row16_sum: the same bits in every
+// lane).  The sums grow with the rank (float addition is monotone), so the survivors are a leading run of the order, and the first
+// note's sum is 0 < top_p * S: it always survives.  The draw is arvae_tick_free_run_sampled's over the survivors in index order:
+// e's inclusive prefixes tile by tile (row16_prefix, a tile's total = its last lane's prefix carried into the next), the first
+// SURVIVING note whose prefix reaches u * (the last survivor's prefix).  Nothing allowed: note 0.
+constexpr int FLT_LS = 68;                                     // floats between the logits' rows in LDS (16-byte reads, rows on their own banks)
+__device__ __forceinline__ int tick_filtered_pick(const float *lg, int col, int quad, int nnote, float u, const TickFilter &f, int vocab) {
+    float lv[4], before[4] = {0.f, 0.f, 0.f, 0.f};
+    int key[4], rank[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        lv[c] = lg[16 * c + col];
+        key[c] = lv[c] >= 0.f ? (__builtin_bit_cast(int, lv[c]) & 0x7fffffff) : -1;
+    }
+    const float big = row16_max(fmaxf(fmaxf(lv[0], lv[1]), fmaxf(lv[2], lv[3])));
+    for (int n4 = 0; n4 < nnote; n4 += 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4 *>(lg + n4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = n4 + j;
+            const float ln = q[j];                             // (a scalar copy of the element: tools/probes/bitcast_vector_element.hip)
+            const int kn = ln >= 0.f ? (__builtin_bit_cast(int, ln) & 0x7fffffff) : -1;
+            const float en = __expf((ln - big) * f.inv_t);     // (a banned note is ordered before no allowed one: its e is never added)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const bool first = kn > key[c] || (kn == key[c] && n < 16 * c + col);
+                rank[c] += first ? 1 : 0;
+                before[c] += first ? en : 0.f;
+            }
+        }
+    }
+    float e[4];
+    bool keep[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        keep[c] = key[c] >= 0 && rank[c] < f.top_k;
+        e[c] = keep[c] ? __expf((lv[c] - big) * f.inv_t) : 0.f;
+    }
+    const float cut = f.top_p * row16_sum((e[0] + e[1]) + (e[2] + e[3]));
+    float run = 0.f, pre[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        keep[c] = keep[c] && (f.top_p >= 1.f || before[c] < cut);
+        pre[c] = run + row16_prefix(keep[c] ? e[c] : 0.f);
+        run = __shfl(pre[c], 15, 16);                          // the tile's last prefix: the next tile's base
+    }
+    // C_last is the LAST SURVIVOR's own prefix, not lane 15's: the four shifts of row16_prefix add a lane's terms in an order that
+    // depends on the lane, so a lane behind the last survivor can hold the same sum one ulp higher, and u = 1 against that value
+    // would be reached by no survivor.  u * (its own prefix) <= that prefix for u <= 1: the last survivor always reaches the target.
+    int last = -1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int bits = (int)((unsigned)(__ballot(keep[c]) >> (16 * quad)) & 0xffffu);
+        last = bits != 0 ? 16 * c + 31 - __clz(bits) : last;
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) mine = (last >> 4) == c ? pre[c] : mine;
+    const float target = u * __shfl(mine, last & 15, 16);
+    int ix = max(last, 0);                                     // (not finite: no test below holds, the last survivor; no survivor: note 0)
+#pragma unroll
+    for (int c = 3; c >= 0; --c) {
+        const unsigned long long reached = __ballot(keep[c] && pre[c] >= target);
+        const int bits = (int)((unsigned)(reached >> (16 * quad)) & 0xffffu);
+        ix = bits != 0 ? 16 * c + __ffs(bits) - 1 : ix;
+    }
+    return min(ix, vocab - 1);
+}
 
 constexpr int TICK_MAX_LAYERS = 4;
 // the recurrent matrices of a free-running pass, in the order the kernels stream them: W_hh0, then per upper layer l its W_ih_l
@@ -155,7 +255,7 @@ __global__ __launch_bounds__(256) void tick_prep_kernel(TickPrep p, const float 
 // tile's sum is the prefix of its last note INSIDE the vocabulary, so that note's test is the expression that made S_c and the
 // tile's search ends on a note that exists; S_last >= u * S_last (u clamped to [0, 1]) ends the tiles'.
 template <int H, bool MASKED, int RW, int PICK>
-__global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, const uint4 *__restrict__ packed, TickSample smp) {
+__global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, const uint4 *__restrict__ packed, typename TickPick<PICK>::type smp) {
     static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
     constexpr int E = RW / 4;
     constexpr int NW = H / 16, KS = H / 32, KQ = H / 16;
@@ -173,6 +273,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     __shared__ int cand_i[4][16];
     __shared__ float smp_max[4][16];               // PICK_MULTINOMIAL: [tile][row] maximum, [tile][row][note] inclusive prefixes of e
     __shared__ float smp_pre[4][16][16];
+    __shared__ __attribute__((aligned(16))) float flt_lg[PICK == PICK_FILTERED ? 16 * FLT_LS : 4];   // PICK_FILTERED: [row] the logits
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
@@ -205,6 +306,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     const int note = 16 * w + col;
     const bool note_ok = w < ntile && note < p.vocab;
     const float bout = note_ok ? p.b_out[note] : 0.f;
+    bool note_on = note_ok;                                    // PICK_FILTERED: the note may be emitted
+    if constexpr (PICK == PICK_FILTERED) {
+        if (note_ok && smp.allow != nullptr) note_on = smp.allow[note] != 0;
+        for (int e = threadIdx.x; e < 16 * FLT_LS; e += H * 4) flt_lg[e] = -1.f;    // (columns past the last tile stay -1)
+    }
 
     auto lrow = [&](int i) { return gru_lrow<E>(quad, i); };                  // the tile row of this lane's element i
     int rows[E];
@@ -300,8 +406,8 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
             gi[i][0] = gb[i][0] + pt[0]; gi[i][1] = gb[i][1] + pt[H]; gi[i][2] = gb[i][2] + pt[2 * H];
             keep[i] = MASKED ? p.keep_scale * (float)p.mask[((int64_t)t * B + rows[i]) * H + unit] : 1.f;
         }
-        float un[E];                                           // this tick's draws of the lane's rows (PICK_MULTINOMIAL)
-        if constexpr (PICK == PICK_MULTINOMIAL) {
+        float un[E];                                           // this tick's draws of the lane's rows (PICK_MULTINOMIAL, PICK_FILTERED)
+        if constexpr (PICK != PICK_ARGMAX) {
 #pragma unroll
             for (int i = 0; i < E; ++i) un[i] = fminf(fmaxf(smp.u[(int64_t)rows[i] * ticks + t], 0.f), 1.f);
         }
@@ -397,6 +503,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                         }
                         return;
                     }
+                    if constexpr (PICK == PICK_FILTERED) {     // the row's logits to LDS; every lane ranks and draws behind the barrier
+#pragma unroll
+                        for (int i = 0; i < E; ++i) flt_lg[lrow(i) * FLT_LS + note] = note_on ? fmaxf(lv[i] + bout, 0.f) : -1.f;
+                        return;
+                    }
 #pragma unroll
                     for (int i = 0; i < E; ++i) { v[i] = note_ok ? fmaxf(lv[i] + bout, 0.f) : -1.f; ix[i] = note; }
 #pragma unroll
@@ -473,6 +584,13 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                 tok[i] = ix;
                 if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
             }
+        } else if constexpr (PICK == PICK_FILTERED) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const int ix = tick_filtered_pick(&flt_lg[lrow(i) * FLT_LS], col, quad, 16 * ntile, un[i], smp, p.vocab);
+                tok[i] = ix;
+                if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < E; ++i) {
@@ -529,7 +647,7 @@ struct TickStack {
 };
 
 template <int H, int L, int RW, int PICK>
-__global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p, const uint4 *__restrict__ packed, TickSample smp) {
+__global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p, const uint4 *__restrict__ packed, typename TickPick<PICK>::type smp) {
     static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
     static_assert(L >= 1 && L <= TICK_MAX_LAYERS, "layer count");
     constexpr int E = RW / 4;
@@ -548,6 +666,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
     __shared__ int cand_i[4][16];
     __shared__ float smp_max[4][16];
     __shared__ float smp_pre[4][16][16];
+    __shared__ __attribute__((aligned(16))) float flt_lg[PICK == PICK_FILTERED ? 16 * FLT_LS : 4];   // PICK_FILTERED: [row] the logits
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
@@ -586,6 +705,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
     const int note = 16 * w + col;
     const bool note_ok = w < ntile && note < p.vocab;
     const float bout = note_ok ? p.b_out[note] : 0.f;
+    bool note_on = note_ok;                                    // PICK_FILTERED: the note may be emitted
+    if constexpr (PICK == PICK_FILTERED) {
+        if (note_ok && smp.allow != nullptr) note_on = smp.allow[note] != 0;
+        for (int e = threadIdx.x; e < 16 * FLT_LS; e += H * 4) flt_lg[e] = -1.f;    // (columns past the last tile stay -1)
+    }
 
     auto lrow = [&](int i) { return gru_lrow<E>(quad, i); };
     int rows[E];
@@ -716,7 +840,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
             }
         }
         float un[E];
-        if constexpr (PICK == PICK_MULTINOMIAL) {
+        if constexpr (PICK != PICK_ARGMAX) {
 #pragma unroll
             for (int i = 0; i < E; ++i) un[i] = fminf(fmaxf(smp.u[(int64_t)rows[i] * ticks + t], 0.f), 1.f);
         }
@@ -769,6 +893,9 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
 #pragma unroll
                     for (int i = 0; i < E; ++i) smp_max[w][lrow(i)] = mx[i];
                 }
+            } else if constexpr (PICK == PICK_FILTERED) {      // the row's logits to LDS, banned notes as -1
+#pragma unroll
+                for (int i = 0; i < E; ++i) flt_lg[lrow(i) * FLT_LS + note] = note_on ? v[i] : -1.f;
             } else {
                 int ix[E];
 #pragma unroll
@@ -825,6 +952,13 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
                 const float ck = __builtin_fmaf(smp_pre[tile[i]][lrow(i)][col], scale[i], base[i]);
                 const unsigned long long reached = __ballot(ck >= target[i]);
                 const int ix = min(max(16 * tile[i] + __ffs((int)((unsigned)(reached >> (16 * quad)) & 0xffffu)) - 1, 0), p.vocab - 1);
+                tok[i] = ix;
+                if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
+            }
+        } else if constexpr (PICK == PICK_FILTERED) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const int ix = tick_filtered_pick(&flt_lg[lrow(i) * FLT_LS], col, quad, 16 * ntile, un[i], smp, p.vocab);
                 tok[i] = ix;
                 if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
             }
@@ -885,11 +1019,23 @@ static bool tick_h2_launch(const TickFreeRun &p, const TickPrep &tp, float *ws, 
     });
 }
 
-// uniforms null: the top-1 note is fed back; else a note drawn at uniforms [batch][ticks] from softmax(logits * inv_temperature)
+// PICK_FILTERED: generation runs with dropout off, so only the unmasked kernels exist
+template <int HH>
+static bool tick_h2_launch_filtered(const TickFreeRun &p, const TickPrep &tp, float *ws, int rw, const TickFilter &flt, hipStream_t st) {
+    const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
+    const dim3 gr((p.batch + rw - 1) / rw);
+    tick_prep_launch<HH>(tp, ws, st);
+    return with_int<4, 8, 16>(rw, [&](auto RW) {
+        ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, false, decltype(RW)::value, PICK_FILTERED>), gr, dim3(4 * HH), 0, st, p, packed, flt);
+    });
+}
+
+// uniforms null: the top-1 note is fed back; else a note drawn at uniforms [batch][ticks] from softmax(logits * inv_temperature), with
+// flt (its draws those of `uniforms`) over the notes the filter leaves
 static int tick_free_run_launch(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride, const float *gib,
                                 const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
                                 int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
-                                int64_t *tokens, float *ws, arvae_stream_t stream) {
+                                int64_t *tokens, float *ws, arvae_stream_t stream, const TickFilter *flt = nullptr) {
     ARVAE_REQUIRE(wts && h0_l0 && h0_l1 && gib && ptab && tokens, "tick_free_run: null pointer");
     ARVAE_REQUIRE(wts->w_hh0 && wts->b_hh0 && wts->w_ih1 && wts->b_ih1 && wts->w_hh1 && wts->b_hh1 && wts->w_out && wts->b_out,
                   "tick_free_run: null weight pointer");
@@ -912,7 +1058,8 @@ static int tick_free_run_launch(const arvae_tick_weights_t *wts, const float *h0
     const TickSample smp{uniforms, inv_temperature};
     bool rw_known = false;
     const bool h_known = with_int<128, 64, 32>(hidden, [&](auto HH) {
-        with_bool(mask != nullptr, [&](auto MM) { rw_known = tick_h2_launch<decltype(HH)::value, decltype(MM)::value>(p, tp, ws, rw, smp, st); });
+        if (flt != nullptr) rw_known = tick_h2_launch_filtered<decltype(HH)::value>(p, tp, ws, rw, *flt, st);
+        else with_bool(mask != nullptr, [&](auto MM) { rw_known = tick_h2_launch<decltype(HH)::value, decltype(MM)::value>(p, tp, ws, rw, smp, st); });
     });
     ARVAE_REQUIRE(h_known && rw_known, "tick_free_run: no kernel for hidden size %d at %d rows per workgroup", hidden, rw);
     return check_launch("tick_free_run_h2_kernel");
@@ -937,6 +1084,28 @@ extern "C" int arvae_tick_free_run_sampled(const arvae_tick_weights_t *wts, cons
                   "tick_free_run_sampled: inverse temperature %f is not a positive finite number", (double)inv_temperature);
     return tick_free_run_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, hidden, vocab,
                                 uniforms, inv_temperature, tokens, ws, stream);
+}
+
+extern "C" int arvae_tick_free_run_filtered(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                            const float *gib, const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch,
+                                            int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
+                                            float inv_temperature, const arvae_sample_filter_t *filter, int64_t *tokens, float *ws,
+                                            arvae_stream_t stream) {
+    int top_k = 0;
+    bool active = false;
+    if (const int rc = sample_filter_check("tick_free_run_filtered", filter, vocab, &top_k, &active)) return rc;
+    ARVAE_REQUIRE(uniforms != nullptr, "tick_free_run_filtered: null uniforms");
+    ARVAE_REQUIRE(mask == nullptr, "tick_free_run_filtered: a dropout keep-mask was given (generation runs with dropout off: the filtered "
+                                   "kernels are built without masks)");
+    if (!active)
+        return arvae_tick_free_run_sampled(wts, h0_l0, h0_l1, h0_stride, gib, ptab, nullptr, keep_scale, batch, beats, ticks_per_beat, hidden,
+                                           vocab, uniforms, inv_temperature, tokens, ws, stream);
+    ARVAE_REQUIRE(ws != nullptr, "tick_free_run_filtered: null workspace (arvae_tick_free_run_ws_floats)");
+    ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
+                  "tick_free_run_filtered: inverse temperature %f is not a positive finite number", (double)inv_temperature);
+    const TickFilter flt{uniforms, inv_temperature, top_k, filter->top_p, filter->allow};
+    return tick_free_run_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, nullptr, keep_scale, batch, beats, ticks_per_beat, hidden, vocab,
+                                uniforms, inv_temperature, tokens, ws, stream, &flt);
 }
 
 // ---- layer counts other than two (tick_free_run_layers_kernel) ----------------------------------------------------
@@ -968,10 +1137,20 @@ static bool tick_stack_launch(const TickStack &p, const TickPrep &tp, float *ws,
     });
 }
 
-extern "C" int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask,
-                                          float keep_scale, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
-                                          int32_t vocab, const float *uniforms, float inv_temperature, int64_t *tokens, float *ws,
-                                          arvae_stream_t stream) {
+template <int HH, int LL>
+static bool tick_stack_launch_filtered(const TickStack &p, const TickPrep &tp, float *ws, int rw, const TickFilter &flt, hipStream_t st) {
+    const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
+    const dim3 gr((p.batch + rw - 1) / rw);
+    tick_prep_launch<HH>(tp, ws, st);
+    return with_int<4, 8, 16>(rw, [&](auto RW) {
+        ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, decltype(RW)::value, PICK_FILTERED>), gr, dim3(4 * HH), 0, st, p, packed, flt);
+    });
+}
+
+// flt: PICK_FILTERED over its cuts (its draws those of `uniforms`), else the pick `uniforms` selects
+static int tick_layers_launch(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask, float keep_scale,
+                              int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
+                              float inv_temperature, int64_t *tokens, float *ws, arvae_stream_t stream, const TickFilter *flt) {
     ARVAE_REQUIRE(stack && gib && ptab && tokens, "tick_free_run_layers: null pointer");
     ARVAE_REQUIRE(ws != nullptr, "tick_free_run_layers: null workspace (arvae_tick_free_run_layers_ws_floats)");
     const int layers = stack->layers;
@@ -1016,10 +1195,34 @@ extern "C" int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const
         with_int<128, 64, 32>(hidden, [&](auto HH) {
             constexpr int H = decltype(HH)::value, L = decltype(LL)::value;
             // (hidden 128 with three or four layers is not built: arvae_tick_free_run_layers_supported)
-            if constexpr (H != 128 || L == 1) launched = tick_stack_launch<H, L>(p, tp, ws, rw, smp, st);
+            if constexpr (H != 128 || L == 1)
+                launched = flt != nullptr ? tick_stack_launch_filtered<H, L>(p, tp, ws, rw, *flt, st) : tick_stack_launch<H, L>(p, tp, ws, rw, smp, st);
         });
     });
     ARVAE_REQUIRE(launched, "tick_free_run_layers: no kernel for %d layers of hidden size %d at %d rows per workgroup", layers, hidden, rw);
     return check_launch("tick_free_run_layers_kernel");
+}
+
+extern "C" int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask,
+                                          float keep_scale, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
+                                          int32_t vocab, const float *uniforms, float inv_temperature, int64_t *tokens, float *ws,
+                                          arvae_stream_t stream) {
+    return tick_layers_launch(stack, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, hidden, vocab, uniforms, inv_temperature,
+                              tokens, ws, stream, nullptr);
+}
+
+extern "C" int arvae_tick_free_run_layers_filtered(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask,
+                                                   float keep_scale, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
+                                                   int32_t vocab, const float *uniforms, float inv_temperature,
+                                                   const arvae_sample_filter_t *filter, int64_t *tokens, float *ws, arvae_stream_t stream) {
+    int top_k = 0;
+    bool active = false;
+    if (const int rc = sample_filter_check("tick_free_run_layers_filtered", filter, vocab, &top_k, &active)) return rc;
+    ARVAE_REQUIRE(uniforms != nullptr, "tick_free_run_layers_filtered: null uniforms");
+    ARVAE_REQUIRE(mask == nullptr, "tick_free_run_layers_filtered: dropout keep-masks were given (generation runs with dropout off: the "
+                                   "filtered kernels are built without masks)");
+    const TickFilter flt{uniforms, inv_temperature, top_k, filter->top_p, filter->allow};
+    return tick_layers_launch(stack, gib, ptab, nullptr, keep_scale, batch, beats, ticks_per_beat, hidden, vocab, uniforms, inv_temperature,
+                              tokens, ws, stream, active ? &flt : nullptr);
 }
 

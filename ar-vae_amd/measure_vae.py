@@ -9,6 +9,8 @@ decoder gets its tokens from one more launch.  Any layer count >= 1 (nn.GRU(num_
 dropout between layers only); the two-layer stacks of the reference's defaults keep their own one-launch tick kernel.  Hidden sizes other than 32 / 64 / 128 (or ARVAE_GRU_STEPWISE=1) fall back
 to one launch per GRU cell and time step (csrc/sequence.hip + the dense kernels).  autograd only chains the launches.
 """
+import math
+import numbers
 import os
 from collections import deque
 
@@ -263,6 +265,24 @@ class Decoder(nn.Module):
                 nn.init.xavier_normal_(param)
 
 
+def check_sampling_cuts(top_k, top_p, vocab=None):
+    """the one place that knows the cuts' ranges (HierarchicalDecoder.sampling_filter, the command line): top_k None or an integer in
+    [1, vocab] (vocab None: no upper end known yet), top_p None or a number in (0, 1].  -> (top_k as int, top_p as float)"""
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
+            raise TypeError(f'top_k must be an integer, got {type(top_k).__name__}')
+        if top_k < 1 or (vocab is not None and top_k > vocab):
+            raise ValueError(f'top_k must lie in [1, {"the vocabulary" if vocab is None else vocab}], got {top_k}')
+        top_k = int(top_k)
+    if top_p is not None:
+        if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real):
+            raise TypeError(f'top_p must be a number, got {type(top_p).__name__}')
+        if not (math.isfinite(top_p) and 0.0 < top_p <= 1.0):
+            raise ValueError(f'top_p must lie in (0, 1], got {top_p}')
+        top_p = float(top_p)
+    return top_k, top_p
+
+
 class HierarchicalDecoder(Decoder):
     def __init__(self, note_embedding_dim, num_notes, z_dim, num_layers, rnn_hidden_size, dropout, rnn_class=nn.GRU):
         super().__init__(note_embedding_dim, num_notes, z_dim)
@@ -288,6 +308,7 @@ class HierarchicalDecoder(Decoder):
         self.xavier_initialization()
         self._mask_queue = deque()
         self._uniform_queue = deque()
+        self._filter = None                                    # (top_k, top_p, allowed on the device) while `generate` runs with cuts
 
     def __repr__(self):
         return f'{self.name}{self.note_embedding_dim},{self.rnn_class},{self.num_layers},{self.rnn_hidden_size},{self.dropout},)'
@@ -374,22 +395,56 @@ class HierarchicalDecoder(Decoder):
         beat_out = self.forward_beat_rnn(z, 4, masks[0])
         return self.forward_tick_rnn(score_tensor, beat_out, 6, teacher_forced, sampling, masks[1], uniforms)
 
-    def generate(self, z, sampling='multinomial', temperature=1.0, uniforms=None):
+    def sampling_filter(self, top_k=None, top_p=None, allowed=None):
+        """the cuts of `generate`, validated on the host: -> None when none is given, else (top_k or None, top_p or None, allowed as a
+        uint8 CPU tensor (V,) or None).  top_k: an int in [1, V]; top_p: a number in (0, 1]; allowed: a mask of V flags (bool or
+        0 / 1: tensor, array or sequence) with at least one note allowed."""
+        if top_k is None and top_p is None and allowed is None:
+            return None
+        v = self.num_notes
+        top_k, top_p = check_sampling_cuts(top_k, top_p, v)
+        if allowed is not None:
+            mask = torch.as_tensor(allowed).detach().cpu()
+            if mask.dtype == torch.bool:
+                mask = mask.to(torch.uint8)
+            if mask.dtype.is_floating_point or mask.dtype.is_complex:
+                raise TypeError(f'the allowed-note mask must hold flags (bool or 0 / 1 integers), got {mask.dtype}')
+            if tuple(mask.shape) != (v,):
+                raise ValueError(f'the allowed-note mask must have one flag per note of the vocabulary, shape ({v},), got {tuple(mask.shape)}')
+            if bool(((mask != 0) & (mask != 1)).any()):
+                raise ValueError('the allowed-note mask must hold flags (0 or 1)')
+            if not bool(mask.any()):
+                raise ValueError('the allowed-note mask allows no note of the vocabulary')
+            allowed = mask.to(torch.uint8).contiguous()
+        return top_k, top_p, allowed
+
+    def generate(self, z, sampling='multinomial', temperature=1.0, uniforms=None, top_k=None, top_p=None, allowed=None):
         """Free-running decode of latent codes z (B, z_dim) without autograd and with dropout off: -> (weights (B, 24, V), samples
         (B, 1, 24)).  sampling 'multinomial' draws every fed-back note from softmax(probs / temperature) (uniforms: explicit (B, 24)
-        draws in (0, 1], else one launch of the library's generator); 'argmax' feeds the top-1 note back."""
+        draws in (0, 1], else one launch of the library's generator); 'argmax' feeds the top-1 note back.
+        top_k / top_p / allowed (multinomial only; `sampling_filter`): the draw is over the notes that survive -- allowed[v] set, fewer
+        than top_k allowed notes ordered before v (descending logit, ties to the lower index), and those notes' share of the softmax
+        mass below top_p (the first note always survives); include/arvae_hip.h, arvae_sample_filter_t.  The returned weights are
+        the unfiltered logits."""
         if sampling not in ('argmax', 'multinomial'):
             raise NotImplementedError(f'sampling {sampling!r}: argmax and multinomial are implemented')
+        flt = self.sampling_filter(top_k, top_p, allowed)
+        if flt is not None and sampling != 'multinomial':
+            raise ValueError('top_k, top_p and allowed cut the multinomial draw: they need sampling=\'multinomial\'')
+        if flt is not None and flt[2] is not None:
+            flt = (flt[0], flt[1], flt[2].to(z.device))        # the one upload of the call
         dummy = torch.zeros(z.size(0), 24, dtype=torch.int64, device=z.device)
         saved = (self.sampling, self.temperature, self.use_teacher_forcing, self.training)
         self.sampling, self.temperature, self.use_teacher_forcing = sampling, float(temperature), False
         self.train(False)
+        self._filter = flt
         try:
             if uniforms is not None and sampling == 'multinomial':
                 self.push_sampling_uniforms(uniforms)
             with torch.no_grad():
                 return self.forward(z, dummy, sampling == 'multinomial')      # train=True is what lets `sampling` apply
         finally:
+            self._filter = None
             self.sampling, self.temperature, self.use_teacher_forcing = saved[:3]
             self.train(saved[3])
 
@@ -471,6 +526,9 @@ class HierarchicalDecoder(Decoder):
         stepwise = os.environ.get('ARVAE_TICK_STEPWISE', '0') == '1'
         one_launch = not stepwise and (ops.tick_free_run_supported(hid, self.num_notes) if layers == 2 else
                                        ops.tick_free_run_layers_supported(hid, self.num_notes, layers))
+        flt = self._filter if uniforms is not None else None   # `generate`'s cuts; dropout is off there: no keep-masks
+        if flt is not None and mask is not None:
+            raise RuntimeError('filtered sampling runs with dropout off')
         if one_launch:
             # one launch (csrc/tick_decoder.hip: tick_free_run_h2_kernel for two layers, tick_free_run_layers_kernel otherwise).  W_ih0
             # acts on [previous-note embedding | beat embedding]: the beat half is applied once per beat, the note half once per
@@ -485,10 +543,16 @@ class HierarchicalDecoder(Decoder):
             if layers == 2:
                 w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
                 weights = tuple(t.detach() for t in (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias))
+                if flt is not None:
+                    return ops.tick_free_run_filtered(weights, h0[0].detach(), h0[1].detach(), gib, ptab, b, nb, 6, uniforms,
+                                                      self.temperature, *flt)
                 return ops.tick_free_run(weights, h0[0].detach(), h0[1].detach(), gib, ptab,
                                          None if mask is None else mask[0].contiguous(), keep_scale, b, nb, 6,
                                          uniforms=uniforms, temperature=self.temperature)
             cells = [tuple(t.detach() for t in self.rnn_tick.cell(k)) for k in range(layers)]     # the boundaries' masks: (layers-1, 24, B, H)
+            if flt is not None:
+                return ops.tick_free_run_layers_filtered(cells, out.weight.detach(), out.bias.detach(), [s.detach() for s in h0], gib, ptab,
+                                                         b, nb, 6, uniforms, self.temperature, *flt)
             return ops.tick_free_run_layers(cells, out.weight.detach(), out.bias.detach(), [s.detach() for s in h0], gib, ptab,
                                             None if mask is None else torch.stack([k.contiguous() for k in mask], 0),
                                             keep_scale, b, nb, 6, uniforms=uniforms, temperature=self.temperature)
@@ -502,7 +566,10 @@ class HierarchicalDecoder(Decoder):
                 gi0 = ops.dense(ops.concat_cols(prev, be), w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
                 h = self._stack_step(self.rnn_tick, gi0, h, None if mask is None else [k[t].contiguous() for k in mask])
                 probs = _lin(h[-1], self.tick_emb_to_note_emb[0], ACT_RELU)
-                idx = ops.row_argmax(probs) if uniforms is None else ops.row_sample(probs, uniforms[:, t].contiguous(), self.temperature)
+                if flt is not None:
+                    idx = ops.row_sample_filtered(probs, uniforms[:, t].contiguous(), self.temperature, *flt)
+                else:
+                    idx = ops.row_argmax(probs) if uniforms is None else ops.row_sample(probs, uniforms[:, t].contiguous(), self.temperature)
                 prev = ops.embed(idx.view(b, 1), self.note_embedding_layer.weight).view(b, -1)
                 tokens.append(idx)
         return torch.stack(tokens, 1)
@@ -539,6 +606,8 @@ class HierarchicalDecoder(Decoder):
                 probs = _lin(h[-1], self.tick_emb_to_note_emb[0], ACT_RELU)
                 if self.use_teacher_forcing and teacher_forced:
                     idx = score_tensor[:, t].contiguous()
+                elif sampling == 'multinomial' and self._filter is not None:
+                    idx = ops.row_sample_filtered(probs.detach(), uniforms[:, t].contiguous(), self.temperature, *self._filter)
                 elif sampling == 'multinomial':
                     idx = ops.row_sample(probs.detach(), uniforms[:, t].contiguous(), self.temperature)
                 else:

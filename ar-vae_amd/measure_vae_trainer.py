@@ -19,6 +19,7 @@ MUSIC_REG_TYPE = {'rhy_complexity': 0, 'pitch_range': 1, 'note_density': 2, 'con
 # reference data/dataloaders/bar_dataset_helpers.py:21-30
 RHY_COMPLEXITY_COEFFS = [0.20, 1, 2, 0.5, 2, 1, 0.67, 1, 2, 0.5, 2, 1, 0.25, 1, 2, 0.5, 2, 1, 0.67, 1, 2, 0.5, 2, 1]
 _NON_NOTES = ('__', 'START', 'END', 'rest', None)
+_PADDING_SYMBOLS = ('START', 'END', None, 'None')        # vocabulary entries that are not music: never part of a playable measure
 _PITCH = {'C': 0, 'D': 2, 'E': 4, 'F': 5, 'G': 7, 'A': 9, 'B': 11}
 
 
@@ -269,28 +270,47 @@ class MeasureVAETrainer(Trainer):
             json.dump(self.metrics, f, indent=2)
         return self.metrics
 
-    def decode_latent_codes(self, latent_codes, sampling='argmax', temperature=1.0, uniforms=None):
+    def playable_mask(self, allowed=None):
+        """uint8 (V,) flags of the notes a generated measure may hold: every entry of the dataset's index dictionaries except the
+        padding symbols START, END and None (the slur '__' and 'rest' stay: they are music); an explicit `allowed` mask is
+        intersected with it."""
+        names = self.dataset.index2note_dicts
+        v = len(names)
+        mask = torch.tensor([0 if names[i] in _PADDING_SYMBOLS else 1 for i in range(v)], dtype=torch.uint8)
+        if allowed is not None:
+            mask = mask & self.model.decoder.sampling_filter(allowed=allowed)[2]
+        return mask
+
+    def decode_latent_codes(self, latent_codes, sampling='argmax', temperature=1.0, uniforms=None, top_k=None, top_p=None, allowed=None,
+                            playable=False):
         """(n, z_dim) latent codes -> (music21 score or None, note indices (n, 1, 24) int64): the decoder alone, free-running
         (measure_vae_trainer.py:281-288).  The score object needs the dataset's music21 converter (`tensor_to_m21score`);
         datasets without one (the device-resident loaders here) give None.  sampling='multinomial': every fed-back note is drawn
-        from softmax(probs / temperature) (HierarchicalDecoder.generate; uniforms: explicit (n, 24) draws) instead of the top-1."""
+        from softmax(probs / temperature) (HierarchicalDecoder.generate; uniforms: explicit (n, 24) draws) instead of the top-1;
+        top_k / top_p / allowed cut that draw (generate), playable=True keeps START, END and None out of it (playable_mask)."""
         dev = next(self.model.parameters()).device
         z = torch.as_tensor(latent_codes, dtype=torch.float32, device=dev).contiguous()
-        if sampling == 'argmax':
+        if playable:
+            allowed = self.playable_mask(allowed)
+        if sampling == 'argmax' and top_k is None and top_p is None and allowed is None:
             dummy = torch.zeros(z.size(0), self.model.num_ticks_per_measure, dtype=torch.int64, device=dev)
             with torch.no_grad():
                 _, tensor_score = self.model.decoder(z, dummy, False)
         else:
-            _, tensor_score = self.model.decoder.generate(z, sampling=sampling, temperature=temperature, uniforms=uniforms)
+            _, tensor_score = self.model.decoder.generate(z, sampling=sampling, temperature=temperature, uniforms=uniforms, top_k=top_k,
+                                                          top_p=top_p, allowed=allowed)
         to_score = getattr(self.dataset, 'tensor_to_m21score', None)
         return (to_score(tensor_score) if callable(to_score) else None), tensor_score
 
-    def sample_measures(self, num, temperature=1.0):
+    def sample_measures(self, num, temperature=1.0, top_k=None, top_p=None, allowed=None, playable=False):
         """num measures drawn from the model: z ~ N(0, I) from the library's generator, every note drawn from
-        softmax(probs / temperature).  -> (music21 score or None, note indices (num, 1, 24) int64)"""
+        softmax(probs / temperature) over the notes top_k / top_p / allowed / playable leave (decode_latent_codes).
+        -> (music21 score or None, note indices (num, 1, 24) int64)"""
         dev = next(self.model.parameters()).device
+        flt = (top_k, top_p, self.playable_mask(allowed) if playable else allowed)
+        self.model.decoder.sampling_filter(*flt)                # bad cuts are refused before a draw is made
         z = ops.normal_noise((int(num), self.model.latent_space_dim), dev)
-        return self.decode_latent_codes(z, sampling='multinomial', temperature=temperature)
+        return self.decode_latent_codes(z, sampling='multinomial', temperature=temperature, top_k=flt[0], top_p=flt[1], allowed=flt[2])
 
     def compute_latent_interpolations(self, latent_code, original_score=None, dim1=0, num_points=5):
         """Sweep latent dimension dim1 over [-4, 4] (measure_vae_trainer.py:290-308): all num_points codes are decoded in ONE

@@ -802,6 +802,37 @@ def tick_free_run_supported(hidden, vocab):
     return bool(_lib.load().arvae_tick_free_run_supported(int(hidden), int(vocab)))
 
 
+def sample_filter(vocab, top_k=None, top_p=None, allow=None):
+    """-> (_lib.SampleFilter, the tensors it points into) for arvae_*_filtered over rows of `vocab` notes: top_k None or 0 = off, top_p
+    None or 1 = off, allow None or a uint8 device tensor (vocab,) of the notes that may be emitted.  The ranges are the library's to
+    check (ARVAE_E_INVALID -> RuntimeError); HierarchicalDecoder.generate validates on the host first."""
+    if allow is not None:
+        if allow.dtype != torch.uint8 or tuple(allow.shape) != (vocab,):
+            raise ValueError(f'the allowed-note mask must be uint8 of shape ({vocab},), got {allow.dtype} {tuple(allow.shape)}')
+        _dev(allow)
+        allow = allow.contiguous()
+    return _lib.SampleFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p), _ptr(allow)), allow
+
+
+def tick_free_run_filtered(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, uniforms, temperature=1.0, top_k=None,
+                           top_p=None, allow=None):
+    """tick_free_run's sampled pass over the notes a top-k cut, a nucleus cut and a note mask leave (arvae_tick_free_run_filtered;
+    the semantics: include/arvae_hip.h, arvae_sample_filter_t).  No keep-masks: generation runs with dropout off."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab, uniforms)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    flt, allow = sample_filter(vocab, top_k, top_p, allow)
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    tokens = torch.empty(batch, beats * ticks_per_beat, device=gib.device, dtype=torch.int64)
+    ws = torch.empty(lib.arvae_tick_free_run_ws_floats(hid), device=gib.device, dtype=torch.float32)
+    u = _sampling_uniforms(uniforms, (batch, beats * ticks_per_beat))
+    with _timed('tick_free_run_filtered', 2.0 * batch * beats * ticks_per_beat * (9 * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_free_run_filtered(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), None, 1.0, batch,
+                                                    beats, ticks_per_beat, hid, vocab, _ptr(u), 1.0 / float(temperature),
+                                                    ctypes.byref(flt), _ptr(tokens), _ptr(ws), _stream()), 'tick_free_run_filtered')
+    return tokens
+
+
 def tick_free_run(weights, h0_l0, h0_l1, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, uniforms=None, temperature=1.0):
     """tokens (B, beats*ticks_per_beat) int64 of the free-running tick decoder; no autograd (csrc/tick_decoder.hip).
     weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, w_out, b_out).
@@ -833,33 +864,59 @@ def tick_free_run_layers_supported(hidden, vocab, layers):
     return bool(_lib.load().arvae_tick_free_run_layers_supported(int(hidden), int(vocab), int(layers)))
 
 
-def tick_free_run_layers(cells, w_out, b_out, h0, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, uniforms=None,
-                         temperature=1.0):
-    """tick_free_run for a GRU stack of len(cells) layers (arvae_tick_free_run_layers): cells[l] = (w_ih, w_hh, b_ih, b_hh) of layer l
-    (layer 0's input weights are not read: gib / ptab hold their products), h0 = the layers' initial states (beats*B, H) each,
-    mask None or uint8 (layers-1, beats*ticks_per_beat, B, H), one keep-mask per layer boundary."""
+def _tick_stack(cells, w_out, b_out, h0, gib, ptab, batch, ticks):
+    """-> (_lib.TickStack of a GRU stack, the contiguous initial states it points into, tokens, workspace) for the layers calls"""
     layers = len(cells)
     if len(h0) != layers or layers > _lib.TICK_MAX_LAYERS:
         raise ValueError(f'{layers} layers need {layers} initial states (at most {_lib.TICK_MAX_LAYERS} layers)')
     h0 = [s.contiguous() for s in h0]
-    _dev(*[t for c in cells for t in c], w_out, b_out, *h0, gib, ptab, mask, uniforms)
-    lib = _lib.load()
-    hid, vocab, ticks = cells[0][1].shape[1], w_out.shape[0], beats * ticks_per_beat
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (layers - 1, ticks, batch, hid)):
-        raise ValueError(f'keep-masks must be uint8 of shape {(layers - 1, ticks, batch, hid)}, got {mask.dtype} {tuple(mask.shape)}')
+    _dev(*[t for c in cells for t in c], w_out, b_out, *h0, gib, ptab)
+    hid = cells[0][1].shape[1]
     ts = _lib.TickStack()
     ts.layers = layers
     for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(cells):
         ts.w_ih[l], ts.w_hh[l], ts.b_ih[l], ts.b_hh[l], ts.h0[l] = _ptr(w_ih), _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(h0[l])
     ts.w_out, ts.b_out, ts.h0_stride = _ptr(w_out), _ptr(b_out), 0
     tokens = torch.empty(batch, ticks, device=gib.device, dtype=torch.int64)
-    ws = torch.empty(lib.arvae_tick_free_run_layers_ws_floats(hid, layers), device=gib.device, dtype=torch.float32)
+    ws = torch.empty(_lib.load().arvae_tick_free_run_layers_ws_floats(hid, layers), device=gib.device, dtype=torch.float32)
+    return ts, h0, tokens, ws
+
+
+def tick_free_run_layers(cells, w_out, b_out, h0, gib, ptab, mask, keep_scale, batch, beats, ticks_per_beat, uniforms=None,
+                         temperature=1.0):
+    """tick_free_run for a GRU stack of len(cells) layers (arvae_tick_free_run_layers): cells[l] = (w_ih, w_hh, b_ih, b_hh) of layer l
+    (layer 0's input weights are not read: gib / ptab hold their products), h0 = the layers' initial states (beats*B, H) each,
+    mask None or uint8 (layers-1, beats*ticks_per_beat, B, H), one keep-mask per layer boundary."""
+    layers, ticks = len(cells), beats * ticks_per_beat
+    ts, h0, tokens, ws = _tick_stack(cells, w_out, b_out, h0, gib, ptab, batch, ticks)
+    _dev(mask, uniforms)
+    lib = _lib.load()
+    hid, vocab = cells[0][1].shape[1], w_out.shape[0]
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (layers - 1, ticks, batch, hid)):
+        raise ValueError(f'keep-masks must be uint8 of shape {(layers - 1, ticks, batch, hid)}, got {mask.dtype} {tuple(mask.shape)}')
     u = None if uniforms is None else _sampling_uniforms(uniforms, (batch, ticks))
     mask = None if mask is None else mask.contiguous()
     with _timed('tick_free_run_layers', 2.0 * batch * ticks * (3 * (2 * layers - 1) * hid * hid + vocab * hid), 0.0):
         _lib.check(lib.arvae_tick_free_run_layers(ctypes.byref(ts), _ptr(gib), _ptr(ptab), _ptr(mask), float(keep_scale), batch, beats,
                                                   ticks_per_beat, hid, vocab, _ptr(u), 1.0 / float(temperature), _ptr(tokens),
                                                   _ptr(ws), _stream()), 'tick_free_run_layers')
+    return tokens
+
+
+def tick_free_run_layers_filtered(cells, w_out, b_out, h0, gib, ptab, batch, beats, ticks_per_beat, uniforms, temperature=1.0, top_k=None,
+                                  top_p=None, allow=None):
+    """tick_free_run_filtered for a GRU stack of 1, 3 or 4 layers (arvae_tick_free_run_layers_filtered).  No keep-masks."""
+    layers, ticks = len(cells), beats * ticks_per_beat
+    ts, h0, tokens, ws = _tick_stack(cells, w_out, b_out, h0, gib, ptab, batch, ticks)
+    _dev(uniforms)
+    lib = _lib.load()
+    hid, vocab = cells[0][1].shape[1], w_out.shape[0]
+    flt, allow = sample_filter(vocab, top_k, top_p, allow)
+    u = _sampling_uniforms(uniforms, (batch, ticks))
+    with _timed('tick_free_run_layers_filtered', 2.0 * batch * ticks * (3 * (2 * layers - 1) * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_free_run_layers_filtered(ctypes.byref(ts), _ptr(gib), _ptr(ptab), None, 1.0, batch, beats, ticks_per_beat,
+                                                           hid, vocab, _ptr(u), 1.0 / float(temperature), ctypes.byref(flt),
+                                                           _ptr(tokens), _ptr(ws), _stream()), 'tick_free_run_layers_filtered')
     return tokens
 
 
@@ -999,6 +1056,20 @@ def row_sample(w, u, temperature=1.0):
     idx = torch.empty(w.shape[0], device=w.device, dtype=torch.int64)
     _lib.check(lib.arvae_row_sample(_ptr(w), w.shape[0], w.shape[1], _ptr(u), 1.0 / float(temperature), _ptr(idx), _stream()),
                'row_sample')
+    return idx
+
+
+def row_sample_filtered(w, u, temperature=1.0, top_k=None, top_p=None, allow=None):
+    """row_sample over the notes a top-k cut, a nucleus cut and a note mask leave (arvae_row_sample_filtered; the semantics:
+    include/arvae_hip.h, arvae_sample_filter_t): top_k None or 0 = off, top_p None or 1 = off, allow None or uint8 (cols,)."""
+    _dev(w, u)
+    lib = _lib.load()
+    w = w.contiguous()
+    u = _sampling_uniforms(u, (w.shape[0],))
+    flt, allow = sample_filter(w.shape[1], top_k, top_p, allow)
+    idx = torch.empty(w.shape[0], device=w.device, dtype=torch.int64)
+    _lib.check(lib.arvae_row_sample_filtered(_ptr(w), w.shape[0], w.shape[1], _ptr(u), 1.0 / float(temperature), ctypes.byref(flt),
+                                             _ptr(idx), _stream()), 'row_sample_filtered')
     return idx
 
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 16  /* 16: arvae_resnet18_* (inference of the Morpho-MNIST ResNet-18 digit classifier: digit_pred_acc of imagevae/image_vae_trainer.py:319-368); 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 16  /* 16: arvae_resnet18_* (inference of the Morpho-MNIST ResNet-18 digit classifier: digit_pred_acc of imagevae/image_vae_trainer.py:319-368), and, added without a new number (symbols only), arvae_sample_filter_t, arvae_row_sample_filtered, arvae_tick_free_run_filtered, arvae_tick_free_run_layers_filtered (top-k, nucleus and note-mask sampling of the free-running decoder); 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -388,6 +388,42 @@ int arvae_row_argmax(const float *w, int32_t rows, int32_t cols, int64_t *idx, a
  * k with C_k >= u[r] * C_{cols-1}.  Any cols >= 1; inv_temperature finite and > 0. */
 int arvae_row_sample(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature, int64_t *idx,
                      arvae_stream_t stream);
+
+
+/* Filtered sampling of the free-running decoder (generation; beyond the reference): a top-k cut, a nucleus (top-p) cut and a mask of
+ * the notes that may be emitted, one definition for the three entry points below.  Per row, with logits l_v (the tick kernels':
+ * relu(W_out h + b_out)_v) and T = 1 / inv_temperature:
+ *   allowed set A: allow[v] != 0 (allow: DEVICE pointer to vocab bytes; NULL = every note);
+ *   order: the allowed notes by descending l, ties to the lower index (the argmax pick's rule); rank(v) = v's position in it;
+ *   top_k in [1, vocab], 0 = off: v survives iff rank(v) < top_k;
+ *   e_v = exp((l_v - max_A l) / T), S = the sum of e over the allowed notes that survive top_k;
+ *   top_p in (0, 1], 1 = off: v survives iff mass_before(v) < top_p, mass_before(v) = (the sum of e_u over the notes ordered before
+ *   v) / S; the first note of the order always survives;
+ *   draw: arvae_tick_free_run_sampled's over the survivors in index order: C_k the running sum of e, the note is the smallest
+ *   surviving k with C_k >= u * C_last.
+ * A token in [0, vocab) comes back for ANY input, a mask that allows nothing included (note 0 then): "in range, no fault"; callers
+ * reject such a mask themselves.  ARVAE_E_INVALID with a message: top_k outside [0, vocab], top_p not in (0, 1] or not finite, null
+ * uniforms, and for the tick calls a dropout keep-mask (generation runs with dropout off: the filtered kernels are built without
+ * masks).  With no filter active (top_k 0 or vocab, top_p 1, allow NULL) the calls forward to arvae_row_sample /
+ * arvae_tick_free_run_sampled / arvae_tick_free_run_layers: the same tokens bit for bit.  Shapes: those of
+ * arvae_tick_free_run_supported / arvae_tick_free_run_layers_supported; arvae_row_sample_filtered takes any cols >= 1 (top_k against
+ * cols).  Every other argument as in the unfiltered call. */
+typedef struct arvae_sample_filter {
+    int32_t top_k;          /* 0 = off */
+    float top_p;            /* 1 = off */
+    const uint8_t *allow;   /* device, [vocab] bytes; NULL = every note */
+} arvae_sample_filter_t;
+int arvae_row_sample_filtered(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature,
+                              const arvae_sample_filter_t *filter, int64_t *idx, arvae_stream_t stream);
+int arvae_tick_free_run_filtered(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1, int64_t h0_stride /* 0 = hidden */,
+                                 const float *gib, const float *ptab, const uint8_t *mask /* must be NULL */, float keep_scale, int32_t batch,
+                                 int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
+                                 float inv_temperature, const arvae_sample_filter_t *filter, int64_t *tokens, float *ws,
+                                 arvae_stream_t stream);
+int arvae_tick_free_run_layers_filtered(const arvae_tick_stack_t *stack, const float *gib, const float *ptab,
+                                        const uint8_t *mask /* must be NULL */, float keep_scale, int32_t batch, int32_t beats,
+                                        int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
+                                        const arvae_sample_filter_t *filter, int64_t *tokens, float *ws, arvae_stream_t stream);
 
 /* out[r] = [a[r] | b[r]] (torch.cat along dim 1/2, decoder.py:503) and its adjoint (db optionally accumulated) */
 int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,

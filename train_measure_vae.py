@@ -2,8 +2,9 @@
 """Train / evaluate the MeasureVAE on MI355X: counterpart of the reference's train_measure_vae.py (same flags and
 defaults).  Only the `folk` one-bar dataset in its pre-built tensor form is supported (arvae_amd.data.FolkNBarDataset):
 building it from ABC files with music21, and the `bach` chorales, are offline steps outside this build.  `--metrics` adds the
-reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary; `--sample N [--temperature T]` adds N measures
-drawn from the model (z from the prior, every note from softmax(probs / T)) as lists of note names."""
+reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary; `--sample N [--temperature T] [--top_k K]
+[--top_p P] [--playable]` adds N measures drawn from the model (z from the prior, every note from softmax(probs / T) over the notes a
+top-k cut, a nucleus cut and the playable-note mask leave) as lists of note names."""
 import json
 import os
 import sys
@@ -15,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from arvae_amd.evaluation import eval_metrics_or_warn  # noqa: E402
 from arvae_amd.data import FolkNBarDataset  # noqa: E402
-from arvae_amd.measure_vae import MeasureVAE  # noqa: E402
+from arvae_amd.measure_vae import MeasureVAE, check_sampling_cuts  # noqa: E402
 from arvae_amd.measure_vae_trainer import MUSIC_REG_TYPE, MeasureVAETrainer  # noqa: E402
 
 
@@ -60,9 +61,12 @@ METRICS_HELP = (f'{METRICS_FLAG}: add the disentanglement metrics (Interpretabil
 with_metrics = False
 # likewise opt-in and outside the reference's flags: measures drawn from the evaluated model (MeasureVAETrainer.sample_measures)
 SAMPLE_FLAG, TEMPERATURE_FLAG = '--sample', '--temperature'
-SAMPLE_HELP = (f'{SAMPLE_FLAG} N [{TEMPERATURE_FLAG} T]: add `samples` to the evaluation summary, N measures drawn from the model '
-               '(z from the prior, every note from softmax(probs / T), T = 1 by default) as 24 note names each.')
-num_samples, temperature = 0, 1.0
+TOP_K_FLAG, TOP_P_FLAG, PLAYABLE_FLAG = '--top_k', '--top_p', '--playable'
+SAMPLE_HELP = (f'{SAMPLE_FLAG} N [{TEMPERATURE_FLAG} T] [{TOP_K_FLAG} K] [{TOP_P_FLAG} P] [{PLAYABLE_FLAG}]: add `samples` to the '
+               'evaluation summary, N measures drawn from the model (z from the prior, every note from softmax(probs / T), T = 1 by '
+               'default) as 24 note names each; K keeps the K most likely notes, P the most likely notes up to a share P of the mass, '
+               f'{PLAYABLE_FLAG} keeps START, END and None out.  These three are echoed as `sampling`.')
+num_samples, temperature, top_k, top_p, playable = 0, 1.0, None, None, False
 
 
 def with_options(fn):
@@ -142,7 +146,9 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         if num_samples > 0:
             trainer.cuda()
             model.eval()
-            _, notes = trainer.sample_measures(num_samples, temperature)
+            _, notes = trainer.sample_measures(num_samples, temperature, top_k=top_k, top_p=top_p, playable=playable)
+            if top_k is not None or top_p is not None or playable:          # the cuts are echoed beside the measures they shaped
+                summary['sampling'] = {'temperature': temperature, 'top_k': top_k, 'top_p': top_p, 'playable': playable}
             summary['samples'] = [[dataset.index2note_dicts[int(i)] for i in row] for row in notes.squeeze(1).tolist()]
         print(json.dumps(summary, indent=2))
 
@@ -165,15 +171,20 @@ def _take_value(argv, flag, cast, default):
 
 
 def run(argv=None):
-    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample and --temperature"""
-    global with_metrics, num_samples, temperature
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p
+    and --playable.  Values of --top_k / --top_p outside their ranges raise the decoder's ValueError (sampling_filter)."""
+    global with_metrics, num_samples, temperature, top_k, top_p, playable
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
+    playable = PLAYABLE_FLAG in argv
     num_samples, argv = _take_value(argv, SAMPLE_FLAG, int, 0)
     temperature, argv = _take_value(argv, TEMPERATURE_FLAG, float, 1.0)
+    top_k, argv = _take_value(argv, TOP_K_FLAG, int, None)
+    top_p, argv = _take_value(argv, TOP_P_FLAG, float, None)
     if num_samples < 0 or not temperature > 0:
         raise SystemExit(f'{SAMPLE_FLAG} takes a count >= 0 and {TEMPERATURE_FLAG} a positive number')
-    main(args=[a for a in argv if a != METRICS_FLAG])
+    check_sampling_cuts(top_k, top_p)          # the decoder's own ValueError, before anything is loaded or trained
+    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG)])
 
 
 if __name__ == '__main__':
