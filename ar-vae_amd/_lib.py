@@ -176,6 +176,12 @@ SIGNATURES = {
     'arvae_row_argmax': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     'arvae_row_sample': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     'arvae_row_sample_filtered': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, _P(SampleFilter), c_vp, c_vp]),
+    'arvae_beam_select': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_sequence_log_prob': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'arvae_tick_beam_search_supported': (c_i32, [c_i32, c_i32, c_i32]),
+    'arvae_tick_beam_search_ws_floats': (c_i64, [c_i32]),
+    'arvae_tick_beam_search': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'arvae_concat_cols': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     'arvae_split_cols': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     'arvae_scale_mask': (c_i32, [c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp]),

@@ -448,6 +448,114 @@ class HierarchicalDecoder(Decoder):
             self.sampling, self.temperature, self.use_teacher_forcing = saved[:3]
             self.train(saved[3])
 
+    # ---- beam search ---------------------------------------------------------------------------------------------
+    def _beam_mask(self, beam_width, allowed, device):
+        """beam_search's arguments, validated on the host -> (W, the mask uint8 (V,) on `device` or None, the notes it allows)"""
+        if isinstance(beam_width, bool) or not isinstance(beam_width, numbers.Integral):
+            raise TypeError(f'beam_width must be an integer, got {type(beam_width).__name__}')
+        if not 1 <= beam_width <= 16:
+            raise ValueError(f'beam_width must lie in [1, 16], got {beam_width}')
+        flt = self.sampling_filter(None, None, allowed)
+        mask = None if flt is None else flt[2]
+        count = self.num_notes if mask is None else int(mask.count_nonzero())
+        if beam_width > count:
+            raise ValueError(f'beam_width {beam_width} is above the {count} allowed notes: fewer distinct hypotheses exist after the first tick')
+        return int(beam_width), (None if mask is None else mask.to(device)), count
+
+    def _eval_no_grad(self, fn):
+        """fn() without autograd, with dropout off and teacher forcing on, the decoder's state put back afterwards (as `generate`)"""
+        saved = (self.use_teacher_forcing, self.training)
+        self.use_teacher_forcing = True
+        self.train(False)
+        try:
+            with torch.no_grad():
+                return fn()
+        finally:
+            self.use_teacher_forcing = saved[0]
+            self.train(saved[1])
+
+    def _beats(self, z):
+        """-> the beat RNN's outputs (4, B, H)"""
+        if _use_sequence_kernels(self.rnn_hidden_size):
+            return self.beat_rnn_sequence(z, 4, None)
+        return torch.stack(self.forward_beat_rnn(z, 4, None), 0)
+
+    def _teacher_forced_weights(self, beat_out, tokens):
+        """the logits (B, 24, V) of the decoder fed `tokens` (B, 24): the existing teacher-forced path"""
+        if _use_sequence_kernels(self.rnn_hidden_size):
+            return self.tick_rnn_sequence(tokens, beat_out, 6, True)[0]
+        return self.forward_tick_rnn(tokens, list(torch.unbind(beat_out, 0)), 6, True, 'argmax')[0]
+
+    def _beam_history(self, beat_out, width, mask, count):
+        """-> (parents (B, 24, W) int32, tokens (B, 24, W) int64, scores (B, 24, W), sequences (B, W, 24) int64, scores (B, W)): one
+        launch (csrc/beam_decoder.hip, tick_beam_search_kernel) where it is offered, else tick by tick with the existing dense and
+        gate launches, ops.beam_select and a gather of the states (ARVAE_TICK_STEPWISE=1, other layer counts, hidden sizes, V > 64)."""
+        nb, b, hid = beat_out.shape
+        layers, vocab = self.num_layers, self.num_notes
+        h0, beat_emb = self._tick_restart(beat_out.reshape(nb * b, hid))
+        w_ih0, w_hh0, b_ih0, b_hh0 = self.rnn_tick.cell(0)
+        out = self.tick_emb_to_note_emb[0]
+        stepwise = os.environ.get('ARVAE_TICK_STEPWISE', '0') == '1'
+        if not stepwise and layers == 2 and ops.tick_beam_search_supported(hid, vocab, width):
+            emb_dim = self.note_embedding_dim
+            w_note, w_beat = w_ih0[:, :emb_dim].contiguous(), w_ih0[:, emb_dim:].contiguous()
+            gib = ops.dense(beat_emb, w_beat, b_ih0, Link.dense(hid, 3 * hid), ACT_NONE)
+            table = torch.cat((self.note_embedding_layer.weight, self.x_0[None]), 0)
+            ptab = ops.dense(table, w_note, None, Link.dense(emb_dim, 3 * hid), ACT_NONE)
+            w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
+            weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias)
+            return ops.tick_beam_search(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, mask, count)
+        dev = beat_out.device
+        rows = torch.arange(b, device=dev).repeat_interleave(width)               # row (code, k) -> code
+        base = (torch.arange(b, device=dev) * width)[:, None]
+        prev = self.x_0[None].expand(b * width, -1).contiguous()
+        scores = torch.zeros(b, width, device=dev)
+        parents, tokens, hist = [], [], []
+        for i in range(nb):
+            h = [s[i * b:(i + 1) * b].index_select(0, rows) for s in h0]
+            be = beat_emb[i * b:(i + 1) * b].index_select(0, rows)
+            for j in range(6):
+                gi0 = ops.dense(ops.concat_cols(prev, be), w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
+                h = self._stack_step(self.rnn_tick, gi0, h, None)
+                probs = _lin(h[-1], out, ACT_RELU)
+                par, note, scores = ops.beam_select(probs, scores, 1 if i == 0 and j == 0 else width, mask, count)
+                src = (base + par.to(torch.int64)).reshape(-1)
+                h = [s.index_select(0, src) for s in h]
+                prev = ops.embed(note.view(b * width, 1), self.note_embedding_layer.weight).view(b * width, -1)
+                parents.append(par), tokens.append(note), hist.append(scores)
+        parents, tokens, hist = torch.stack(parents, 1), torch.stack(tokens, 1), torch.stack(hist, 1)
+        at = torch.arange(width, device=dev)[None].expand(b, -1)
+        seq = []
+        for t in range(nb * 6 - 1, -1, -1):                                       # backtracking: a gather per tick
+            seq.append(tokens[:, t].gather(1, at))
+            at = parents[:, t].to(torch.int64).gather(1, at)
+        return parents, tokens, hist, torch.stack(seq[::-1], 2), scores
+
+    def beam_search(self, z, beam_width=4, allowed=None, return_history=False):
+        """The beam_width most likely measures of latent codes z (B, z_dim) under the decoder, without autograd and with dropout off
+        (include/arvae_hip.h, "Beam search"): -> (weights (B, 24, V), samples (B, 1, 24), scores (B,)) of the best beam -- the weights
+        from the whole-sequence kernels evaluated on its tokens --, sequences (B, W, 24) best first and scores (B, W) = their
+        log p(x | z) over the allowed notes; return_history=True: also (parents (B, 24, W) int32, tokens (B, 24, W), scores (B, 24, W)).
+        allowed: a mask of V flags (`sampling_filter`), at least beam_width of them set."""
+        width, mask, count = self._beam_mask(beam_width, allowed, z.device)
+
+        def run():
+            beat_out = self._beats(z)
+            parents, tokens, hist, seqs, scores = self._beam_history(beat_out, width, mask, count)
+            best = seqs[:, 0].contiguous()
+            weights = self._teacher_forced_weights(beat_out, best)
+            res = (weights, best[:, None, :], scores[:, 0].contiguous(), seqs, scores)
+            return res + ((parents, tokens, hist),) if return_history else res
+        return self._eval_no_grad(run)
+
+    def score_tokens(self, z, tokens, allowed=None):
+        """log p(tokens | z) (B,) under teacher forcing, the softmax over the allowed notes (ops.sequence_log_prob on the
+        whole-sequence kernels' weights); tokens (B, 24) or (B, 1, 24) int64.  Without autograd, dropout off."""
+        flt = self.sampling_filter(None, None, allowed)
+        mask = None if flt is None else flt[2].to(z.device)
+        tokens = torch.as_tensor(tokens, device=z.device).reshape(z.size(0), 24).to(torch.int64).contiguous()
+        return self._eval_no_grad(lambda: ops.sequence_log_prob(self._teacher_forced_weights(self._beats(z), tokens).contiguous(), tokens, mask))
+
     # ---- whole-sequence path ------------------------------------------------------------------------------------
     def _stack_sequence(self, rnn, steps, gi0, h0, masks):
         """unidirectional GRU stack over `steps`: gi0 (T, R, 3H) or (R, 3H); h0 = the layers' initial states; masks = per boundary a
@@ -474,6 +582,16 @@ class HierarchicalDecoder(Decoder):
         m = None if mask is None else [k.contiguous().view(seq_len * b, -1) for k in mask]
         return self._stack_sequence(self.rnn_beat, seq_len, gi0, h, m)
 
+    def _tick_restart(self, bo):
+        """beat outputs (4B, H) -> (the tick RNN's initial states per layer, (4B, H) each; the beat embeddings (4B, H))"""
+        hid = self.rnn_hidden_size
+        la, lb = self.beat_emb_to_tick_rnn_hidden[0], self.beat_emb_to_tick_rnn_input[0]
+        both = ops.dense_pair(bo, la.weight, la.bias, lb.weight, lb.bias, ACT_SELU)           # (4B, L H + H) or None
+        if both is not None:
+            flat, beat_emb = ops.split_cols(both, la.weight.shape[0])
+            return _split_layers(flat, hid, self.num_layers), beat_emb
+        return self.hidden_init(bo, 'tick'), _lin(bo, lb, ACT_SELU)
+
     def tick_rnn_sequence(self, score_tensor, beat_out, tick_seq_len, teacher_forced, mask=None, uniforms=None):
         """The tick RNN restarts from a beat-dependent hidden state at every beat (decoder.py:459-525), so given the
         fed-back tokens the four beats are independent 6-step sequences: they run as ONE sequence launch per layer over
@@ -483,15 +601,7 @@ class HierarchicalDecoder(Decoder):
         nb, b = beat_out.shape[0], beat_out.shape[1]
         hid, steps = self.rnn_hidden_size, tick_seq_len
         ticks = nb * steps
-        bo = beat_out.view(nb * b, hid)
-        la, lb = self.beat_emb_to_tick_rnn_hidden[0], self.beat_emb_to_tick_rnn_input[0]
-        both = ops.dense_pair(bo, la.weight, la.bias, lb.weight, lb.bias, ACT_SELU)           # (4B, L H + H) or None
-        if both is not None:
-            flat, beat_emb = ops.split_cols(both, la.weight.shape[0])
-            h0 = _split_layers(flat, hid, self.num_layers)
-        else:
-            h0 = self.hidden_init(bo, 'tick')
-            beat_emb = _lin(bo, lb, ACT_SELU)                                                  # (4B, H)
+        h0, beat_emb = self._tick_restart(beat_out.view(nb * b, hid))
         m = None
         if mask is not None:                                                                   # per boundary (24, B, H) -> rows (j, beat, b)
             m = [k.view(nb, steps, b, hid).transpose(0, 1).contiguous().view(steps * nb * b, hid) for k in mask]

@@ -282,16 +282,27 @@ class MeasureVAETrainer(Trainer):
         return mask
 
     def decode_latent_codes(self, latent_codes, sampling='argmax', temperature=1.0, uniforms=None, top_k=None, top_p=None, allowed=None,
-                            playable=False):
+                            playable=False, beam_width=4):
         """(n, z_dim) latent codes -> (music21 score or None, note indices (n, 1, 24) int64): the decoder alone, free-running
         (measure_vae_trainer.py:281-288).  The score object needs the dataset's music21 converter (`tensor_to_m21score`);
         datasets without one (the device-resident loaders here) give None.  sampling='multinomial': every fed-back note is drawn
         from softmax(probs / temperature) (HierarchicalDecoder.generate; uniforms: explicit (n, 24) draws) instead of the top-1;
-        top_k / top_p / allowed cut that draw (generate), playable=True keeps START, END and None out of it (playable_mask)."""
+        top_k / top_p / allowed cut that draw (generate), playable=True keeps START, END and None out of it (playable_mask).
+        sampling='beam': the most likely measure of every code among beam_width beams over the allowed / playable notes
+        (HierarchicalDecoder.beam_search); nothing is drawn, so top_k, top_p, temperature and uniforms are refused with it."""
         dev = next(self.model.parameters()).device
         z = torch.as_tensor(latent_codes, dtype=torch.float32, device=dev).contiguous()
+        if sampling == 'beam':
+            given = [n for n, on in (('top_k', top_k is not None), ('top_p', top_p is not None), ('temperature', temperature != 1.0),
+                                     ('uniforms', uniforms is not None)) if on]
+            if given:
+                raise ValueError(f"sampling='beam' draws nothing: {', '.join(given)} cannot be combined with it")
         if playable:
             allowed = self.playable_mask(allowed)
+        if sampling == 'beam':
+            tensor_score = self.model.decoder.beam_search(z, beam_width=beam_width, allowed=allowed)[1]
+            to_score = getattr(self.dataset, 'tensor_to_m21score', None)
+            return (to_score(tensor_score) if callable(to_score) else None), tensor_score
         if sampling == 'argmax' and top_k is None and top_p is None and allowed is None:
             dummy = torch.zeros(z.size(0), self.model.num_ticks_per_measure, dtype=torch.int64, device=dev)
             with torch.no_grad():
@@ -302,11 +313,19 @@ class MeasureVAETrainer(Trainer):
         to_score = getattr(self.dataset, 'tensor_to_m21score', None)
         return (to_score(tensor_score) if callable(to_score) else None), tensor_score
 
-    def sample_measures(self, num, temperature=1.0, top_k=None, top_p=None, allowed=None, playable=False):
+    def sample_measures(self, num, temperature=1.0, top_k=None, top_p=None, allowed=None, playable=False, beam_width=None):
         """num measures drawn from the model: z ~ N(0, I) from the library's generator, every note drawn from
         softmax(probs / temperature) over the notes top_k / top_p / allowed / playable leave (decode_latent_codes).
+        beam_width W: the prior draws are decoded by beam search instead (sampling='beam'; no note is drawn).
         -> (music21 score or None, note indices (num, 1, 24) int64)"""
         dev = next(self.model.parameters()).device
+        if beam_width is not None:
+            mask = self.playable_mask(allowed) if playable else allowed
+            self.model.decoder._beam_mask(beam_width, mask, 'cpu')   # a bad width or mask is refused before a draw is made
+            if top_k is not None or top_p is not None or temperature != 1.0:
+                raise ValueError("beam search draws no note: top_k, top_p and temperature cannot be combined with it")
+            z = ops.normal_noise((int(num), self.model.latent_space_dim), dev)
+            return self.decode_latent_codes(z, sampling='beam', beam_width=beam_width, allowed=mask)
         flt = (top_k, top_p, self.playable_mask(allowed) if playable else allowed)
         self.model.decoder.sampling_filter(*flt)                # bad cuts are refused before a draw is made
         z = ops.normal_noise((int(num), self.model.latent_space_dim), dev)

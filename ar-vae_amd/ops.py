@@ -920,6 +920,80 @@ def tick_free_run_layers_filtered(cells, w_out, b_out, h0, gib, ptab, batch, bea
     return tokens
 
 
+def _beam_mask(vocab, allow):
+    """-> (the mask on the device or None, the number of notes it allows): the library takes the count from the host"""
+    if allow is None:
+        return None, int(vocab)
+    if allow.dtype != torch.uint8 or tuple(allow.shape) != (vocab,):
+        raise ValueError(f'the allowed-note mask must be uint8 of shape ({vocab},), got {allow.dtype} {tuple(allow.shape)}')
+    _dev(allow)
+    return allow.contiguous(), int(allow.count_nonzero())
+
+
+def tick_beam_search_supported(hidden, vocab, width):
+    """True when the one-launch beam search is offered for (hidden, vocab, width); else go tick by tick (beam_select)."""
+    return bool(_lib.load().arvae_tick_beam_search_supported(int(hidden), int(vocab), int(width)))
+
+
+def tick_beam_search(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, width, allow=None, allowed=None):
+    """the beam search of the two-layer tick decoder in one launch (arvae_tick_beam_search; the semantics: include/arvae_hip.h, "Beam
+    search"): -> (parents (B, T, W) int32, tokens (B, T, W) int64, scores_hist (B, T, W), sequences (B, W, T) int64, scores (B, W)).
+    weights / h0 / gib / ptab as tick_free_run; allow None or uint8 (V,) on the device (allowed: its count, when the caller has it)."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    allow, count = _beam_mask(vocab, allow) if allowed is None or allow is None else (allow.contiguous(), int(allowed))
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    ticks, dev = beats * ticks_per_beat, gib.device
+    parents = torch.empty(batch, ticks, width, device=dev, dtype=torch.int32)
+    tokens = torch.empty(batch, ticks, width, device=dev, dtype=torch.int64)
+    hist = torch.empty(batch, ticks, width, device=dev, dtype=torch.float32)
+    seqs = torch.empty(batch, width, ticks, device=dev, dtype=torch.int64)
+    scores = torch.empty(batch, width, device=dev, dtype=torch.float32)
+    ws = torch.empty(lib.arvae_tick_beam_search_ws_floats(hid), device=dev, dtype=torch.float32)
+    with _timed('tick_beam_search', 2.0 * batch * width * ticks * (9 * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_beam_search(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), batch, beats,
+                                              ticks_per_beat, hid, vocab, int(width), _ptr(allow), count, _ptr(parents), _ptr(tokens),
+                                              _ptr(hist), _ptr(seqs), _ptr(scores), _ptr(ws), _stream()), 'tick_beam_search')
+    return parents, tokens, hist, seqs, scores
+
+
+def beam_select(logits, scores, live, allow=None, allowed=None):
+    """one tick's selection of the beam search on given logits (codes * W, V) and scores (codes, W), the first `live` beams of a code
+    live (arvae_beam_select) -> (parents (codes, W) int32, notes (codes, W) int64, scores (codes, W))."""
+    _dev(logits, scores)
+    lib = _lib.load()
+    logits, scores = logits.contiguous(), scores.contiguous()
+    codes, width = scores.shape
+    vocab = logits.shape[1]
+    if logits.shape[0] != codes * width or scores.dtype != torch.float32 or logits.dtype != torch.float32:
+        raise ValueError(f'beam_select takes float32 logits ({codes * width}, V) for scores ({codes}, {width}), got {tuple(logits.shape)}')
+    allow, count = _beam_mask(vocab, allow) if allowed is None or allow is None else (allow.contiguous(), int(allowed))
+    parents = torch.empty(codes, width, device=logits.device, dtype=torch.int32)
+    notes = torch.empty(codes, width, device=logits.device, dtype=torch.int64)
+    out = torch.empty(codes, width, device=logits.device, dtype=torch.float32)
+    _lib.check(lib.arvae_beam_select(_ptr(logits), _ptr(scores), codes, width, vocab, int(live), _ptr(allow), count, _ptr(parents),
+                                     _ptr(notes), _ptr(out), _stream()), 'beam_select')
+    return parents, notes, out
+
+
+def sequence_log_prob(weights, tokens, allow=None):
+    """(R,) float32: the sum over t of the log-softmax of weights (R, T, V) over the allowed notes at tokens (R, T) int64
+    (arvae_sequence_log_prob); a token that is not allowed gives -inf."""
+    _dev(weights, tokens)
+    lib = _lib.load()
+    if weights.dim() != 3 or tuple(tokens.shape) != tuple(weights.shape[:2]) or tokens.dtype != torch.int64 or weights.dtype != torch.float32:
+        raise ValueError(f'sequence_log_prob takes float32 weights (R, T, V) and int64 tokens (R, T), got {tuple(weights.shape)} '
+                         f'{weights.dtype} and {tuple(tokens.shape)} {tokens.dtype}')
+    weights, tokens = weights.contiguous(), tokens.contiguous()
+    rows, steps, vocab = weights.shape
+    allow, _ = _beam_mask(vocab, allow)
+    out = torch.empty(rows, device=weights.device, dtype=torch.float32)
+    _lib.check(lib.arvae_sequence_log_prob(_ptr(weights), _ptr(tokens), rows, steps, vocab, _ptr(allow), _ptr(out), _stream()),
+               'sequence_log_prob')
+    return out
+
+
 def _sampling_uniforms(u, shape):
     if u.dtype != torch.float32 or tuple(u.shape) != tuple(shape):
         raise ValueError(f'sampling uniforms must be float32 of shape {tuple(shape)}, got {u.dtype} {tuple(u.shape)}')

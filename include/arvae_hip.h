@@ -425,6 +425,44 @@ int arvae_tick_free_run_layers_filtered(const arvae_tick_stack_t *stack, const f
                                         int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
                                         const arvae_sample_filter_t *filter, int64_t *tokens, float *ws, arvae_stream_t stream);
 
+/* Beam search of the free-running decoder (generation; beyond the reference): the `width` most likely measures of a latent code,
+ * and the log-probability of a given measure.  One definition for the entry points below.
+ *   Inputs per code: the tick RNN's inputs as for arvae_tick_free_run, width W in [1, 16], allow: DEVICE pointer to vocab bytes
+ *   (NULL = every note) and `allowed` = the number of notes it allows, counted by the host (vocab when allow is NULL).  W <= allowed:
+ *   otherwise fewer than W distinct hypotheses exist after tick 0 (ARVAE_E_INVALID).
+ *   A beam is (score, previous note, tick-GRU states).  At tick t, for every live beam k:
+ *     1. logits l = relu(W_out h + b_out), exactly as the free-running kernel forms them;
+ *     2. logp_v = (l_v - M) - log(sum over allowed u of exp(l_u - M)), M = max over allowed u of l_u: the log-softmax over the
+ *        allowed notes only (the renormalisation of the filtered draw);
+ *     3. candidate (k, v) for allowed v: c = score_k + logp_v in fp32;
+ *     4. the candidates of a code are ordered by c descending (compared as floats), ties to the lower k, then the lower v (as
+ *        integers: the argmax pick's rule extended).  New beam j is the j-th candidate: beam k's states after tick t, note v as its
+ *        previous note, score c.
+ *   At tick 0 only beam 0 is live (score 0; the others -inf, never a parent).  At a beat's first tick every beam restarts from that
+ *   beat's initial states, as the decoder does.  All hypotheses have beats*ticks_per_beat ticks: no length normalisation.
+ *   Outputs: the per-tick history parents [batch][ticks][W] int32, tokens [batch][ticks][W] int64, scores_hist [batch][ticks][W];
+ *   the backtracked sequences [batch][W][ticks] int64, best first, and their scores [batch][W] (the last tick's).  By construction the
+ *   W sequences of a code are distinct and their scores non-increasing in j; W = 1 is the argmax free run.
+ * arvae_beam_select: step 2 to 4 on given logits [codes*width][vocab] (row = code*width + k) and scores_in [codes][width], of which the
+ *   first `live` beams of every code are read (1 at tick 0, width afterwards; live * allowed >= width) -> parents / notes / scores_out
+ *   [codes][width].  Any vocab >= 1: the tick-by-tick path.
+ * arvae_sequence_log_prob: out[r] = sum over t of logp (step 2) of weights [rows][steps][vocab] at tokens [rows][steps]; fp32, sums in a
+ *   fixed order.  A token outside [0, vocab) or not allowed gives -inf.
+ * arvae_tick_beam_search: the whole search in one launch, for the two-layer tick RNN at the shapes of
+ *   arvae_tick_beam_search_supported(hidden, vocab, width) (those of arvae_tick_free_run_supported, every width in [1, 16]) and at most
+ *   32 ticks; ws: arvae_tick_beam_search_ws_floats(hidden) floats, 16-byte aligned, required.  No keep-masks: generation runs with
+ *   dropout off.  Every bad argument is refused with a message before any launch. */
+int arvae_beam_select(const float *logits, const float *scores_in, int32_t codes, int32_t width, int32_t vocab, int32_t live,
+                      const uint8_t *allow, int32_t allowed, int32_t *parents, int64_t *notes, float *scores_out, arvae_stream_t stream);
+int arvae_sequence_log_prob(const float *weights, const int64_t *tokens, int32_t rows, int32_t steps, int32_t vocab, const uint8_t *allow,
+                            float *out, arvae_stream_t stream);
+int arvae_tick_beam_search_supported(int32_t hidden, int32_t vocab, int32_t width);
+int64_t arvae_tick_beam_search_ws_floats(int32_t hidden);
+int arvae_tick_beam_search(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1, int64_t h0_stride /* 0 = hidden */,
+                           const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
+                           int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed, int32_t *parents, int64_t *tokens,
+                           float *scores_hist, int64_t *sequences, float *scores, float *ws, arvae_stream_t stream);
+
 /* out[r] = [a[r] | b[r]] (torch.cat along dim 1/2, decoder.py:503) and its adjoint (db optionally accumulated) */
 int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,
                       arvae_stream_t stream);

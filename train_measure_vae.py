@@ -62,11 +62,15 @@ with_metrics = False
 # likewise opt-in and outside the reference's flags: measures drawn from the evaluated model (MeasureVAETrainer.sample_measures)
 SAMPLE_FLAG, TEMPERATURE_FLAG = '--sample', '--temperature'
 TOP_K_FLAG, TOP_P_FLAG, PLAYABLE_FLAG = '--top_k', '--top_p', '--playable'
+BEAM_FLAG = '--beam'
 SAMPLE_HELP = (f'{SAMPLE_FLAG} N [{TEMPERATURE_FLAG} T] [{TOP_K_FLAG} K] [{TOP_P_FLAG} P] [{PLAYABLE_FLAG}]: add `samples` to the '
                'evaluation summary, N measures drawn from the model (z from the prior, every note from softmax(probs / T), T = 1 by '
                'default) as 24 note names each; K keeps the K most likely notes, P the most likely notes up to a share P of the mass, '
-               f'{PLAYABLE_FLAG} keeps START, END and None out.  These three are echoed as `sampling`.')
-num_samples, temperature, top_k, top_p, playable = 0, 1.0, None, None, False
+               f'{PLAYABLE_FLAG} keeps START, END and None out.  These three are echoed as `sampling`.  '
+               f'{SAMPLE_FLAG} N {BEAM_FLAG} W [{PLAYABLE_FLAG}]: the N prior draws are decoded by beam search over W beams instead of '
+               f'drawing notes (the most likely measure of each code); not together with {TOP_K_FLAG}, {TOP_P_FLAG} or '
+               f'{TEMPERATURE_FLAG}.')
+num_samples, temperature, top_k, top_p, playable, beam = 0, 1.0, None, None, False, None
 
 
 def with_options(fn):
@@ -146,8 +150,10 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         if num_samples > 0:
             trainer.cuda()
             model.eval()
-            _, notes = trainer.sample_measures(num_samples, temperature, top_k=top_k, top_p=top_p, playable=playable)
-            if top_k is not None or top_p is not None or playable:          # the cuts are echoed beside the measures they shaped
+            _, notes = trainer.sample_measures(num_samples, temperature, top_k=top_k, top_p=top_p, playable=playable, beam_width=beam)
+            if beam is not None:
+                summary['sampling'] = {'beam': beam, 'playable': playable}
+            elif top_k is not None or top_p is not None or playable:        # the cuts are echoed beside the measures they shaped
                 summary['sampling'] = {'temperature': temperature, 'top_k': top_k, 'top_p': top_p, 'playable': playable}
             summary['samples'] = [[dataset.index2note_dicts[int(i)] for i in row] for row in notes.squeeze(1).tolist()]
         print(json.dumps(summary, indent=2))
@@ -171,16 +177,25 @@ def _take_value(argv, flag, cast, default):
 
 
 def run(argv=None):
-    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p
-    and --playable.  Values of --top_k / --top_p outside their ranges raise the decoder's ValueError (sampling_filter)."""
-    global with_metrics, num_samples, temperature, top_k, top_p, playable
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p,
+    --playable and --beam.  Values of --top_k / --top_p outside their ranges raise the decoder's ValueError (sampling_filter); --beam
+    takes a width in [1, 16] and is refused together with --top_k, --top_p or --temperature (beam search draws nothing)."""
+    global with_metrics, num_samples, temperature, top_k, top_p, playable, beam
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
     playable = PLAYABLE_FLAG in argv
     num_samples, argv = _take_value(argv, SAMPLE_FLAG, int, 0)
+    drew = any(a == TEMPERATURE_FLAG or a.startswith(TEMPERATURE_FLAG + '=') for a in argv)
     temperature, argv = _take_value(argv, TEMPERATURE_FLAG, float, 1.0)
     top_k, argv = _take_value(argv, TOP_K_FLAG, int, None)
     top_p, argv = _take_value(argv, TOP_P_FLAG, float, None)
+    beam, argv = _take_value(argv, BEAM_FLAG, int, None)
+    if beam is not None:
+        if not 1 <= beam <= 16:
+            raise ValueError(f'{BEAM_FLAG} takes a beam width in [1, 16], got {beam}')
+        if top_k is not None or top_p is not None or drew:
+            raise ValueError(f'{BEAM_FLAG} decodes by beam search, which draws no note: it cannot be combined with {TOP_K_FLAG}, '
+                             f'{TOP_P_FLAG} or {TEMPERATURE_FLAG}')
     if num_samples < 0 or not temperature > 0:
         raise SystemExit(f'{SAMPLE_FLAG} takes a count >= 0 and {TEMPERATURE_FLAG} a positive number')
     check_sampling_cuts(top_k, top_p)          # the decoder's own ValueError, before anything is loaded or trained
