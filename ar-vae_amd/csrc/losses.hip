@@ -528,6 +528,7 @@ extern "C" int arvae_reg_loss(const float *z_rows, const float *lab_rows, int64_
     for (int i = 0; i < 16; ++i) rd.d[i] = i < r ? dims[i] : 0;
     for (int i = 0; i < r; ++i)
         ARVAE_REQUIRE(dims[i] >= 0 && dims[i] < ldz && dims[i] < ldl, "reg_loss: dim %d outside z/labels", dims[i]);
+    ARVAE_REQUIRE(reg_dims_repeated(dims, r) < 0, "reg_loss: dim %d listed twice", reg_dims_repeated(dims, r));
     float *row_loss = ws, *row_grad = ws + n_rows * r;
     hipStream_t s = as_stream(stream);
     if (int rc = reg_partials(z_rows, lab_rows, n_rows, z_cols, lab_cols, n_cols, ldz, ldl, rd, r, delta, ws, s, nullptr, nullptr)) return rc;

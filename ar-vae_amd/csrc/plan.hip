@@ -708,6 +708,8 @@ extern "C" int arvae_image_vae_forward(const arvae_image_vae_t *m, int32_t batch
         for (int i = 0; i < m->n_reg; ++i)
             ARVAE_REQUIRE(m->reg_dims[i] >= 0 && m->reg_dims[i] < m->zdim && m->reg_dims[i] < ld_labels,
                           "image_vae_forward: reg dim %d outside z/labels", m->reg_dims[i]);
+        ARVAE_REQUIRE(reg_dims_repeated(m->reg_dims, m->n_reg) < 0, "image_vae_forward: reg dim %d listed twice",
+                      reg_dims_repeated(m->reg_dims, m->n_reg));
         const float *zc = z_cols != nullptr ? z_cols : z;
         const float *lc = lab_cols != nullptr ? lab_cols : labels;
         reg_args = RegArgs{z, labels, batch, zc, lc, z_cols != nullptr ? n_cols : (int64_t)batch, m->zdim, ld_labels, reg_dims_of(m),
@@ -777,6 +779,8 @@ extern "C" int arvae_image_vae_finish(const arvae_image_vae_t *m, int32_t batch,
         for (int i = 0; i < m->n_reg; ++i)
             ARVAE_REQUIRE(m->reg_dims[i] >= 0 && m->reg_dims[i] < m->zdim && m->reg_dims[i] < ld_labels,
                           "image_vae_finish: reg dim %d outside z/labels", m->reg_dims[i]);
+        ARVAE_REQUIRE(reg_dims_repeated(m->reg_dims, m->n_reg) < 0, "image_vae_finish: reg dim %d listed twice",
+                      reg_dims_repeated(m->reg_dims, m->n_reg));
         // the gathered columns index dims 0 .. zdim-1 / 0 .. ld_labels-1 like the local arrays (whole rows are gathered)
         // (a training step may leave the finishing step to its backward pass -- ARVAE_VAE_DEFER_FINISH, as in the single-rank forward
         // pass: the regulariser's launch, the last of this call, then parks that step's arguments and poisons the scalars)

@@ -354,6 +354,8 @@ static int reg_and_finish(const MvPass &p, const char *what, int nb, const float
         for (int i = 0; i < m->n_reg; ++i)
             ARVAE_REQUIRE(m->reg_dims[i] >= 0 && m->reg_dims[i] < d.z && m->reg_dims[i] < 4, "%s: regularised dim %d outside z / the attributes",
                           what, m->reg_dims[i]);
+        ARVAE_REQUIRE(reg_dims_repeated(m->reg_dims, m->n_reg) < 0, "%s: regularised dim %d listed twice", what,
+                      reg_dims_repeated(m->reg_dims, m->n_reg));
         MV_TRY(reg_partials(z, lab, d.b, z_cols, lab_cols, n_cols, d.z, 4, rd, m->n_reg, m->delta, w.reg_ws, p.s));
     }
     return vae_finish(w.rec_ws, nb, d.b, d.rt, mu, sigma, d.z, m->beta, capacity, m->n_reg > 0 ? w.reg_ws : nullptr, n_cols, d.z, m->reg_dims,

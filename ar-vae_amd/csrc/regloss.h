@@ -14,6 +14,16 @@ constexpr int REG_CHUNK = 2048;   // columns staged per pass: 2 * 8 KB of LDS
 
 struct RegDims { int d[16]; };
 
+// the first dimension that `dims` lists twice, or -1.  A repeated dimension would be counted twice in the loss while dz has one
+// entry for it (the finishing step gives dz[row][c] the row gradient of the LAST k with dims[k] == c: one share lost), so every
+// entry point refuses it.
+static inline int reg_dims_repeated(const int32_t *dims, int r) {
+    for (int i = 1; i < r; ++i)
+        for (int j = 0; j < i; ++j)
+            if (dims[i] == dims[j]) return dims[i];
+    return -1;
+}
+
 struct RegArgs {
     const float *zr, *lr;        // this rank's rows: z [n_rows][ldz], labels [n_rows][ldl]
     int64_t n_rows;

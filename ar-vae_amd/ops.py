@@ -470,6 +470,8 @@ def reg_loss(z, labels, dims, gamma, delta, z_cols=None, lab_cols=None):
     dims = tuple(int(d) for d in dims)
     if len(dims) == 0:
         raise ValueError('reg_loss needs at least one dimension')
+    if len(set(dims)) != len(dims):
+        raise ValueError(f'reg_loss: a dimension is listed twice in {dims} (dz has one entry per column)')
     return _RegLossFn.apply(z.contiguous(), labels.contiguous().to(torch.float32), dims, float(gamma), float(delta),
                             None if z_cols is None else z_cols.contiguous(),
                             None if lab_cols is None else lab_cols.contiguous().to(torch.float32))

@@ -184,7 +184,8 @@ int arvae_kld_bwd(const float *g, const float *mu, const float *sigma, const flo
  *   loss = sum_r gamma/NC^2 * sum_{i in rows, j in cols} | tanh(delta*(z_i - z_j)) - sign(a_i - a_j) |
  *   dz[i, dims[r]] = 2*gamma*delta/NC^2 * sum_j (1 - t_ij^2) * sgn(t_ij - s_ij)      (other columns 0)
  * Rows are this rank's samples, cols the (all-gathered) global batch; single GPU: cols == rows.
- * dims: HOST array of R latent/label column indices (z[:,d] pairs with labels[:,d]).
+ * dims: HOST array of R DISTINCT latent/label column indices (z[:,d] pairs with labels[:,d]); an index listed twice is
+ * ARVAE_E_INVALID here and as a model's reg_dims (dz has one entry per column: the second share would be lost).
  * ws: device scratch of arvae_reg_loss_ws_floats(n_rows, R) floats.  loss_out: 1 float.
  * dz: [n_rows, ldz] fully written (gradient for unit upstream gradient), may be NULL.
  * ------------------------------------------------------------------------------------------------ */
