@@ -172,6 +172,8 @@ def test_token_recon_golden(golden_dir, dev, b):
 
 
 # ---------------------------------------------------------------- links vs torch fp32 on CPU
+# (the accuracy bar of the single-channel rows -- chi = 1 here, chi(out) = 1 in DECONV_CASES -- is in
+# test_single_channel_links_float64.py: float64 references, linear maps, the batches at which the persistent loops run again)
 CONV_CASES = [  # (n, hi, chi, clo, k, s, p, act)
     (3, 64, 1, 32, 4, 2, 1, 'relu'), (5, 32, 32, 32, 4, 2, 1, 'relu'), (9, 8, 32, 32, 4, 2, 1, 'relu'),
     (2, 28, 1, 64, 4, 1, 0, 'selu'), (2, 25, 64, 64, 4, 1, 0, 'selu'), (3, 22, 64, 8, 4, 1, 0, 'selu'),

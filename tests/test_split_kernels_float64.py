@@ -41,12 +41,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from single_channel_cases import SELU_SA, fold as _fold          # (the folded gradient operand, shared with the single-channel links' test)
 from split_cases import (CONV_BATCHES, CONV_LINKS, DENSE_LONG, DENSE_SMALL, DENSE_WIDE, FLOOR, R, WGRAD_CASES, link_geometry)
 
 pytestmark = pytest.mark.gpu
-
-SELU_SCALE = float(np.float32(1.0507009873554805))          # the kernels' fp32 constants (common.h), so that the float64
-SELU_SA = float(np.float32(1.0507009873554805) * np.float32(1.6732632423543772))       # reference is the SAME operation
 
 
 @pytest.fixture(scope='module')
@@ -87,16 +85,6 @@ def _tensors(name, n, seed):
     return dict(hi=rs.standard_normal((n, hi, hi, chi)).astype(np.float32), lo=rs.standard_normal((n, lo, lo, clo)).astype(np.float32),
                 w=(rs.standard_normal((clo, chi, k, k)) * 0.2).astype(np.float32),
                 b_lo=rs.standard_normal(clo).astype(np.float32), b_hi=rs.standard_normal(chi).astype(np.float32))
-
-
-def _fold(g, y, mask, act, dtype):
-    """a gradient operand as multiplied (common.h Operand::at): g * act'(y) [* 2 mask, y read as y / 2], in `dtype` from fp32 data"""
-    g, y = torch.from_numpy(g).to(dtype), torch.from_numpy(y).to(dtype)
-    if mask is not None:
-        g, y = g * (2.0 * torch.from_numpy(mask).to(dtype)), y * 0.5
-    if act == 1:
-        return g * (y > 0).to(dtype)
-    return g * torch.where(y > 0, torch.full_like(y, SELU_SCALE), y + SELU_SA)
 
 
 def _nchw(a, dtype):
