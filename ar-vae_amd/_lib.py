@@ -77,6 +77,11 @@ class SampleFilter(ctypes.Structure):
     _fields_ = [('top_k', c_i32), ('top_p', c_f32), ('allow', c_vp)]
 
 
+class NotePlan(ctypes.Structure):
+    """arvae_note_plan_t"""
+    _fields_ = [('allow', c_vp), ('row_stride', c_i64), ('tick_stride', c_i64)]
+
+
 class MeasureVaeDesc(ctypes.Structure):
     """arvae_measure_vae_t"""
     _fields_ = ([(n, c_i32) for n in ('vocab', 'emb', 'enc_hidden', 'dec_hidden', 'zdim', 'steps', 'beats', 'ticks_per_beat')] +
@@ -159,12 +164,16 @@ SIGNATURES = {
                                             c_vp, c_f32, c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_filtered': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                              c_vp, c_f32, _P(SampleFilter), c_vp, c_vp, c_vp]),
+    'arvae_tick_free_run_planned': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                            c_vp, c_f32, _P(SampleFilter), _P(NotePlan), c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_layers_supported': (c_i32, [c_i32, c_i32, c_i32]),
     'arvae_tick_free_run_layers_ws_floats': (c_i64, [c_i32, c_i32]),
     'arvae_tick_free_run_layers': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp,
                                            c_vp, c_vp]),
     'arvae_tick_free_run_layers_filtered': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
                                                     _P(SampleFilter), c_vp, c_vp, c_vp]),
+    'arvae_tick_free_run_layers_planned': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
+                                                   _P(SampleFilter), _P(NotePlan), c_vp, c_vp, c_vp]),
     'arvae_embed_fwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'arvae_embed_bwd_ws_floats': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     'arvae_embed_bwd': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
@@ -176,6 +185,11 @@ SIGNATURES = {
     'arvae_row_argmax': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     'arvae_row_sample': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     'arvae_row_sample_filtered': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, _P(SampleFilter), c_vp, c_vp]),
+    'arvae_row_sample_planned': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f32, _P(SampleFilter), _P(NotePlan), c_i32, c_i32, c_vp, c_vp]),
+    'arvae_beam_select_planned': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, _P(NotePlan), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_sequence_log_prob_planned': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, _P(NotePlan), c_vp, c_vp]),
+    'arvae_tick_beam_search_planned': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                               _P(NotePlan), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'arvae_beam_select': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'arvae_sequence_log_prob': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'arvae_tick_beam_search_supported': (c_i32, [c_i32, c_i32, c_i32]),

@@ -7,8 +7,11 @@
 //   beam_select_kernel        the selection alone on given logits, any vocabulary: the tick-by-tick path (ARVAE_TICK_STEPWISE=1, other
 //                             layer counts and hidden sizes, more than 64 notes) and the on-device yardstick of the one-launch kernel;
 //   sequence_log_prob_kernel  sum over t of the masked log-softmax of given logits at given tokens.
+// All three also serve a note plan (include/arvae_hip.h, "Note plans": the allowed notes per (code, tick)); the one-launch kernel has an
+// instantiation of its own for it, in which a code may hold fewer than W finite hypotheses (dead slots).
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "diag.h"
 #include "common.h"
 #include "dispatch.h"
@@ -31,14 +34,23 @@ __device__ __forceinline__ bool beam_before(float ca, int ka, int va, float cb, 
 // One wave per code.  Per live beam k: M_k = the allowed maximum, S_k = the sum of exp(l - M_k) over the allowed notes (every lane its
 // notes in index order, then the xor butterfly: both lanes of a pair add the same two values, so every lane holds the same bits), lane
 // k keeps (M_k, log S_k, score_k).  Then W rounds: every lane takes the first of its candidates that is ordered behind the previous
-// round's pick, the butterfly the first among the lanes.  No allowed candidate left (the entry point rules it out): parent 0, note 0, -inf.
+// round's pick, the butterfly the first among the lanes.  No allowed candidate left (arvae_beam_select rules it out; under a note plan
+// a forced tick or dead beams bring it about): a dead slot -- parent 0, the code's first allowed note (note 0 without one), -inf.
+// allow_stride: bytes between the codes' masks (a note plan's tick; 0: one mask for every code).
 __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict__ logits, const float *__restrict__ scores_in, int width,
-                                                         int vocab, int live, const uint8_t *__restrict__ allow,
+                                                         int vocab, int live, const uint8_t *__restrict__ allow_all, int64_t allow_stride,
                                                          int *__restrict__ parents, int64_t *__restrict__ notes,
                                                          float *__restrict__ scores_out) {
     const int code = blockIdx.x, lane = threadIdx.x;
     const float *base = logits + (int64_t)code * width * vocab;
+    const uint8_t *allow = allow_all != nullptr ? allow_all + code * allow_stride : nullptr;
     auto on = [&](int v) { return allow == nullptr || allow[v] != 0; };
+    int first_on = vocab;
+    for (int v = lane; v < vocab; v += 64)
+        if (on(v)) { first_on = v; break; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) first_on = min(first_on, __shfl_xor(first_on, off, 64));
+    first_on = first_on < vocab ? first_on : 0;
     float my_m = 0.f, my_ls = 0.f, my_sc = -INFINITY;
     for (int k = 0; k < live; ++k) {
         const float *row = base + (int64_t)k * vocab;
@@ -78,7 +90,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict
             bc = take ? oc : bc; bk = take ? ok : bk; bv = take ? ov : bv;
             found = found || of;
         }
-        if (!found) { bc = -INFINITY; bk = 0; bv = 0; }
+        if (!found) { bc = -INFINITY; bk = 0; bv = first_on; }
         if (lane == 0) {
             parents[(int64_t)code * width + j] = bk;
             notes[(int64_t)code * width + j] = bv;
@@ -92,12 +104,15 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict
 // exp(l - M) over the allowed notes in index order with a compensated (Kahan) running sum, (l_tok - M) - log S -- and adds its ticks in
 // order; the butterfly adds the lanes.  A token outside the vocabulary or not allowed: -inf.
 __global__ __launch_bounds__(64) void sequence_log_prob_kernel(const float *__restrict__ w, const int64_t *__restrict__ tokens, int steps,
-                                                               int vocab, const uint8_t *__restrict__ allow, float *__restrict__ out) {
+                                                               int vocab, const uint8_t *__restrict__ allow_all, int64_t row_stride,
+                                                               int64_t tick_stride, float *__restrict__ out) {
 #pragma clang fp contract(off)
     const int r = blockIdx.x, lane = threadIdx.x;
-    auto on = [&](int v) { return allow == nullptr || allow[v] != 0; };
     float acc = 0.f;
     for (int t = lane; t < steps; t += 64) {
+        // (a note plan: the mask of this row at this tick; the strides are 0 for the one mask of arvae_sequence_log_prob)
+        const uint8_t *allow = allow_all != nullptr ? allow_all + r * row_stride + t * tick_stride : nullptr;
+        auto on = [&](int v) { return allow == nullptr || allow[v] != 0; };
         const float *row = w + ((int64_t)r * steps + t) * vocab;
         const int64_t tok = tokens[(int64_t)r * steps + t];
         float lp = -INFINITY;
@@ -137,6 +152,13 @@ struct TickBeam {
     float *scores;                 // [B][W]
 };
 
+// TickBeam with a note plan (arvae_note_plan_t) in place of `allow`: the allowed notes of code b at tick t are plan[b * row_stride +
+// t * tick_stride + v] != 0.  A type of its own, so that the unplanned kernel's arguments stay what they were.
+struct TickBeamPlanned : TickBeam {
+    const uint8_t *plan;
+    int64_t row_stride, tick_stride;
+};
+
 // The recurrence is tick_free_run_h2_kernel's (the same operands, products and gates in the same order: width 1 feeds back the argmax
 // run's notes), over tile rows r = (code, beam k): code = r >> wshift of the workgroup's RW >> wshift codes, k = r & (WP - 1); beams
 // k >= W of a padded width are dead (score -inf, never a parent).  What differs:
@@ -151,9 +173,20 @@ struct TickBeam {
 //     history;
 //   * behind the next barrier every lane takes its rows' parents' states from h0f / h1f and rebuilds the split images.
 // After the last tick one lane per beam walks the history in LDS backwards and writes the sequence.
-template <int H, int RW>
-__global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, const uint4 *__restrict__ packed) {
+//
+// P = TickBeamPlanned (PLAN): a lane reads its note's plan byte of its rows' codes at every tick's top (under the layers' products),
+// and the selection holds with FEWER than W allowed notes in a row and fewer than W finite candidates in a code:
+//   * stage 1 marks the notes outside A(b, t) (and past the vocabulary) in `cnd` as NaN, which no comparison orders before anything:
+//     an allowed note's rank counts allowed notes only.  The marked notes take the slots behind the row's allowed ones as FILLERS
+//     (-inf, the row's first allowed note), so that every row still writes all its W slots at every tick and nothing stale is read;
+//   * stage 2 orders the entries by (c, k, slot) -- inside a row the slots ARE the (c, v) order, so for finite entries this is
+//     (c, k, v) -- which keeps equal fillers apart, and counts the slots below W only: the W * W entries of a code then have
+//     distinct ranks and the ranks 0 .. W - 1 are each written once.  Entries of -inf are DEAD beams: behind every finite one, their
+//     notes inside A(b, t), their score -inf for good (-inf + logp).
+template <int H, int RW, class P>
+__global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint4 *__restrict__ packed) {
     static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
+    constexpr bool PLAN = std::is_same<P, TickBeamPlanned>::value;
     constexpr int E = RW / 4;
     constexpr int NW = H / 16, KS = H / 32, KQ = H / 16;
     constexpr int NGG = 9 * KS;
@@ -212,7 +245,8 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, con
     const int note = 16 * w + col;
     const bool note_ok = w < ntile && note < p.vocab;
     const float bout = note_ok ? p.b_out[note] : 0.f;
-    const bool note_on = note_ok && (p.allow == nullptr || p.allow[note] != 0);
+    bool note_on = note_ok;
+    if constexpr (!PLAN) note_on = note_ok && (p.allow == nullptr || p.allow[note] != 0);
 
     auto lrow = [&](int i) { return gru_lrow<E>(quad, i); };
     int rows[E];                                               // the code whose inputs the lane's element i reads
@@ -270,6 +304,11 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, con
         for (int i = 0; i < E; ++i) {
             const float *pt = p.ptab + (int64_t)tok[i] * 3 * H + unit;
             gi[i][0] = gb[i][0] + pt[0]; gi[i][1] = gb[i][1] + pt[H]; gi[i][2] = gb[i][2] + pt[2 * H];
+        }
+        [[maybe_unused]] unsigned plan_b[PLAN ? E : 1];        // PLAN: the tick's plan bytes of the lane's note, raw until the logits
+        if constexpr (PLAN) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) plan_b[i] = p.plan[rows[i] * p.row_stride + t * p.tick_stride + (note_ok ? note : 0)];
         }
         // ---- layer 0: matrix 0
         {
@@ -346,7 +385,11 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, con
             float lv[E];
             elems(lg, lv);
 #pragma unroll
-            for (int i = 0; i < E; ++i) lgs[lrow(i) * FLT_LS + note] = note_on ? fmaxf(lv[i] + bout, 0.f) : -1.f;
+            for (int i = 0; i < E; ++i) {
+                bool on = note_on;
+                if constexpr (PLAN) on = note_ok && plan_b[i] != 0;
+                lgs[lrow(i) * FLT_LS + note] = on ? fmaxf(lv[i] + bout, 0.f) : -1.f;
+            }
         }
         lds_barrier();
         // ---- selection, stage 1: a row's candidates and each note's rank inside its row.  Unit (element i, tile q) on wave
@@ -367,7 +410,7 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, con
             const float sc = score_s[r];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                c[q] = lv[q] >= 0.f ? sc + ((lv[q] - big) - ls) : -INFINITY;
+                c[q] = lv[q] >= 0.f ? sc + ((lv[q] - big) - ls) : (PLAN ? __builtin_nanf("") : -INFINITY);
                 cnd[r * FLT_LS + 16 * q + col] = c[q];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -377,6 +420,31 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, con
 #pragma unroll
             for (int q = 1; q < 4; ++q) mine = tq == q ? c[q] : mine;
             const int v = 16 * tq + col;
+            if constexpr (PLAN) {
+                int first_on = 0;                              // the row's first allowed note (the quad's 16 lanes hold the row)
+#pragma unroll
+                for (int q = 3; q >= 0; --q) {
+                    const int bits = (int)((unsigned)(__ballot(lv[q] >= 0.f) >> (16 * quad)) & 0xffffu);
+                    first_on = bits != 0 ? 16 * q + __ffs(bits) - 1 : first_on;
+                }
+                int rank = 0, nal = 0, nbad = 0;
+#pragma unroll 4
+                for (int n4 = 0; n4 < 16 * ntile; n4 += 4) {
+                    const f32x4 q4 = *reinterpret_cast<const f32x4 *>(&cnd[r * FLT_LS + n4]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float cn = q4[j];
+                        const bool bad = cn != cn;
+                        rank += (cn > mine || (cn == mine && n4 + j < v)) ? 1 : 0;
+                        nal += bad ? 0 : 1;
+                        nbad += bad && n4 + j < v ? 1 : 0;
+                    }
+                }
+                const bool filler = mine != mine;
+                const int slot = filler ? nal + nbad : rank;
+                if (slot < W) { top_c[r][slot] = filler ? -INFINITY : mine; top_v[r][slot] = filler ? first_on : v; }
+                continue;
+            }
             int rank = 0;
 #pragma unroll 4
             for (int n4 = 0; n4 < 16 * ntile; n4 += 4) {
@@ -419,7 +487,12 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(TickBeam p, con
                         for (int m = 0; m < 4; ++m) {
                             const float c2 = c4[m];
                             const int v2 = v4[m];
-                            rank += beam_before(c2, k2, v2, c, k, v) ? 1 : 0;
+                            if constexpr (PLAN) {
+                                const int s2 = 4 * j + m;
+                                rank += s2 < W && (c2 > c || (c2 == c && (k2 < k || (k2 == k && s2 < s)))) ? 1 : 0;
+                            } else {
+                                rank += beam_before(c2, k2, v2, c, k, v) ? 1 : 0;
+                            }
                         }
                     }
                 }
@@ -496,8 +569,23 @@ extern "C" int arvae_beam_select(const float *logits, const float *scores_in, in
     ARVAE_REQUIRE(live >= 1 && live <= width, "beam_select: live %d is outside [1, width = %d]", live, width);
     ARVAE_REQUIRE((int64_t)live * allowed >= width, "beam_select: %d live beams of %d allowed notes give fewer than width = %d candidates",
                   live, allowed, width);
-    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live, allow, parents,
-                 notes, scores_out);
+    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live, allow, (int64_t)0,
+                 parents, notes, scores_out);
+    return check_launch("beam_select_kernel");
+}
+
+extern "C" int arvae_beam_select_planned(const float *logits, const float *scores_in, int32_t codes, int32_t width, int32_t vocab, int32_t live,
+                                         const arvae_note_plan_t *plan, int32_t ticks, int32_t tick, int32_t *parents, int64_t *notes,
+                                         float *scores_out, arvae_stream_t stream) {
+    ARVAE_REQUIRE(logits && scores_in && parents && notes && scores_out, "beam_select_planned: null pointer");
+    ARVAE_REQUIRE(codes >= 1, "beam_select_planned: codes %d is not positive", codes);
+    ARVAE_REQUIRE(width >= 1 && width <= BEAM_MAX_WIDTH, "beam_select_planned: width %d is outside [1, %d]", width, BEAM_MAX_WIDTH);
+    ARVAE_REQUIRE(vocab >= 1, "beam_select_planned: vocab %d is not positive", vocab);
+    ARVAE_REQUIRE(live >= 1 && live <= width, "beam_select_planned: live %d is outside [1, width = %d]", live, width);
+    if (const int rc = note_plan_check("beam_select_planned", plan, ticks, vocab)) return rc;
+    ARVAE_REQUIRE(tick >= 0 && tick < ticks, "beam_select_planned: tick %d is outside [0, %d)", tick, ticks);
+    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live,
+                 plan->allow + tick * plan->tick_stride, plan->row_stride, parents, notes, scores_out);
     return check_launch("beam_select_kernel");
 }
 
@@ -507,7 +595,20 @@ extern "C" int arvae_sequence_log_prob(const float *weights, const int64_t *toke
     ARVAE_REQUIRE(rows >= 1, "sequence_log_prob: rows %d is not positive", rows);
     ARVAE_REQUIRE(steps >= 1, "sequence_log_prob: steps %d is not positive", steps);
     ARVAE_REQUIRE(vocab >= 1, "sequence_log_prob: vocab %d is not positive", vocab);
-    ARVAE_LAUNCH(sequence_log_prob_kernel, dim3(rows), dim3(64), 0, as_stream(stream), weights, tokens, steps, vocab, allow, out);
+    ARVAE_LAUNCH(sequence_log_prob_kernel, dim3(rows), dim3(64), 0, as_stream(stream), weights, tokens, steps, vocab, allow, (int64_t)0,
+                 (int64_t)0, out);
+    return check_launch("sequence_log_prob_kernel");
+}
+
+extern "C" int arvae_sequence_log_prob_planned(const float *weights, const int64_t *tokens, int32_t rows, int32_t steps, int32_t vocab,
+                                               const arvae_note_plan_t *plan, float *out, arvae_stream_t stream) {
+    ARVAE_REQUIRE(weights && tokens && out, "sequence_log_prob_planned: null pointer");
+    ARVAE_REQUIRE(rows >= 1, "sequence_log_prob_planned: rows %d is not positive", rows);
+    ARVAE_REQUIRE(steps >= 1, "sequence_log_prob_planned: steps %d is not positive", steps);
+    ARVAE_REQUIRE(vocab >= 1, "sequence_log_prob_planned: vocab %d is not positive", vocab);
+    if (const int rc = note_plan_check("sequence_log_prob_planned", plan, steps, vocab)) return rc;
+    ARVAE_LAUNCH(sequence_log_prob_kernel, dim3(rows), dim3(64), 0, as_stream(stream), weights, tokens, steps, vocab, plan->allow,
+                 plan->row_stride, plan->tick_stride, out);
     return check_launch("sequence_log_prob_kernel");
 }
 
@@ -517,11 +618,12 @@ extern "C" int arvae_tick_beam_search_supported(int32_t hidden, int32_t vocab, i
 
 extern "C" int64_t arvae_tick_beam_search_ws_floats(int32_t hidden) { return arvae_tick_free_run_ws_floats(hidden); }
 
-extern "C" int arvae_tick_beam_search(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
-                                      const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat,
-                                      int32_t hidden, int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed,
-                                      int32_t *parents, int64_t *tokens, float *scores_hist, int64_t *sequences, float *scores, float *ws,
-                                      arvae_stream_t stream) {
+// the two one-launch searches: plan null = arvae_tick_beam_search's mask and count, else the plan (no count: dead slots exist)
+static int tick_beam_search_launch(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                   const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat,
+                                   int32_t hidden, int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed,
+                                   const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens, float *scores_hist,
+                                   int64_t *sequences, float *scores, float *ws, arvae_stream_t stream) {
     ARVAE_REQUIRE(wts && h0_l0 && h0_l1 && gib && ptab, "tick_beam_search: null pointer");
     ARVAE_REQUIRE(wts->w_hh0 && wts->b_hh0 && wts->w_ih1 && wts->b_ih1 && wts->w_hh1 && wts->b_hh1 && wts->w_out && wts->b_out,
                   "tick_beam_search: null weight pointer");
@@ -533,19 +635,25 @@ extern "C" int arvae_tick_beam_search(const arvae_tick_weights_t *wts, const flo
     ARVAE_REQUIRE(arvae_gru_seq_supported(hidden), "tick_beam_search: hidden size %d is not built (32, 64, 128)", hidden);
     ARVAE_REQUIRE(arvae_tick_free_run_supported(hidden, vocab), "tick_beam_search: vocab of %d notes not supported at hidden size %d",
                   vocab, hidden);
-    if (const int rc = beam_width_check("tick_beam_search", width, vocab, allow, allowed)) return rc;
+    if (plan == nullptr) {
+        if (const int rc = beam_width_check("tick_beam_search", width, vocab, allow, allowed)) return rc;
+    } else {
+        ARVAE_REQUIRE(width >= 1 && width <= BEAM_MAX_WIDTH, "tick_beam_search: width %d is outside [1, %d]", width, BEAM_MAX_WIDTH);
+        if (const int rc = note_plan_check("tick_beam_search_planned", plan, (int64_t)beats * ticks_per_beat, vocab)) return rc;
+    }
     ARVAE_REQUIRE(arvae_tick_beam_search_supported(hidden, vocab, width), "tick_beam_search: width %d at hidden size %d is not offered",
                   width, hidden);
     ARVAE_REQUIRE(h0_stride == 0 || h0_stride >= hidden, "tick_beam_search: h0_stride %lld is below the hidden size %d",
                   (long long)h0_stride, hidden);
     ARVAE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "tick_beam_search: workspace must be 16-byte aligned");
-    TickBeam p{};
+    TickBeamPlanned p{};
     p.w_hh0 = wts->w_hh0; p.b_hh0 = wts->b_hh0; p.w_ih1 = wts->w_ih1; p.b_ih1 = wts->b_ih1;
     p.w_hh1 = wts->w_hh1; p.b_hh1 = wts->b_hh1; p.w_out = wts->w_out; p.b_out = wts->b_out;
     p.h0_l0 = h0_l0; p.h0_l1 = h0_l1; p.h0_stride = h0_stride != 0 ? h0_stride : hidden; p.gib = gib; p.ptab = ptab; p.allow = allow;
     p.batch = batch; p.beats = beats; p.tpb = ticks_per_beat; p.vocab = vocab; p.width = width;
     while ((1 << p.wshift) < width) ++p.wshift;
     p.parents = parents; p.tokens = tokens; p.scores_hist = scores_hist; p.sequences = sequences; p.scores = scores;
+    if (plan != nullptr) { p.plan = plan->allow; p.row_stride = plan->row_stride; p.tick_stride = plan->tick_stride; }
     TickPrep tp{};
     tp.w[0] = wts->w_hh0; tp.w[1] = wts->w_ih1; tp.w[2] = wts->w_hh1;
     tp.nmat = 3;
@@ -560,9 +668,30 @@ extern "C" int arvae_tick_beam_search(const arvae_tick_weights_t *wts, const flo
     const bool h_known = with_int<128, 64, 32>(hidden, [&](auto HH) {
         tick_prep_launch<decltype(HH)::value>(tp, ws, st);
         rw_known = with_int<4, 8, 16>(rw, [&](auto RW) {
-            ARVAE_LAUNCH((tick_beam_search_kernel<decltype(HH)::value, decltype(RW)::value>), gr, dim3(4 * decltype(HH)::value), 0, st, p, packed);
+            constexpr int H = decltype(HH)::value, R = decltype(RW)::value;
+            if (plan != nullptr) ARVAE_LAUNCH((tick_beam_search_kernel<H, R, TickBeamPlanned>), gr, dim3(4 * H), 0, st, p, packed);
+            else ARVAE_LAUNCH((tick_beam_search_kernel<H, R, TickBeam>), gr, dim3(4 * H), 0, st, static_cast<const TickBeam &>(p), packed);
         });
     });
     ARVAE_REQUIRE(h_known && rw_known, "tick_beam_search: no kernel for hidden size %d at %d rows per workgroup", hidden, rw);
     return check_launch("tick_beam_search_kernel");
+}
+
+extern "C" int arvae_tick_beam_search(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                      const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat,
+                                      int32_t hidden, int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed,
+                                      int32_t *parents, int64_t *tokens, float *scores_hist, int64_t *sequences, float *scores, float *ws,
+                                      arvae_stream_t stream) {
+    return tick_beam_search_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, batch, beats, ticks_per_beat, hidden, vocab, width, allow,
+                                   allowed, nullptr, parents, tokens, scores_hist, sequences, scores, ws, stream);
+}
+
+extern "C" int arvae_tick_beam_search_planned(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                              const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat,
+                                              int32_t hidden, int32_t vocab, int32_t width, const arvae_note_plan_t *plan,
+                                              int32_t *parents, int64_t *tokens, float *scores_hist, int64_t *sequences, float *scores,
+                                              float *ws, arvae_stream_t stream) {
+    ARVAE_REQUIRE(plan != nullptr, "tick_beam_search_planned: null plan");
+    return tick_beam_search_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, batch, beats, ticks_per_beat, hidden, vocab, width, nullptr,
+                                   vocab, plan, parents, tokens, scores_hist, sequences, scores, ws, stream);
 }

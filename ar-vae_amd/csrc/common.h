@@ -41,6 +41,20 @@ static inline int sample_filter_check(const char *who, const arvae_sample_filter
     return ARVAE_OK;
 }
 
+// what the planned entry points check of a note plan (arvae_note_plan_t): pointers, and strides that are 0 (broadcast) or the dense
+// [rows][ticks][vocab] form's -- anything else could read outside the caller's buffer
+static inline int note_plan_check(const char *who, const arvae_note_plan_t *plan, int64_t ticks, int32_t vocab) {
+    ARVAE_REQUIRE(plan != nullptr, "%s: null plan", who);
+    ARVAE_REQUIRE(plan->allow != nullptr, "%s: null plan mask (plan->allow)", who);
+    ARVAE_REQUIRE(ticks >= 1 && vocab >= 1, "%s: a plan of %lld ticks and %d notes", who, (long long)ticks, vocab);
+    ARVAE_REQUIRE(plan->row_stride == 0 || plan->row_stride == ticks * vocab,
+                  "%s: plan row stride %lld is neither 0 (one plan for every row) nor ticks * vocab = %lld", who,
+                  (long long)plan->row_stride, (long long)(ticks * vocab));
+    ARVAE_REQUIRE(plan->tick_stride == 0 || plan->tick_stride == vocab,
+                  "%s: plan tick stride %lld is neither 0 (one mask for every tick) nor vocab = %d", who, (long long)plan->tick_stride, vocab);
+    return ARVAE_OK;
+}
+
 // stream of the ABI call in progress on this thread (lets check_launch() timestamp kernels when profiling)
 extern thread_local hipStream_t g_cur_stream;
 static inline hipStream_t as_stream(arvae_stream_t s) {

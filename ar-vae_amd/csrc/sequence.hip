@@ -355,12 +355,14 @@ __global__ __launch_bounds__(256) void row_sample_kernel(const float *__restrict
 // top_k notes are ordered before it and the e of those notes sums to less than top_p * S, S = the sum of e over the notes top_k leaves
 // (top_p >= 1: no such cut).  The sums grow along the order, so the survivors are a leading run of it: (cut_l, cut_i) is its last
 // note, and a note survives iff it is not ordered behind that one.  Two walks of cols^2 steps per row (S, then the cut), one thread per
-// row: this is the tick-by-tick path.  No allowed note: index 0.
+// row: this is the tick-by-tick path.  No allowed note: index 0.  allow_stride: bytes between the rows' masks (a note plan's tick:
+// arvae_row_sample_planned; 0: one mask for every row).
 __global__ __launch_bounds__(256) void row_sample_filtered_kernel(const float *__restrict__ w, int rows, int cols, const float *__restrict__ u,
-                                                                   float inv_t, int top_k, float top_p, const uint8_t *__restrict__ allow,
-                                                                   int64_t *__restrict__ idx) {
+                                                                   float inv_t, int top_k, float top_p, const uint8_t *__restrict__ allow_all,
+                                                                   int64_t allow_stride, int64_t *__restrict__ idx) {
     for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) {
         const float *row = w + (int64_t)r * cols;
+        const uint8_t *allow = allow_all != nullptr ? allow_all + r * allow_stride : nullptr;
         auto on = [&](int j) { return allow == nullptr || allow[j] != 0; };
         float mx = -INFINITY;
         for (int j = 0; j < cols; ++j)
@@ -620,7 +622,24 @@ extern "C" int arvae_row_sample_filtered(const float *w, int32_t rows, int32_t c
     ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
                   "row_sample_filtered: inverse temperature %f is not a positive finite number", (double)inv_temperature);
     ARVAE_LAUNCH(row_sample_filtered_kernel, dim3(blocks_for(rows)), dim3(256), 0, as_stream(stream), w, rows, cols, u, inv_temperature, top_k,
-                 filter->top_p, filter->allow, idx);
+                 filter->top_p, filter->allow, (int64_t)0, idx);
+    return check_launch("row_sample_filtered_kernel");
+}
+
+extern "C" int arvae_row_sample_planned(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature,
+                                        const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, int32_t ticks, int32_t tick,
+                                        int64_t *idx, arvae_stream_t stream) {
+    int top_k = 0;
+    bool active = false;
+    if (const int rc = sample_filter_check("row_sample_planned", filter, cols, &top_k, &active)) return rc;
+    ARVAE_REQUIRE(filter->allow == nullptr, "row_sample_planned: filter->allow is set (with a plan the allowed mask is folded into the plan)");
+    ARVAE_REQUIRE(w && u && idx && rows > 0 && cols > 0, "row_sample_planned: bad argument (null pointer or empty problem)");
+    if (const int rc = note_plan_check("row_sample_planned", plan, ticks, cols)) return rc;
+    ARVAE_REQUIRE(tick >= 0 && tick < ticks, "row_sample_planned: tick %d is outside [0, %d)", tick, ticks);
+    ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f,
+                  "row_sample_planned: inverse temperature %f is not a positive finite number", (double)inv_temperature);
+    ARVAE_LAUNCH(row_sample_filtered_kernel, dim3(blocks_for(rows)), dim3(256), 0, as_stream(stream), w, rows, cols, u, inv_temperature, top_k,
+                 filter->top_p, plan->allow + tick * plan->tick_stride, plan->row_stride, idx);
     return check_launch("row_sample_filtered_kernel");
 }
 

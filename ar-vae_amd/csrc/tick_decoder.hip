@@ -9,7 +9,8 @@
 //   layer 1: r,z: W_ih1 mid + W_hh1 h1 in one accumulator each; n: the two products apart -> gates -> h1'
 //   logits = relu(W_out h1' + b_out) on waves 0..ceil(V/16)-1, the row's pick (PICK_ARGMAX: lowest index on ties) through DPP rows
 //            and LDS -> token, fed back.  (PICK_MULTINOMIAL: a drawn note; PICK_FILTERED: drawn among the notes a mask, a top-k and a
-//            nucleus cut leave -- tick_filtered_pick.)
+//            nucleus cut leave -- tick_filtered_pick; PICK_PLANNED: the same with the mask read per (row, tick) from a note plan, so
+//            that a tick with one allowed note forces it and the forced note is what the next tick is fed: infilling.)
 // The products run on the fp16 MFMA with the scaled two-term operands of gru_seq_fwd_h2_kernel (splitmath.h); the recurrent matrices
 // are split and laid out for streaming by one prep pair per call (tick_amax_kernel, tick_prep_kernel) into the caller's workspace.
 // Two kernels: tick_free_run_h2_kernel for the reference's two layers, tick_free_run_layers_kernel behind it for one, three and four.
@@ -76,7 +77,8 @@ __device__ __forceinline__ float row16_prefix(float v) {
 
 // what the free-running kernel feeds back (measurevae/decoder.py:502-516): the top-1 note, or a note drawn from softmax(logits / T)
 // PICK_FILTERED: the multinomial draw over the notes a mask, a top-k and a nucleus (top-p) cut leave (generation only: no keep-masks)
-constexpr int PICK_ARGMAX = 0, PICK_MULTINOMIAL = 1, PICK_FILTERED = 2;
+// PICK_PLANNED: PICK_FILTERED's draw with the allowed notes read per (row, tick) from a note plan (arvae_note_plan_t): infilling
+constexpr int PICK_ARGMAX = 0, PICK_MULTINOMIAL = 1, PICK_FILTERED = 2, PICK_PLANNED = 3;
 // the draws of PICK_MULTINOMIAL: u [batch][ticks] in (0, 1] and 1 / T (null and unused for PICK_ARGMAX)
 struct TickSample {
     const float *u;
@@ -91,8 +93,24 @@ struct TickFilter {
     float top_p;
     const uint8_t *allow;
 };
+// PICK_PLANNED's: the draws and the cuts as TickFilter's; allow[row * row_stride + tick * tick_stride + note] != 0: the note may be
+// emitted by that row at that tick (strides in bytes, 0 = the same for every row / tick).  Again a type of its own.
+struct TickPlan {
+    const float *u;
+    float inv_t;
+    int top_k;
+    float top_p;
+    const uint8_t *allow;
+    int64_t row_stride, tick_stride;
+};
 template <int PICK> struct TickPick { using type = TickSample; };
 template <> struct TickPick<PICK_FILTERED> { using type = TickFilter; };
+template <> struct TickPick<PICK_PLANNED> { using type = TickPlan; };
+// the picks that publish a row's logits to LDS and rank them behind the barrier (tick_filtered_pick)
+template <int PICK> constexpr bool tick_row_pick = PICK == PICK_FILTERED || PICK == PICK_PLANNED;
+// the cuts of either as tick_filtered_pick takes them (it does not read `allow`: the banned notes are -1 in the row by then)
+__device__ __forceinline__ const TickFilter &tick_cuts(const TickFilter &f) { return f; }
+__device__ __forceinline__ TickFilter tick_cuts(const TickPlan &f) { return TickFilter{f.u, f.inv_t, f.top_k, f.top_p, nullptr}; }
 
 // PICK_FILTERED behind the barrier.  The tile waves have published the row's logits to LDS: `lg` = the row's FLT_LS floats, banned
 // notes and notes past the vocabulary as -1 (below every relu output), columns past the last tile -1 from the kernel's start.  The 16
@@ -201,7 +219,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     __shared__ int cand_i[4][16];
     __shared__ float smp_max[4][16];               // PICK_MULTINOMIAL: [tile][row] maximum, [tile][row][note] inclusive prefixes of e
     __shared__ float smp_pre[4][16][16];
-    __shared__ __attribute__((aligned(16))) float flt_lg[PICK == PICK_FILTERED ? 16 * FLT_LS : 4];   // PICK_FILTERED: [row] the logits
+    __shared__ __attribute__((aligned(16))) float flt_lg[tick_row_pick<PICK> ? 16 * FLT_LS : 4];   // PICK_FILTERED, PICK_PLANNED: [row] the logits
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
@@ -237,6 +255,8 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
     bool note_on = note_ok;                                    // PICK_FILTERED: the note may be emitted
     if constexpr (PICK == PICK_FILTERED) {
         if (note_ok && smp.allow != nullptr) note_on = smp.allow[note] != 0;
+    }
+    if constexpr (tick_row_pick<PICK>) {
         for (int e = threadIdx.x; e < 16 * FLT_LS; e += H * 4) flt_lg[e] = -1.f;    // (columns past the last tile stay -1)
     }
 
@@ -339,6 +359,14 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
 #pragma unroll
             for (int i = 0; i < E; ++i) un[i] = fminf(fmaxf(smp.u[(int64_t)rows[i] * ticks + t], 0.f), 1.f);
         }
+        // PICK_PLANNED: the tick's plan bytes of the lane's note, one per row element, requested here at the tick's top: they do not
+        // depend on the recurrence, so their latency lies under the layers' products and not in front of the logits' barrier.  Raw
+        // until the logits are published (converted here they would be waited for at once)
+        [[maybe_unused]] unsigned plan_b[PICK == PICK_PLANNED ? E : 1];
+        if constexpr (PICK == PICK_PLANNED) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) plan_b[i] = smp.allow[rows[i] * smp.row_stride + t * smp.tick_stride + (note_ok ? note : 0)];
+        }
         TSTAMP(0);                                             // tick top: a beat's state; the token's projections requested
         // ---- layer 0: matrix 0 (multiplied at the end of the previous tick unless a beat starts)
         {
@@ -436,6 +464,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                         for (int i = 0; i < E; ++i) flt_lg[lrow(i) * FLT_LS + note] = note_on ? fmaxf(lv[i] + bout, 0.f) : -1.f;
                         return;
                     }
+                    if constexpr (PICK == PICK_PLANNED) {      // the same, the note's flag this row's at this tick
+#pragma unroll
+                        for (int i = 0; i < E; ++i) flt_lg[lrow(i) * FLT_LS + note] = note_ok && plan_b[i] != 0 ? fmaxf(lv[i] + bout, 0.f) : -1.f;
+                        return;
+                    }
 #pragma unroll
                     for (int i = 0; i < E; ++i) { v[i] = note_ok ? fmaxf(lv[i] + bout, 0.f) : -1.f; ix[i] = note; }
 #pragma unroll
@@ -512,10 +545,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_h2_kernel(TickFreeRun p, 
                 tok[i] = ix;
                 if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
             }
-        } else if constexpr (PICK == PICK_FILTERED) {
+        } else if constexpr (tick_row_pick<PICK>) {
+            const auto cuts = tick_cuts(smp);
 #pragma unroll
             for (int i = 0; i < E; ++i) {
-                const int ix = tick_filtered_pick(&flt_lg[lrow(i) * FLT_LS], col, quad, 16 * ntile, un[i], smp, p.vocab);
+                const int ix = tick_filtered_pick(&flt_lg[lrow(i) * FLT_LS], col, quad, 16 * ntile, un[i], cuts, p.vocab);
                 tok[i] = ix;
                 if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
             }
@@ -594,7 +628,7 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
     __shared__ int cand_i[4][16];
     __shared__ float smp_max[4][16];
     __shared__ float smp_pre[4][16][16];
-    __shared__ __attribute__((aligned(16))) float flt_lg[PICK == PICK_FILTERED ? 16 * FLT_LS : 4];   // PICK_FILTERED: [row] the logits
+    __shared__ __attribute__((aligned(16))) float flt_lg[tick_row_pick<PICK> ? 16 * FLT_LS : 4];   // PICK_FILTERED, PICK_PLANNED: [row] the logits
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
@@ -636,6 +670,8 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
     bool note_on = note_ok;                                    // PICK_FILTERED: the note may be emitted
     if constexpr (PICK == PICK_FILTERED) {
         if (note_ok && smp.allow != nullptr) note_on = smp.allow[note] != 0;
+    }
+    if constexpr (tick_row_pick<PICK>) {
         for (int e = threadIdx.x; e < 16 * FLT_LS; e += H * 4) flt_lg[e] = -1.f;    // (columns past the last tile stay -1)
     }
 
@@ -772,6 +808,14 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
 #pragma unroll
             for (int i = 0; i < E; ++i) un[i] = fminf(fmaxf(smp.u[(int64_t)rows[i] * ticks + t], 0.f), 1.f);
         }
+        // PICK_PLANNED: the tick's plan bytes of the lane's note, one per row element, requested here at the tick's top: they do not
+        // depend on the recurrence, so their latency lies under the layers' products and not in front of the logits' barrier.  Raw
+        // until the logits are published (converted here they would be waited for at once)
+        [[maybe_unused]] unsigned plan_b[PICK == PICK_PLANNED ? E : 1];
+        if constexpr (PICK == PICK_PLANNED) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) plan_b[i] = smp.allow[rows[i] * smp.row_stride + t * smp.tick_stride + (note_ok ? note : 0)];
+        }
         // ---- layer 0: matrix 0 on its own state, the input projections from the token
         {
             f32x4 a0[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -824,6 +868,9 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
             } else if constexpr (PICK == PICK_FILTERED) {      // the row's logits to LDS, banned notes as -1
 #pragma unroll
                 for (int i = 0; i < E; ++i) flt_lg[lrow(i) * FLT_LS + note] = note_on ? v[i] : -1.f;
+            } else if constexpr (PICK == PICK_PLANNED) {       // the same, the note's flag this row's at this tick
+#pragma unroll
+                for (int i = 0; i < E; ++i) flt_lg[lrow(i) * FLT_LS + note] = note_ok && plan_b[i] != 0 ? v[i] : -1.f;
             } else {
                 int ix[E];
 #pragma unroll
@@ -883,10 +930,11 @@ __global__ __launch_bounds__(H * 4) void tick_free_run_layers_kernel(TickStack p
                 tok[i] = ix;
                 if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
             }
-        } else if constexpr (PICK == PICK_FILTERED) {
+        } else if constexpr (tick_row_pick<PICK>) {
+            const auto cuts = tick_cuts(smp);
 #pragma unroll
             for (int i = 0; i < E; ++i) {
-                const int ix = tick_filtered_pick(&flt_lg[lrow(i) * FLT_LS], col, quad, 16 * ntile, un[i], smp, p.vocab);
+                const int ix = tick_filtered_pick(&flt_lg[lrow(i) * FLT_LS], col, quad, 16 * ntile, un[i], cuts, p.vocab);
                 tok[i] = ix;
                 if (w == 0 && col == 0 && live[i]) p.tokens[(int64_t)rows[i] * ticks + t] = ix;
             }
@@ -949,12 +997,24 @@ static bool tick_h2_launch_filtered(const TickFreeRun &p, const TickPrep &tp, fl
     });
 }
 
+// PICK_PLANNED: as PICK_FILTERED, unmasked kernels only
+template <int HH>
+static bool tick_h2_launch_planned(const TickFreeRun &p, const TickPrep &tp, float *ws, int rw, const TickPlan &pl, hipStream_t st) {
+    const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
+    const dim3 gr((p.batch + rw - 1) / rw);
+    tick_prep_launch<HH>(tp, ws, st);
+    return with_int<4, 8, 16>(rw, [&](auto RW) {
+        ARVAE_LAUNCH((tick_free_run_h2_kernel<HH, false, decltype(RW)::value, PICK_PLANNED>), gr, dim3(4 * HH), 0, st, p, packed, pl);
+    });
+}
+
 // uniforms null: the top-1 note is fed back; else a note drawn at uniforms [batch][ticks] from softmax(logits * inv_temperature), with
-// flt (its draws those of `uniforms`) over the notes the filter leaves
+// flt (its draws those of `uniforms`) over the notes the filter leaves, with pl over the notes its plan leaves per (row, tick)
 static int tick_free_run_launch(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride, const float *gib,
                                 const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
                                 int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
-                                int64_t *tokens, float *ws, arvae_stream_t stream, const TickFilter *flt = nullptr) {
+                                int64_t *tokens, float *ws, arvae_stream_t stream, const TickFilter *flt = nullptr,
+                                const TickPlan *pl = nullptr) {
     ARVAE_REQUIRE(wts && h0_l0 && h0_l1 && gib && ptab && tokens, "tick_free_run: null pointer");
     ARVAE_REQUIRE(wts->w_hh0 && wts->b_hh0 && wts->w_ih1 && wts->b_ih1 && wts->w_hh1 && wts->b_hh1 && wts->w_out && wts->b_out,
                   "tick_free_run: null weight pointer");
@@ -977,7 +1037,8 @@ static int tick_free_run_launch(const arvae_tick_weights_t *wts, const float *h0
     const TickSample smp{uniforms, inv_temperature};
     bool rw_known = false;
     const bool h_known = with_int<128, 64, 32>(hidden, [&](auto HH) {
-        if (flt != nullptr) rw_known = tick_h2_launch_filtered<decltype(HH)::value>(p, tp, ws, rw, *flt, st);
+        if (pl != nullptr) rw_known = tick_h2_launch_planned<decltype(HH)::value>(p, tp, ws, rw, *pl, st);
+        else if (flt != nullptr) rw_known = tick_h2_launch_filtered<decltype(HH)::value>(p, tp, ws, rw, *flt, st);
         else with_bool(mask != nullptr, [&](auto MM) { rw_known = tick_h2_launch<decltype(HH)::value, decltype(MM)::value>(p, tp, ws, rw, smp, st); });
     });
     ARVAE_REQUIRE(h_known && rw_known, "tick_free_run: no kernel for hidden size %d at %d rows per workgroup", hidden, rw);
@@ -1027,6 +1088,37 @@ extern "C" int arvae_tick_free_run_filtered(const arvae_tick_weights_t *wts, con
                                 uniforms, inv_temperature, tokens, ws, stream, &flt);
 }
 
+// what the two planned free runs check beyond the filtered ones, and their kernel argument: the plan, no mask inside the filter
+static int tick_plan_arg(const char *who, const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, const uint8_t *mask,
+                         const float *uniforms, float inv_temperature, int32_t beats, int32_t ticks_per_beat, int32_t vocab, TickPlan *out) {
+    int top_k = 0;
+    bool active = false;
+    if (const int rc = sample_filter_check(who, filter, vocab, &top_k, &active)) return rc;
+    ARVAE_REQUIRE(filter->allow == nullptr, "%s: filter->allow is set (with a plan the allowed mask is folded into the plan)", who);
+    ARVAE_REQUIRE(beats >= 1 && ticks_per_beat >= 1, "%s: empty problem", who);
+    if (const int rc = note_plan_check(who, plan, (int64_t)beats * ticks_per_beat, vocab)) return rc;
+    ARVAE_REQUIRE(uniforms != nullptr, "%s: null uniforms", who);
+    ARVAE_REQUIRE(mask == nullptr, "%s: a dropout keep-mask was given together with a plan (generation runs with dropout off: the planned "
+                                   "kernels are built without masks)", who);
+    ARVAE_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0.f, "%s: inverse temperature %f is not a positive finite number", who,
+                  (double)inv_temperature);
+    *out = TickPlan{uniforms, inv_temperature, top_k, filter->top_p, plan->allow, plan->row_stride, plan->tick_stride};
+    return ARVAE_OK;
+}
+
+extern "C" int arvae_tick_free_run_planned(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                           const float *gib, const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch,
+                                           int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
+                                           float inv_temperature, const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan,
+                                           int64_t *tokens, float *ws, arvae_stream_t stream) {
+    TickPlan pl{};
+    if (const int rc = tick_plan_arg("tick_free_run_planned", filter, plan, mask, uniforms, inv_temperature, beats, ticks_per_beat, vocab, &pl))
+        return rc;
+    ARVAE_REQUIRE(ws != nullptr, "tick_free_run_planned: null workspace (arvae_tick_free_run_ws_floats)");
+    return tick_free_run_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, nullptr, keep_scale, batch, beats, ticks_per_beat, hidden, vocab,
+                                uniforms, inv_temperature, tokens, ws, stream, nullptr, &pl);
+}
+
 // ---- layer counts other than two (tick_free_run_layers_kernel) ----------------------------------------------------
 static int tick_stack_matrices(int layers) { return 2 * layers - 1; }
 
@@ -1066,10 +1158,21 @@ static bool tick_stack_launch_filtered(const TickStack &p, const TickPrep &tp, f
     });
 }
 
-// flt: PICK_FILTERED over its cuts (its draws those of `uniforms`), else the pick `uniforms` selects
+template <int HH, int LL>
+static bool tick_stack_launch_planned(const TickStack &p, const TickPrep &tp, float *ws, int rw, const TickPlan &pl, hipStream_t st) {
+    const uint4 *packed = reinterpret_cast<const uint4 *>(ws);
+    const dim3 gr((p.batch + rw - 1) / rw);
+    tick_prep_launch<HH>(tp, ws, st);
+    return with_int<4, 8, 16>(rw, [&](auto RW) {
+        ARVAE_LAUNCH((tick_free_run_layers_kernel<HH, LL, decltype(RW)::value, PICK_PLANNED>), gr, dim3(4 * HH), 0, st, p, packed, pl);
+    });
+}
+
+// pl: PICK_PLANNED; flt: PICK_FILTERED over its cuts (its draws those of `uniforms`), else the pick `uniforms` selects
 static int tick_layers_launch(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask, float keep_scale,
                               int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
-                              float inv_temperature, int64_t *tokens, float *ws, arvae_stream_t stream, const TickFilter *flt) {
+                              float inv_temperature, int64_t *tokens, float *ws, arvae_stream_t stream, const TickFilter *flt,
+                              const TickPlan *pl = nullptr) {
     ARVAE_REQUIRE(stack && gib && ptab && tokens, "tick_free_run_layers: null pointer");
     ARVAE_REQUIRE(ws != nullptr, "tick_free_run_layers: null workspace (arvae_tick_free_run_layers_ws_floats)");
     const int layers = stack->layers;
@@ -1115,7 +1218,9 @@ static int tick_layers_launch(const arvae_tick_stack_t *stack, const float *gib,
             constexpr int H = decltype(HH)::value, L = decltype(LL)::value;
             // (hidden 128 with three or four layers is not built: arvae_tick_free_run_layers_supported)
             if constexpr (H != 128 || L == 1)
-                launched = flt != nullptr ? tick_stack_launch_filtered<H, L>(p, tp, ws, rw, *flt, st) : tick_stack_launch<H, L>(p, tp, ws, rw, smp, st);
+                launched = pl != nullptr    ? tick_stack_launch_planned<H, L>(p, tp, ws, rw, *pl, st)
+                           : flt != nullptr ? tick_stack_launch_filtered<H, L>(p, tp, ws, rw, *flt, st)
+                                            : tick_stack_launch<H, L>(p, tp, ws, rw, smp, st);
         });
     });
     ARVAE_REQUIRE(launched, "tick_free_run_layers: no kernel for %d layers of hidden size %d at %d rows per workgroup", layers, hidden, rw);
@@ -1145,3 +1250,15 @@ extern "C" int arvae_tick_free_run_layers_filtered(const arvae_tick_stack_t *sta
                               tokens, ws, stream, active ? &flt : nullptr);
 }
 
+extern "C" int arvae_tick_free_run_layers_planned(const arvae_tick_stack_t *stack, const float *gib, const float *ptab, const uint8_t *mask,
+                                                  float keep_scale, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
+                                                  int32_t vocab, const float *uniforms, float inv_temperature,
+                                                  const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, int64_t *tokens,
+                                                  float *ws, arvae_stream_t stream) {
+    TickPlan pl{};
+    if (const int rc = tick_plan_arg("tick_free_run_layers_planned", filter, plan, mask, uniforms, inv_temperature, beats, ticks_per_beat,
+                                     vocab, &pl))
+        return rc;
+    return tick_layers_launch(stack, gib, ptab, nullptr, keep_scale, batch, beats, ticks_per_beat, hidden, vocab, uniforms, inv_temperature,
+                              tokens, ws, stream, nullptr, &pl);
+}

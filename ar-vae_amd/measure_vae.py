@@ -309,6 +309,7 @@ class HierarchicalDecoder(Decoder):
         self._mask_queue = deque()
         self._uniform_queue = deque()
         self._filter = None                                    # (top_k, top_p, allowed on the device) while `generate` runs with cuts
+        self._plan = None                                      # (top_k, top_p, plan (B, 24, V) on the device) while it runs with a note plan
 
     def __repr__(self):
         return f'{self.name}{self.note_embedding_dim},{self.rnn_class},{self.num_layers},{self.rnn_hidden_size},{self.dropout},)'
@@ -418,16 +419,57 @@ class HierarchicalDecoder(Decoder):
             allowed = mask.to(torch.uint8).contiguous()
         return top_k, top_p, allowed
 
-    def generate(self, z, sampling='multinomial', temperature=1.0, uniforms=None, top_k=None, top_p=None, allowed=None):
+    def note_plan(self, plan, batch, allowed=None):
+        """a note plan, validated on the host (the one place, as `sampling_filter` is for the cuts): plan[b, t, v] set = note v may be
+        emitted for row b at tick t; (24, V) = the same plan for every row, or (B, 24, V); flags (bool or 0 / 1 integers: tensor, array
+        or nested sequence).  Intersected with `allowed` (V flags) where given; every tick must keep a note.  A tick with one note
+        forces it.  -> uint8 CPU tensor (B, 24, V), or None for no plan -- and for a plan of all ones, which is the call without one."""
+        if plan is None:
+            return None
+        v, ticks = self.num_notes, 24
+        mask = torch.as_tensor(plan).detach().cpu()
+        if mask.dtype.is_floating_point or mask.dtype.is_complex:
+            raise TypeError(f'a note plan must hold flags (bool or 0 / 1 integers), got {mask.dtype}')
+        if tuple(mask.shape) == (v,):
+            raise ValueError(f'a note plan has one mask per tick, shape ({ticks}, {v}) or ({batch}, {ticks}, {v}); a ({v},) mask for every '
+                             f'tick is `allowed`')
+        if tuple(mask.shape) not in ((ticks, v), (batch, ticks, v)):
+            raise ValueError(f'a note plan must have shape ({ticks}, {v}) or ({batch}, {ticks}, {v}), got {tuple(mask.shape)}')
+        if mask.dtype != torch.bool and bool(((mask != 0) & (mask != 1)).any()):
+            raise ValueError('a note plan must hold flags (0 or 1)')
+        mask = mask != 0
+        if bool(mask.all()):
+            return None
+        flt = self.sampling_filter(None, None, allowed)
+        if flt is not None:
+            mask = mask & (flt[2] != 0)
+        empty = (~mask.any(-1)).nonzero()
+        if empty.numel():
+            where = tuple(int(i) for i in empty[0])
+            raise ValueError(f'the note plan leaves no note at {"tick" if len(where) == 1 else "(row, tick)"} {where if len(where) > 1 else where[0]}'
+                             f'{" after the intersection with `allowed`" if flt is not None else ""}')
+        return mask.expand(batch, ticks, v).to(torch.uint8).contiguous()
+
+    def generate(self, z, sampling='multinomial', temperature=1.0, uniforms=None, top_k=None, top_p=None, allowed=None, plan=None):
         """Free-running decode of latent codes z (B, z_dim) without autograd and with dropout off: -> (weights (B, 24, V), samples
         (B, 1, 24)).  sampling 'multinomial' draws every fed-back note from softmax(probs / temperature) (uniforms: explicit (B, 24)
         draws in (0, 1], else one launch of the library's generator); 'argmax' feeds the top-1 note back.
         top_k / top_p / allowed (multinomial only; `sampling_filter`): the draw is over the notes that survive -- allowed[v] set, fewer
         than top_k allowed notes ordered before v (descending logit, ties to the lower index), and those notes' share of the softmax
         mass below top_p (the first note always survives); include/arvae_hip.h, arvae_sample_filter_t.  The returned weights are
-        the unfiltered logits."""
+        the unfiltered logits.
+        plan (`note_plan`): the allowed notes per (row, tick), intersected with `allowed`; the rule above with that set at every tick.
+        With a plan 'argmax' is accepted too: the allowed note with the largest logit (the top_k = 1 rule; no draw is consumed).  The
+        note fed back is the emitted one, forced or chosen."""
         if sampling not in ('argmax', 'multinomial'):
             raise NotImplementedError(f'sampling {sampling!r}: argmax and multinomial are implemented')
+        planned = self.note_plan(plan, z.size(0), allowed)
+        if planned is not None:
+            if sampling == 'argmax' and (top_k is not None or top_p is not None):
+                raise ValueError('top_k and top_p cut the multinomial draw: under a plan, argmax takes the best allowed note')
+            top_k, top_p = check_sampling_cuts(top_k, top_p, self.num_notes)
+            planned = (top_k, top_p, planned.to(z.device))     # the one upload of the call
+            top_k = top_p = allowed = None
         flt = self.sampling_filter(top_k, top_p, allowed)
         if flt is not None and sampling != 'multinomial':
             raise ValueError('top_k, top_p and allowed cut the multinomial draw: they need sampling=\'multinomial\'')
@@ -437,14 +479,14 @@ class HierarchicalDecoder(Decoder):
         saved = (self.sampling, self.temperature, self.use_teacher_forcing, self.training)
         self.sampling, self.temperature, self.use_teacher_forcing = sampling, float(temperature), False
         self.train(False)
-        self._filter = flt
+        self._filter, self._plan = flt, planned
         try:
             if uniforms is not None and sampling == 'multinomial':
                 self.push_sampling_uniforms(uniforms)
             with torch.no_grad():
                 return self.forward(z, dummy, sampling == 'multinomial')      # train=True is what lets `sampling` apply
         finally:
-            self._filter = None
+            self._filter = self._plan = None
             self.sampling, self.temperature, self.use_teacher_forcing = saved[:3]
             self.train(saved[3])
 
@@ -486,10 +528,11 @@ class HierarchicalDecoder(Decoder):
             return self.tick_rnn_sequence(tokens, beat_out, 6, True)[0]
         return self.forward_tick_rnn(tokens, list(torch.unbind(beat_out, 0)), 6, True, 'argmax')[0]
 
-    def _beam_history(self, beat_out, width, mask, count):
+    def _beam_history(self, beat_out, width, mask, count, plan=None):
         """-> (parents (B, 24, W) int32, tokens (B, 24, W) int64, scores (B, 24, W), sequences (B, W, 24) int64, scores (B, W)): one
         launch (csrc/beam_decoder.hip, tick_beam_search_kernel) where it is offered, else tick by tick with the existing dense and
-        gate launches, ops.beam_select and a gather of the states (ARVAE_TICK_STEPWISE=1, other layer counts, hidden sizes, V > 64)."""
+        gate launches, ops.beam_select and a gather of the states (ARVAE_TICK_STEPWISE=1, other layer counts, hidden sizes, V > 64).
+        plan (B, 24, V) uint8 on the device: the planned forms of both (mask and count are then not read)."""
         nb, b, hid = beat_out.shape
         layers, vocab = self.num_layers, self.num_notes
         h0, beat_emb = self._tick_restart(beat_out.reshape(nb * b, hid))
@@ -504,6 +547,8 @@ class HierarchicalDecoder(Decoder):
             ptab = ops.dense(table, w_note, None, Link.dense(emb_dim, 3 * hid), ACT_NONE)
             w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
             weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias)
+            if plan is not None:
+                return ops.tick_beam_search_planned(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, plan)
             return ops.tick_beam_search(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, mask, count)
         dev = beat_out.device
         rows = torch.arange(b, device=dev).repeat_interleave(width)               # row (code, k) -> code
@@ -518,7 +563,11 @@ class HierarchicalDecoder(Decoder):
                 gi0 = ops.dense(ops.concat_cols(prev, be), w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
                 h = self._stack_step(self.rnn_tick, gi0, h, None)
                 probs = _lin(h[-1], out, ACT_RELU)
-                par, note, scores = ops.beam_select(probs, scores, 1 if i == 0 and j == 0 else width, mask, count)
+                live = 1 if i == 0 and j == 0 else width
+                if plan is not None:
+                    par, note, scores = ops.beam_select_planned(probs, scores, live, plan, i * 6 + j)
+                else:
+                    par, note, scores = ops.beam_select(probs, scores, live, mask, count)
                 src = (base + par.to(torch.int64)).reshape(-1)
                 h = [s.index_select(0, src) for s in h]
                 prev = ops.embed(note.view(b * width, 1), self.note_embedding_layer.weight).view(b * width, -1)
@@ -531,26 +580,45 @@ class HierarchicalDecoder(Decoder):
             at = parents[:, t].to(torch.int64).gather(1, at)
         return parents, tokens, hist, torch.stack(seq[::-1], 2), scores
 
-    def beam_search(self, z, beam_width=4, allowed=None, return_history=False):
+    def beam_search(self, z, beam_width=4, allowed=None, return_history=False, plan=None):
         """The beam_width most likely measures of latent codes z (B, z_dim) under the decoder, without autograd and with dropout off
         (include/arvae_hip.h, "Beam search"): -> (weights (B, 24, V), samples (B, 1, 24), scores (B,)) of the best beam -- the weights
         from the whole-sequence kernels evaluated on its tokens --, sequences (B, W, 24) best first and scores (B, W) = their
         log p(x | z) over the allowed notes; return_history=True: also (parents (B, 24, W) int32, tokens (B, 24, W), scores (B, 24, W)).
-        allowed: a mask of V flags (`sampling_filter`), at least beam_width of them set."""
-        width, mask, count = self._beam_mask(beam_width, allowed, z.device)
+        allowed: a mask of V flags (`sampling_filter`), at least beam_width of them set.
+        plan (`note_plan`): the allowed notes per (row, tick), intersected with `allowed`; the candidates and the softmax of a tick are
+        over that set.  Fewer than beam_width hypotheses may then exist (a forced first tick leaves one): the slots without one are
+        dead -- score -inf, listed last, their tokens inside the plan -- and beam_width need not be below the allowed notes' count."""
+        planned = self.note_plan(plan, z.size(0), allowed)
+        if planned is not None:
+            if isinstance(beam_width, bool) or not isinstance(beam_width, numbers.Integral):
+                raise TypeError(f'beam_width must be an integer, got {type(beam_width).__name__}')
+            if not 1 <= beam_width <= 16:
+                raise ValueError(f'beam_width must lie in [1, 16], got {beam_width}')
+            width, mask, count = int(beam_width), None, None
+            planned = planned.to(z.device)                     # the one upload of the call
+        else:
+            width, mask, count = self._beam_mask(beam_width, allowed, z.device)
 
         def run():
             beat_out = self._beats(z)
-            parents, tokens, hist, seqs, scores = self._beam_history(beat_out, width, mask, count)
+            parents, tokens, hist, seqs, scores = self._beam_history(beat_out, width, mask, count, planned)
             best = seqs[:, 0].contiguous()
             weights = self._teacher_forced_weights(beat_out, best)
             res = (weights, best[:, None, :], scores[:, 0].contiguous(), seqs, scores)
             return res + ((parents, tokens, hist),) if return_history else res
         return self._eval_no_grad(run)
 
-    def score_tokens(self, z, tokens, allowed=None):
+    def score_tokens(self, z, tokens, allowed=None, plan=None):
         """log p(tokens | z) (B,) under teacher forcing, the softmax over the allowed notes (ops.sequence_log_prob on the
-        whole-sequence kernels' weights); tokens (B, 24) or (B, 1, 24) int64.  Without autograd, dropout off."""
+        whole-sequence kernels' weights); tokens (B, 24) or (B, 1, 24) int64.  Without autograd, dropout off.
+        plan (`note_plan`): the softmax of a tick over that (row, tick)'s notes; a token outside them gives -inf."""
+        planned = self.note_plan(plan, z.size(0), allowed)
+        if planned is not None:
+            planned = planned.to(z.device)
+            tokens = torch.as_tensor(tokens, device=z.device).reshape(z.size(0), 24).to(torch.int64).contiguous()
+            return self._eval_no_grad(lambda: ops.sequence_log_prob_planned(
+                self._teacher_forced_weights(self._beats(z), tokens).contiguous(), tokens, planned))
         flt = self.sampling_filter(None, None, allowed)
         mask = None if flt is None else flt[2].to(z.device)
         tokens = torch.as_tensor(tokens, device=z.device).reshape(z.size(0), 24).to(torch.int64).contiguous()
@@ -637,8 +705,12 @@ class HierarchicalDecoder(Decoder):
         one_launch = not stepwise and (ops.tick_free_run_supported(hid, self.num_notes) if layers == 2 else
                                        ops.tick_free_run_layers_supported(hid, self.num_notes, layers))
         flt = self._filter if uniforms is not None else None   # `generate`'s cuts; dropout is off there: no keep-masks
-        if flt is not None and mask is not None:
+        planned = self._plan                                   # `generate`'s note plan: draws, or with no draws its argmax (top_k = 1)
+        if (flt is not None or planned is not None) and mask is not None:
             raise RuntimeError('filtered sampling runs with dropout off')
+        if planned is not None:
+            top_k, top_p, plan = planned if uniforms is not None else (1, None, planned[2])
+            draws = uniforms if uniforms is not None else torch.ones(b, nb * 6, device=beat_out.device)
         if one_launch:
             # one launch (csrc/tick_decoder.hip: tick_free_run_h2_kernel for two layers, tick_free_run_layers_kernel otherwise).  W_ih0
             # acts on [previous-note embedding | beat embedding]: the beat half is applied once per beat, the note half once per
@@ -653,6 +725,9 @@ class HierarchicalDecoder(Decoder):
             if layers == 2:
                 w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
                 weights = tuple(t.detach() for t in (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias))
+                if planned is not None:
+                    return ops.tick_free_run_planned(weights, h0[0].detach(), h0[1].detach(), gib, ptab, b, nb, 6, draws, plan,
+                                                     self.temperature, top_k, top_p)
                 if flt is not None:
                     return ops.tick_free_run_filtered(weights, h0[0].detach(), h0[1].detach(), gib, ptab, b, nb, 6, uniforms,
                                                       self.temperature, *flt)
@@ -660,6 +735,9 @@ class HierarchicalDecoder(Decoder):
                                          None if mask is None else mask[0].contiguous(), keep_scale, b, nb, 6,
                                          uniforms=uniforms, temperature=self.temperature)
             cells = [tuple(t.detach() for t in self.rnn_tick.cell(k)) for k in range(layers)]     # the boundaries' masks: (layers-1, 24, B, H)
+            if planned is not None:
+                return ops.tick_free_run_layers_planned(cells, out.weight.detach(), out.bias.detach(), [s.detach() for s in h0], gib, ptab,
+                                                        b, nb, 6, draws, plan, self.temperature, top_k, top_p)
             if flt is not None:
                 return ops.tick_free_run_layers_filtered(cells, out.weight.detach(), out.bias.detach(), [s.detach() for s in h0], gib, ptab,
                                                          b, nb, 6, uniforms, self.temperature, *flt)
@@ -676,7 +754,9 @@ class HierarchicalDecoder(Decoder):
                 gi0 = ops.dense(ops.concat_cols(prev, be), w_ih0, b_ih0, Link.dense(w_ih0.shape[1], w_ih0.shape[0]), ACT_NONE)
                 h = self._stack_step(self.rnn_tick, gi0, h, None if mask is None else [k[t].contiguous() for k in mask])
                 probs = _lin(h[-1], self.tick_emb_to_note_emb[0], ACT_RELU)
-                if flt is not None:
+                if planned is not None:
+                    idx = ops.row_sample_planned(probs, draws[:, t].contiguous(), plan, t, self.temperature, top_k, top_p)
+                elif flt is not None:
                     idx = ops.row_sample_filtered(probs, uniforms[:, t].contiguous(), self.temperature, *flt)
                 else:
                     idx = ops.row_argmax(probs) if uniforms is None else ops.row_sample(probs, uniforms[:, t].contiguous(), self.temperature)
@@ -716,6 +796,10 @@ class HierarchicalDecoder(Decoder):
                 probs = _lin(h[-1], self.tick_emb_to_note_emb[0], ACT_RELU)
                 if self.use_teacher_forcing and teacher_forced:
                     idx = score_tensor[:, t].contiguous()
+                elif self._plan is not None and sampling == 'multinomial':
+                    idx = ops.row_sample_planned(probs.detach(), uniforms[:, t].contiguous(), self._plan[2], t, self.temperature, *self._plan[:2])
+                elif self._plan is not None:                   # the plan's argmax: top_k = 1, the draw without effect
+                    idx = ops.row_sample_planned(probs.detach(), torch.ones(b, device=probs.device), self._plan[2], t, 1.0, 1, None)
                 elif sampling == 'multinomial' and self._filter is not None:
                     idx = ops.row_sample_filtered(probs.detach(), uniforms[:, t].contiguous(), self.temperature, *self._filter)
                 elif sampling == 'multinomial':

@@ -281,37 +281,110 @@ class MeasureVAETrainer(Trainer):
             mask = mask & self.model.decoder.sampling_filter(allowed=allowed)[2]
         return mask
 
+    @staticmethod
+    def _check_beam_draws_nothing(sampling, temperature, uniforms, top_k, top_p):
+        if sampling == 'beam':
+            given = [n for n, on in (('top_k', top_k is not None), ('top_p', top_p is not None), ('temperature', temperature != 1.0),
+                                     ('uniforms', uniforms is not None)) if on]
+            if given:
+                raise ValueError(f"sampling='beam' draws nothing: {', '.join(given)} cannot be combined with it")
+
     def decode_latent_codes(self, latent_codes, sampling='argmax', temperature=1.0, uniforms=None, top_k=None, top_p=None, allowed=None,
-                            playable=False, beam_width=4):
+                            playable=False, beam_width=4, plan=None):
         """(n, z_dim) latent codes -> (music21 score or None, note indices (n, 1, 24) int64): the decoder alone, free-running
         (measure_vae_trainer.py:281-288).  The score object needs the dataset's music21 converter (`tensor_to_m21score`);
         datasets without one (the device-resident loaders here) give None.  sampling='multinomial': every fed-back note is drawn
         from softmax(probs / temperature) (HierarchicalDecoder.generate; uniforms: explicit (n, 24) draws) instead of the top-1;
         top_k / top_p / allowed cut that draw (generate), playable=True keeps START, END and None out of it (playable_mask).
         sampling='beam': the most likely measure of every code among beam_width beams over the allowed / playable notes
-        (HierarchicalDecoder.beam_search); nothing is drawn, so top_k, top_p, temperature and uniforms are refused with it."""
+        (HierarchicalDecoder.beam_search); nothing is drawn, so top_k, top_p, temperature and uniforms are refused with it.
+        plan: a note plan (24, V) or (n, 24, V) (HierarchicalDecoder.note_plan; `build_note_plan`), honoured by all three modes and
+        intersected with allowed / playable; with it 'argmax' takes the best allowed note."""
         dev = next(self.model.parameters()).device
         z = torch.as_tensor(latent_codes, dtype=torch.float32, device=dev).contiguous()
-        if sampling == 'beam':
-            given = [n for n, on in (('top_k', top_k is not None), ('top_p', top_p is not None), ('temperature', temperature != 1.0),
-                                     ('uniforms', uniforms is not None)) if on]
-            if given:
-                raise ValueError(f"sampling='beam' draws nothing: {', '.join(given)} cannot be combined with it")
+        self._check_beam_draws_nothing(sampling, temperature, uniforms, top_k, top_p)
         if playable:
             allowed = self.playable_mask(allowed)
         if sampling == 'beam':
-            tensor_score = self.model.decoder.beam_search(z, beam_width=beam_width, allowed=allowed)[1]
+            tensor_score = self.model.decoder.beam_search(z, beam_width=beam_width, allowed=allowed, plan=plan)[1]
             to_score = getattr(self.dataset, 'tensor_to_m21score', None)
             return (to_score(tensor_score) if callable(to_score) else None), tensor_score
-        if sampling == 'argmax' and top_k is None and top_p is None and allowed is None:
+        if sampling == 'argmax' and top_k is None and top_p is None and allowed is None and plan is None:
             dummy = torch.zeros(z.size(0), self.model.num_ticks_per_measure, dtype=torch.int64, device=dev)
             with torch.no_grad():
                 _, tensor_score = self.model.decoder(z, dummy, False)
         else:
             _, tensor_score = self.model.decoder.generate(z, sampling=sampling, temperature=temperature, uniforms=uniforms, top_k=top_k,
-                                                          top_p=top_p, allowed=allowed)
+                                                          top_p=top_p, allowed=allowed, plan=plan)
         to_score = getattr(self.dataset, 'tensor_to_m21score', None)
         return (to_score(tensor_score) if callable(to_score) else None), tensor_score
+
+    def build_note_plan(self, score=None, keep=None, keep_rhythm=False, allowed=None, playable=False):
+        """A note plan (n, 24, V) -- or (24, V) without a score -- for decode_latent_codes / infill_measures, as a bool CPU tensor.
+        score (n, 24) or (n, 1, 24) note indices: the measures to keep parts of.  keep: bool (24,) or (n, 24), the ticks whose note of
+        `score` is fixed (forced: that note is the only one allowed there).  keep_rhythm=True: a tick where `score` holds the slur
+        '__' is forced to '__', and at every other tick '__' is banned, so onsets stay onsets.  allowed (V flags) / playable
+        (playable_mask) apply at the free ticks only: a forced note stands even if it is not playable."""
+        v, ticks = len(self.dataset.index2note_dicts), 24
+        free = torch.ones(v, dtype=torch.bool)
+        if playable:
+            free = self.playable_mask(allowed) != 0
+        elif allowed is not None:
+            free = self.model.decoder.sampling_filter(allowed=allowed)[2] != 0
+        if score is None:
+            if keep is not None or keep_rhythm:
+                raise ValueError('keep and keep_rhythm fix notes of a score: build_note_plan needs `score` with them')
+            return free[None].expand(ticks, v).clone()
+        notes = torch.as_tensor(score).detach().cpu()
+        if notes.dim() == 3 and notes.shape[1] == 1:
+            notes = notes[:, 0]
+        if notes.dim() != 2 or notes.shape[1] != ticks or notes.dtype.is_floating_point:
+            raise ValueError(f'score must hold note indices of shape (n, {ticks}) or (n, 1, {ticks}), got {tuple(torch.as_tensor(score).shape)}')
+        notes = notes.to(torch.int64)
+        if bool(((notes < 0) | (notes >= v)).any()):
+            raise ValueError(f'score holds note indices outside [0, {v})')
+        n = notes.shape[0]
+        plan = free[None, None].expand(n, ticks, v).clone()
+        forced = torch.zeros(n, ticks, dtype=torch.bool)
+        if keep_rhythm:
+            slur = self.dataset.note2index_dicts.get('__')
+            if slur is None:
+                raise ValueError("keep_rhythm needs the slur symbol '__' in the dataset's vocabulary")
+            plan[:, :, slur] = False
+            forced |= notes == slur
+        if keep is not None:
+            k = torch.as_tensor(keep).detach().cpu()
+            if k.dtype != torch.bool or tuple(k.shape) not in ((ticks,), (n, ticks)):
+                raise ValueError(f'keep must be a bool mask of shape ({ticks},) or ({n}, {ticks}), got {k.dtype} {tuple(k.shape)}')
+            forced |= k.expand(n, ticks)
+        one = torch.zeros(n, ticks, v, dtype=torch.bool).scatter_(2, notes[:, :, None], True)
+        return torch.where(forced[:, :, None], one, plan)
+
+    def infill_measures(self, score, keep=None, keep_rhythm=False, sampling='argmax', temperature=1.0, uniforms=None, top_k=None,
+                        top_p=None, allowed=None, playable=False, beam_width=4):
+        """Rewrite measures around what is kept of them: `score` (n, 24) / (n, 1, 24) is encoded to its posterior mean
+        (encoder.encode_params) and decoded under build_note_plan(score, keep, keep_rhythm, allowed, playable) with sampling 'argmax',
+        'multinomial' or 'beam' (decode_latent_codes).  The kept ticks come back as they were; the notes fed back into the decoder are
+        the kept ones.  -> (music21 score or None, note indices (n, 1, 24) int64)"""
+        if sampling not in ('argmax', 'multinomial', 'beam'):
+            raise ValueError(f"sampling must be 'argmax', 'multinomial' or 'beam', got {sampling!r}")
+        if keep is None and not keep_rhythm:
+            raise ValueError('infill_measures keeps something of the score: give keep (the ticks to keep) or keep_rhythm=True')
+        self._check_beam_draws_nothing(sampling, temperature, uniforms, top_k, top_p)
+        plan = self.build_note_plan(score, keep, keep_rhythm, allowed, playable)
+        if sampling != 'beam':                                 # (bad cuts are refused before the encoder runs)
+            self.model.decoder.sampling_filter(top_k, top_p, None)
+        dev = next(self.model.parameters()).device
+        notes = torch.as_tensor(score).reshape(plan.shape[0], 24).to(device=dev, dtype=torch.int64).contiguous()
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                z = self.model.encoder.encode_params(notes)[0]
+        finally:
+            self.model.train(was_training)
+        return self.decode_latent_codes(z, sampling=sampling, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
+                                        beam_width=beam_width, plan=plan)
 
     def sample_measures(self, num, temperature=1.0, top_k=None, top_p=None, allowed=None, playable=False, beam_width=None):
         """num measures drawn from the model: z ~ N(0, I) from the library's generator, every note drawn from

@@ -996,6 +996,135 @@ def sequence_log_prob(weights, tokens, allow=None):
     return out
 
 
+# ---- note plans: an allowed-note mask per (row, tick) (include/arvae_hip.h, arvae_note_plan_t) -----------------------------------
+def note_plan(plan, rows, ticks, vocab):
+    """-> (_lib.NotePlan, the tensor it points into) of a plan on the device: uint8 (rows, ticks, vocab), or (ticks, vocab) = the same
+    plan for every row (row stride 0).  Emptiness and the flags' values are the host validator's to check
+    (HierarchicalDecoder.note_plan): the kernels return a note in range for any bytes."""
+    if plan.dtype != torch.uint8 or tuple(plan.shape) not in ((rows, ticks, vocab), (ticks, vocab)):
+        raise ValueError(f'a note plan must be uint8 of shape ({rows}, {ticks}, {vocab}) or ({ticks}, {vocab}), got {plan.dtype} '
+                         f'{tuple(plan.shape)}')
+    _dev(plan)
+    plan = plan.contiguous()
+    return _lib.NotePlan(_ptr(plan), ticks * vocab if plan.dim() == 3 else 0, vocab), plan
+
+
+def tick_free_run_planned(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, uniforms, plan, temperature=1.0, top_k=None,
+                          top_p=None):
+    """tick_free_run_filtered with the allowed notes given per (row, tick) by `plan` (arvae_tick_free_run_planned; `note_plan`).
+    top_k = 1 is the plan's argmax: the draws are then without effect."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab, uniforms)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    ticks = beats * ticks_per_beat
+    flt, _ = sample_filter(vocab, top_k, top_p, None)
+    npl, plan = note_plan(plan, batch, ticks, vocab)
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    tokens = torch.empty(batch, ticks, device=gib.device, dtype=torch.int64)
+    ws = torch.empty(lib.arvae_tick_free_run_ws_floats(hid), device=gib.device, dtype=torch.float32)
+    u = _sampling_uniforms(uniforms, (batch, ticks))
+    with _timed('tick_free_run_planned', 2.0 * batch * ticks * (9 * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_free_run_planned(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), None, 1.0, batch,
+                                                   beats, ticks_per_beat, hid, vocab, _ptr(u), 1.0 / float(temperature),
+                                                   ctypes.byref(flt), ctypes.byref(npl), _ptr(tokens), _ptr(ws), _stream()),
+                   'tick_free_run_planned')
+    return tokens
+
+
+def tick_free_run_layers_planned(cells, w_out, b_out, h0, gib, ptab, batch, beats, ticks_per_beat, uniforms, plan, temperature=1.0,
+                                 top_k=None, top_p=None):
+    """tick_free_run_planned for a GRU stack of 1, 3 or 4 layers (arvae_tick_free_run_layers_planned)."""
+    layers, ticks = len(cells), beats * ticks_per_beat
+    ts, h0, tokens, ws = _tick_stack(cells, w_out, b_out, h0, gib, ptab, batch, ticks)
+    _dev(uniforms)
+    lib = _lib.load()
+    hid, vocab = cells[0][1].shape[1], w_out.shape[0]
+    flt, _ = sample_filter(vocab, top_k, top_p, None)
+    npl, plan = note_plan(plan, batch, ticks, vocab)
+    u = _sampling_uniforms(uniforms, (batch, ticks))
+    with _timed('tick_free_run_layers_planned', 2.0 * batch * ticks * (3 * (2 * layers - 1) * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_free_run_layers_planned(ctypes.byref(ts), _ptr(gib), _ptr(ptab), None, 1.0, batch, beats, ticks_per_beat,
+                                                          hid, vocab, _ptr(u), 1.0 / float(temperature), ctypes.byref(flt),
+                                                          ctypes.byref(npl), _ptr(tokens), _ptr(ws), _stream()),
+                   'tick_free_run_layers_planned')
+    return tokens
+
+
+def row_sample_planned(w, u, plan, tick, temperature=1.0, top_k=None, top_p=None):
+    """row_sample_filtered with row r's allowed notes those of plan[r, tick] (arvae_row_sample_planned): the tick-by-tick path."""
+    _dev(w, u)
+    lib = _lib.load()
+    w = w.contiguous()
+    rows, cols = w.shape
+    u = _sampling_uniforms(u, (rows,))
+    ticks = plan.shape[-2]
+    flt, _ = sample_filter(cols, top_k, top_p, None)
+    npl, plan = note_plan(plan, rows, ticks, cols)
+    idx = torch.empty(rows, device=w.device, dtype=torch.int64)
+    _lib.check(lib.arvae_row_sample_planned(_ptr(w), rows, cols, _ptr(u), 1.0 / float(temperature), ctypes.byref(flt), ctypes.byref(npl),
+                                            ticks, int(tick), _ptr(idx), _stream()), 'row_sample_planned')
+    return idx
+
+
+def tick_beam_search_planned(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, width, plan):
+    """tick_beam_search under a note plan (arvae_tick_beam_search_planned): the same five tensors; slots without a finite candidate are
+    dead (score -inf, listed last, their tokens inside the plan)."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    ticks, dev = beats * ticks_per_beat, gib.device
+    npl, plan = note_plan(plan, batch, ticks, vocab)
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    parents = torch.empty(batch, ticks, width, device=dev, dtype=torch.int32)
+    tokens = torch.empty(batch, ticks, width, device=dev, dtype=torch.int64)
+    hist = torch.empty(batch, ticks, width, device=dev, dtype=torch.float32)
+    seqs = torch.empty(batch, width, ticks, device=dev, dtype=torch.int64)
+    scores = torch.empty(batch, width, device=dev, dtype=torch.float32)
+    ws = torch.empty(lib.arvae_tick_beam_search_ws_floats(hid), device=dev, dtype=torch.float32)
+    with _timed('tick_beam_search_planned', 2.0 * batch * width * ticks * (9 * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_beam_search_planned(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), batch, beats,
+                                                      ticks_per_beat, hid, vocab, int(width), ctypes.byref(npl), _ptr(parents),
+                                                      _ptr(tokens), _ptr(hist), _ptr(seqs), _ptr(scores), _ptr(ws), _stream()),
+                   'tick_beam_search_planned')
+    return parents, tokens, hist, seqs, scores
+
+
+def beam_select_planned(logits, scores, live, plan, tick):
+    """beam_select with code b's allowed notes those of plan[b, tick] (arvae_beam_select_planned); no count: slots without a candidate
+    are dead."""
+    _dev(logits, scores)
+    lib = _lib.load()
+    logits, scores = logits.contiguous(), scores.contiguous()
+    codes, width = scores.shape
+    vocab = logits.shape[1]
+    if logits.shape[0] != codes * width or scores.dtype != torch.float32 or logits.dtype != torch.float32:
+        raise ValueError(f'beam_select takes float32 logits ({codes * width}, V) for scores ({codes}, {width}), got {tuple(logits.shape)}')
+    ticks = plan.shape[-2]
+    npl, plan = note_plan(plan, codes, ticks, vocab)
+    parents = torch.empty(codes, width, device=logits.device, dtype=torch.int32)
+    notes = torch.empty(codes, width, device=logits.device, dtype=torch.int64)
+    out = torch.empty(codes, width, device=logits.device, dtype=torch.float32)
+    _lib.check(lib.arvae_beam_select_planned(_ptr(logits), _ptr(scores), codes, width, vocab, int(live), ctypes.byref(npl), ticks, int(tick),
+                                             _ptr(parents), _ptr(notes), _ptr(out), _stream()), 'beam_select_planned')
+    return parents, notes, out
+
+
+def sequence_log_prob_planned(weights, tokens, plan):
+    """sequence_log_prob with the softmax of row r at tick t over the notes of plan[r, t] (arvae_sequence_log_prob_planned)."""
+    _dev(weights, tokens)
+    lib = _lib.load()
+    if weights.dim() != 3 or tuple(tokens.shape) != tuple(weights.shape[:2]) or tokens.dtype != torch.int64 or weights.dtype != torch.float32:
+        raise ValueError(f'sequence_log_prob takes float32 weights (R, T, V) and int64 tokens (R, T), got {tuple(weights.shape)} '
+                         f'{weights.dtype} and {tuple(tokens.shape)} {tokens.dtype}')
+    weights, tokens = weights.contiguous(), tokens.contiguous()
+    rows, steps, vocab = weights.shape
+    npl, plan = note_plan(plan, rows, steps, vocab)
+    out = torch.empty(rows, device=weights.device, dtype=torch.float32)
+    _lib.check(lib.arvae_sequence_log_prob_planned(_ptr(weights), _ptr(tokens), rows, steps, vocab, ctypes.byref(npl), _ptr(out), _stream()),
+               'sequence_log_prob_planned')
+    return out
+
+
 def _sampling_uniforms(u, shape):
     if u.dtype != torch.float32 or tuple(u.shape) != tuple(shape):
         raise ValueError(f'sampling uniforms must be float32 of shape {tuple(shape)}, got {u.dtype} {tuple(u.shape)}')

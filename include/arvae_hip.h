@@ -464,6 +464,54 @@ int arvae_tick_beam_search(const arvae_tick_weights_t *weights, const float *h0_
                            int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed, int32_t *parents, int64_t *tokens,
                            float *scores_hist, int64_t *sequences, float *scores, float *ws, arvae_stream_t stream);
 
+/* Note plans of the free-running decoder (generation; beyond the reference): an allowed-note mask per (row, tick) instead of one per
+ * call, honoured by every decode mode.  One definition for the entry points below.
+ *   allow: DEVICE pointer to bytes, allow[b * row_stride + t * tick_stride + v] != 0: note v may be emitted for row b at tick t.  The
+ *   strides are in bytes; the dense form [batch][ticks][vocab] has tick_stride = vocab and row_stride = ticks * vocab, and 0 broadcasts
+ *   (row_stride 0: one plan for every row; tick_stride 0: one mask for every tick).  Nothing else is accepted.
+ *   A(b, t) = {v : allow[b, t, v] != 0}; the caller folds an `allowed` mask into the plan (filter->allow must be NULL here) and makes
+ *   sure that no A(b, t) is empty (an empty one gives a note in range, no fault: the first note).
+ *   Draws: arvae_sample_filter_t's rule with A(b, t) as the allowed set: the maximum, the ranks, S, mass_before and the draw are taken
+ *   among the notes of A(b, t).  top_k = 1 is the plan's argmax (the allowed note with the largest logit, ties to the lower index;
+ *   the draw u is then without effect).  One allowed note forces it; the forced note is what the recurrence is fed.
+ *   Beam search: the candidates of code b at tick t are (k, v), v in A(b, t); logp is the log-softmax over A(b, t) (a forced tick adds
+ *   exactly 0).  Fewer than W finite candidates may exist: the slots without one are DEAD -- score -inf, listed behind every finite
+ *   hypothesis, never displacing one, every token they carry inside its tick's A(b, t); their parent and note are otherwise not
+ *   promised.  No width <= allowed requirement.
+ *   arvae_sequence_log_prob_planned: the sum over t of the log-softmax over A(r, t) at the token; a token outside A(r, t): -inf.
+ * The tick-by-tick forms (arvae_row_sample_planned, arvae_beam_select_planned) take the whole plan, `ticks` (the dense row stride is
+ * ticks * vocab) and the tick they serve.  ARVAE_E_INVALID with a message before any launch: a null plan or mask, a stride that is
+ * neither 0 nor the dense value, a tick outside [0, ticks), filter->allow set, dropout keep-masks (generation runs with dropout off),
+ * and whatever the unplanned call refuses.  Shapes: those of the unplanned calls. */
+typedef struct arvae_note_plan {
+    const uint8_t *allow;   /* device bytes */
+    int64_t row_stride;     /* bytes between rows: ticks * vocab, or 0 = every row the same */
+    int64_t tick_stride;    /* bytes between ticks: vocab, or 0 = every tick the same */
+} arvae_note_plan_t;
+int arvae_row_sample_planned(const float *w, int32_t rows, int32_t cols, const float *u, float inv_temperature,
+                             const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, int32_t ticks, int32_t tick, int64_t *idx,
+                             arvae_stream_t stream);
+int arvae_tick_free_run_planned(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1, int64_t h0_stride /* 0 = hidden */,
+                                const float *gib, const float *ptab, const uint8_t *mask /* must be NULL */, float keep_scale, int32_t batch,
+                                int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms,
+                                float inv_temperature, const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, int64_t *tokens,
+                                float *ws, arvae_stream_t stream);
+int arvae_tick_free_run_layers_planned(const arvae_tick_stack_t *stack, const float *gib, const float *ptab,
+                                       const uint8_t *mask /* must be NULL */, float keep_scale, int32_t batch, int32_t beats,
+                                       int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
+                                       const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, int64_t *tokens, float *ws,
+                                       arvae_stream_t stream);
+int arvae_beam_select_planned(const float *logits, const float *scores_in, int32_t codes, int32_t width, int32_t vocab, int32_t live,
+                              const arvae_note_plan_t *plan, int32_t ticks, int32_t tick, int32_t *parents, int64_t *notes,
+                              float *scores_out, arvae_stream_t stream);
+int arvae_sequence_log_prob_planned(const float *weights, const int64_t *tokens, int32_t rows, int32_t steps, int32_t vocab,
+                                    const arvae_note_plan_t *plan, float *out, arvae_stream_t stream);
+int arvae_tick_beam_search_planned(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1,
+                                   int64_t h0_stride /* 0 = hidden */, const float *gib, const float *ptab, int32_t batch, int32_t beats,
+                                   int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int32_t width, const arvae_note_plan_t *plan,
+                                   int32_t *parents, int64_t *tokens, float *scores_hist, int64_t *sequences, float *scores, float *ws,
+                                   arvae_stream_t stream);
+
 /* out[r] = [a[r] | b[r]] (torch.cat along dim 1/2, decoder.py:503) and its adjoint (db optionally accumulated) */
 int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,
                       arvae_stream_t stream);

@@ -4,7 +4,8 @@ defaults).  Only the `folk` one-bar dataset in its pre-built tensor form is supp
 building it from ABC files with music21, and the `bach` chorales, are offline steps outside this build.  `--metrics` adds the
 reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary; `--sample N [--temperature T] [--top_k K]
 [--top_p P] [--playable]` adds N measures drawn from the model (z from the prior, every note from softmax(probs / T) over the notes a
-top-k cut, a nucleus cut and the playable-note mask leave) as lists of note names."""
+top-k cut, a nucleus cut and the playable-note mask leave) as lists of note names; `--infill N --keep_ticks SPEC [--keep_rhythm]`
+rewrites N measures of the evaluation split around the ticks SPEC keeps (MeasureVAETrainer.infill_measures)."""
 import json
 import os
 import sys
@@ -71,12 +72,41 @@ SAMPLE_HELP = (f'{SAMPLE_FLAG} N [{TEMPERATURE_FLAG} T] [{TOP_K_FLAG} K] [{TOP_P
                f'drawing notes (the most likely measure of each code); not together with {TOP_K_FLAG}, {TOP_P_FLAG} or '
                f'{TEMPERATURE_FLAG}.')
 num_samples, temperature, top_k, top_p, playable, beam = 0, 1.0, None, None, False, None
+# infilling (MeasureVAETrainer.infill_measures): N measures of the evaluation split, decoded again around the ticks that are kept
+INFILL_FLAG, KEEP_TICKS_FLAG, KEEP_RHYTHM_FLAG = '--infill', '--keep_ticks', '--keep_rhythm'
+INFILL_HELP = (f'{INFILL_FLAG} N {KEEP_TICKS_FLAG} SPEC [{KEEP_RHYTHM_FLAG}]: add `infill` to the evaluation summary, the first N '
+               'measures of the evaluation split and what the model writes around the ticks SPEC keeps of them (SPEC like 0-5,12-17: '
+               f'ticks and inclusive ranges in [0, 23]); {KEEP_RHYTHM_FLAG} also keeps every slur where it is and every onset an onset.  '
+               f'The notes are the best allowed ones, drawn with {TEMPERATURE_FLAG} / {TOP_K_FLAG} / {TOP_P_FLAG}, or searched with '
+               f'{BEAM_FLAG} W; {PLAYABLE_FLAG} keeps START, END and None out of the rewritten ticks.')
+num_infill, keep_ticks, keep_rhythm, drew_notes = 0, None, False, False
+TICKS = 24
+
+
+def parse_keep_ticks(spec):
+    """'0-5,12-17' -> a list of 24 flags: comma-separated ticks and inclusive ranges lo-hi in [0, 23], at least one tick"""
+    keep = [False] * TICKS
+    parts = [p.strip() for p in str(spec).split(',')]
+    if not spec or any(not p for p in parts):
+        raise ValueError(f'{KEEP_TICKS_FLAG} takes ticks and ranges like 0-5,12-17, got {spec!r}')
+    for part in parts:
+        ends = part.split('-')
+        if len(ends) > 2 or not all(e.strip().isdigit() for e in ends):
+            raise ValueError(f'{KEEP_TICKS_FLAG}: {part!r} is neither a tick nor a range lo-hi (in {spec!r})')
+        lo, hi = int(ends[0]), int(ends[-1])
+        if lo > hi:
+            raise ValueError(f'{KEEP_TICKS_FLAG}: the range {part!r} runs backwards')
+        if hi >= TICKS:
+            raise ValueError(f'{KEEP_TICKS_FLAG}: {part!r} is outside the measure\'s ticks [0, {TICKS - 1}]')
+        for t in range(lo, hi + 1):
+            keep[t] = True
+    return keep
 
 
 def with_options(fn):
     for names, kwargs in reversed(MEASURE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP)(fn)
+    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP + '  ' + INFILL_HELP)(fn)
 
 
 @with_options
@@ -156,6 +186,22 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
             elif top_k is not None or top_p is not None or playable:        # the cuts are echoed beside the measures they shaped
                 summary['sampling'] = {'temperature': temperature, 'top_k': top_k, 'top_p': top_p, 'playable': playable}
             summary['samples'] = [[dataset.index2note_dicts[int(i)] for i in row] for row in notes.squeeze(1).tolist()]
+        if num_infill > 0:
+            trainer.cuda()
+            model.eval()
+            score = next(iter(eval_loader))[0]
+            score = score.view(-1, score.shape[-1])[:num_infill]
+            if score.shape[0] < num_infill:
+                raise SystemExit(f'{INFILL_FLAG} {num_infill}: an evaluation batch holds {score.shape[0]} measures')
+            mode = 'beam' if beam is not None else ('multinomial' if drew_notes else 'argmax')
+            _, notes = trainer.infill_measures(score, keep=None if keep_ticks is None else torch.tensor(keep_ticks), keep_rhythm=keep_rhythm,
+                                               sampling=mode, temperature=temperature, top_k=top_k, top_p=top_p, playable=playable,
+                                               beam_width=4 if beam is None else beam)
+            names = dataset.index2note_dicts
+            summary['infill'] = {'sampling': mode, 'keep_ticks': [t for t in range(TICKS) if keep_ticks is not None and keep_ticks[t]],
+                                 'keep_rhythm': keep_rhythm, 'playable': playable,
+                                 'original': [[names[int(i)] for i in row] for row in score.tolist()],
+                                 'infilled': [[names[int(i)] for i in row] for row in notes.squeeze(1).tolist()]}
         print(json.dumps(summary, indent=2))
 
 
@@ -180,7 +226,7 @@ def run(argv=None):
     """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p,
     --playable and --beam.  Values of --top_k / --top_p outside their ranges raise the decoder's ValueError (sampling_filter); --beam
     takes a width in [1, 16] and is refused together with --top_k, --top_p or --temperature (beam search draws nothing)."""
-    global with_metrics, num_samples, temperature, top_k, top_p, playable, beam
+    global with_metrics, num_samples, temperature, top_k, top_p, playable, beam, num_infill, keep_ticks, keep_rhythm, drew_notes
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
     playable = PLAYABLE_FLAG in argv
@@ -196,10 +242,21 @@ def run(argv=None):
         if top_k is not None or top_p is not None or drew:
             raise ValueError(f'{BEAM_FLAG} decodes by beam search, which draws no note: it cannot be combined with {TOP_K_FLAG}, '
                              f'{TOP_P_FLAG} or {TEMPERATURE_FLAG}')
+    num_infill, argv = _take_value(argv, INFILL_FLAG, int, 0)
+    spec, argv = _take_value(argv, KEEP_TICKS_FLAG, str, None)
+    keep_rhythm = KEEP_RHYTHM_FLAG in argv
+    keep_ticks = None if spec is None else parse_keep_ticks(spec)      # a bad spec is refused here, before anything is loaded
+    drew_notes = drew or top_k is not None or top_p is not None
+    if num_infill < 0:
+        raise ValueError(f'{INFILL_FLAG} takes a count >= 0, got {num_infill}')
+    if num_infill > 0 and keep_ticks is None and not keep_rhythm:
+        raise ValueError(f'{INFILL_FLAG} keeps something of every measure: give {KEEP_TICKS_FLAG} SPEC or {KEEP_RHYTHM_FLAG}')
+    if num_infill == 0 and (keep_ticks is not None or keep_rhythm):
+        raise ValueError(f'{KEEP_TICKS_FLAG} and {KEEP_RHYTHM_FLAG} belong to {INFILL_FLAG} N')
     if num_samples < 0 or not temperature > 0:
         raise SystemExit(f'{SAMPLE_FLAG} takes a count >= 0 and {TEMPERATURE_FLAG} a positive number')
     check_sampling_cuts(top_k, top_p)          # the decoder's own ValueError, before anything is loaded or trained
-    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG)])
+    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG, KEEP_RHYTHM_FLAG)])
 
 
 if __name__ == '__main__':
