@@ -190,6 +190,11 @@ SIGNATURES = {
     'arvae_sequence_log_prob_planned': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, _P(NotePlan), c_vp, c_vp]),
     'arvae_tick_beam_search_planned': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                                _P(NotePlan), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_beam_select_groups': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, _P(NotePlan), c_i32, c_i32, c_vp, c_vp,
+                                         c_vp, c_vp, c_vp]),
+    'arvae_tick_beam_search_groups_supported': (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    'arvae_tick_beam_search_groups': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                              c_i32, c_f32, _P(NotePlan), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'arvae_beam_select': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'arvae_sequence_log_prob': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'arvae_tick_beam_search_supported': (c_i32, [c_i32, c_i32, c_i32]),

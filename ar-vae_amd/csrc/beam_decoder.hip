@@ -8,7 +8,9 @@
 //                             layer counts and hidden sizes, more than 64 notes) and the on-device yardstick of the one-launch kernel;
 //   sequence_log_prob_kernel  sum over t of the masked log-softmax of given logits at given tokens.
 // All three also serve a note plan (include/arvae_hip.h, "Note plans": the allowed notes per (code, tick)); the one-launch kernel has an
-// instantiation of its own for it, in which a code may hold fewer than W finite hypotheses (dead slots).
+// instantiation of its own for it, in which a code may hold fewer than W finite hypotheses (dead slots).  The one-launch kernel and
+// beam_select_kernel also serve the beams in groups (include/arvae_hip.h, "Diverse beam search"): a further instantiation on the
+// planned form, and a group loop in the row kernel.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -30,18 +32,34 @@ __device__ __forceinline__ bool beam_before(float ca, int ka, int va, float cb, 
     return ca > cb || (ca == cb && (ka < kb || (ka == kb && va < vb)));
 }
 
+// the key of the diverse search, c - penalty * float(n): the product and the difference each rounded.  Contraction is off inside this
+// function alone (the compiler would otherwise fuse the two into fma(-penalty, n, c)); everything around it keeps the file's default
+__device__ __forceinline__ float beam_penalised(float c, float penalty, int n) {
+#pragma clang fp contract(off)
+    const float pay = penalty * (float)n;
+    return c - pay;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // One wave per code.  Per live beam k: M_k = the allowed maximum, S_k = the sum of exp(l - M_k) over the allowed notes (every lane its
 // notes in index order, then the xor butterfly: both lanes of a pair add the same two values, so every lane holds the same bits), lane
 // k keeps (M_k, log S_k, score_k).  Then W rounds: every lane takes the first of its candidates that is ordered behind the previous
 // round's pick, the butterfly the first among the lanes.  No allowed candidate left (arvae_beam_select rules it out; under a note plan
-// a forced tick or dead beams bring it about): a dead slot -- parent 0, the code's first allowed note (note 0 without one), -inf.
+// a forced tick or dead beams bring it about): a dead slot -- the group's first beam, the code's first allowed note (note 0 without
+// one), -inf.
 // allow_stride: bytes between the codes' masks (a note plan's tick; 0: one mask for every code).
+// groups G (include/arvae_hip.h, "Diverse beam search"): the groups of width / G beams are served one after the other, each over its
+// own beams (`live`: the live ones of EVERY group, its first) with the rounds above; a candidate's key is c - penalty * n_v, n_v the
+// number of finite picks with note v that the earlier groups of this call made (their notes in LDS, at most 15).  G = 1: no pick is
+// ever counted and the key is c.  logp_in / logp_out (both or neither): the beams' unpenalised sums, carried beside the scores.
 __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict__ logits, const float *__restrict__ scores_in, int width,
                                                          int vocab, int live, const uint8_t *__restrict__ allow_all, int64_t allow_stride,
                                                          int *__restrict__ parents, int64_t *__restrict__ notes,
-                                                         float *__restrict__ scores_out) {
+                                                         float *__restrict__ scores_out, int groups, float penalty,
+                                                         const float *__restrict__ logp_in, float *__restrict__ logp_out) {
+    __shared__ int pick_note[BEAM_MAX_WIDTH];
     const int code = blockIdx.x, lane = threadIdx.x;
+    const int gw = width / groups;
     const float *base = logits + (int64_t)code * width * vocab;
     const uint8_t *allow = allow_all != nullptr ? allow_all + code * allow_stride : nullptr;
     auto on = [&](int v) { return allow == nullptr || allow[v] != 0; };
@@ -51,8 +69,9 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) first_on = min(first_on, __shfl_xor(first_on, off, 64));
     first_on = first_on < vocab ? first_on : 0;
-    float my_m = 0.f, my_ls = 0.f, my_sc = -INFINITY;
-    for (int k = 0; k < live; ++k) {
+    float my_m = 0.f, my_ls = 0.f, my_sc = -INFINITY, my_lp = -INFINITY;
+    for (int k = 0; k < width; ++k) {
+        if (k % gw >= live) continue;
         const float *row = base + (int64_t)k * vocab;
         float m = -INFINITY;
         for (int v = lane; v < vocab; v += 64)
@@ -63,40 +82,64 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict
         for (int v = lane; v < vocab; v += 64)
             if (on(v)) s += expf(row[v] - m);
         s = wave_sum(s);
-        if (lane == k) { my_m = m; my_ls = logf(s); my_sc = scores_in[(int64_t)code * width + k]; }
+        if (lane == k) {
+            my_m = m; my_ls = logf(s); my_sc = scores_in[(int64_t)code * width + k];
+            if (logp_in != nullptr) my_lp = logp_in[(int64_t)code * width + k];
+        }
     }
-    float pc = INFINITY;
-    int pk = -1, pv = -1;
-    for (int j = 0; j < width; ++j) {
-        float bc = -INFINITY;
-        int bk = 0, bv = 0;
-        bool found = false;
-        for (int k = 0; k < live; ++k) {
-            const float m = __shfl(my_m, k, 64), ls = __shfl(my_ls, k, 64), sc = __shfl(my_sc, k, 64);
-            const float *row = base + (int64_t)k * vocab;
-            for (int v = lane; v < vocab; v += 64) {
-                if (!on(v)) continue;
-                const float c = sc + ((row[v] - m) - ls);
-                if (!beam_before(pc, pk, pv, c, k, v)) continue;           // taken in an earlier round (or not a number)
-                if (!found || beam_before(c, k, v, bc, bk, bv)) { bc = c; bk = k; bv = v; found = true; }
+    int seen = 0, made = 0;                                    // the picks the current group counts / those made so far (wave-uniform)
+    for (int g = 0; g < groups; ++g) {
+        const int k0 = g * gw;
+        float pc = INFINITY;
+        int pk = -1, pv = -1;
+        for (int j = 0; j < gw; ++j) {
+            float bc = -INFINITY;
+            int bk = 0, bv = 0;
+            bool found = false;
+            for (int k = k0; k < k0 + live; ++k) {
+                const float m = __shfl(my_m, k, 64), ls = __shfl(my_ls, k, 64), sc = __shfl(my_sc, k, 64);
+                const float *row = base + (int64_t)k * vocab;
+                for (int v = lane; v < vocab; v += 64) {
+                    if (!on(v)) continue;
+                    float c = sc + ((row[v] - m) - ls);
+                    if (seen > 0) {
+                        int n = 0;
+                        for (int q = 0; q < seen; ++q) n += pick_note[q] == v ? 1 : 0;
+                        c = beam_penalised(c, penalty, n);
+                    }
+                    if (!beam_before(pc, pk, pv, c, k, v)) continue;       // taken in an earlier round (or not a number)
+                    if (!found || beam_before(c, k, v, bc, bk, bv)) { bc = c; bk = k; bv = v; found = true; }
+                }
             }
-        }
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float oc = __shfl_xor(bc, off, 64);
-            const int ok = __shfl_xor(bk, off, 64), ov = __shfl_xor(bv, off, 64);
-            const bool of = __shfl_xor((int)found, off, 64) != 0;
-            const bool take = of && (!found || beam_before(oc, ok, ov, bc, bk, bv));
-            bc = take ? oc : bc; bk = take ? ok : bk; bv = take ? ov : bv;
-            found = found || of;
+            for (int off = 32; off > 0; off >>= 1) {
+                const float oc = __shfl_xor(bc, off, 64);
+                const int ok = __shfl_xor(bk, off, 64), ov = __shfl_xor(bv, off, 64);
+                const bool of = __shfl_xor((int)found, off, 64) != 0;
+                const bool take = of && (!found || beam_before(oc, ok, ov, bc, bk, bv));
+                bc = take ? oc : bc; bk = take ? ok : bk; bv = take ? ov : bv;
+                found = found || of;
+            }
+            if (!found) { bc = -INFINITY; bk = k0; bv = first_on; }
+            float lp = -INFINITY;
+            if (logp_out != nullptr) {
+                const float m = __shfl(my_m, bk, 64), ls = __shfl(my_ls, bk, 64), plp = __shfl(my_lp, bk, 64);
+                if (found) lp = plp + ((base[(int64_t)bk * vocab + bv] - m) - ls);
+            }
+            if (lane == 0) {
+                parents[(int64_t)code * width + k0 + j] = bk;
+                notes[(int64_t)code * width + k0 + j] = bv;
+                scores_out[(int64_t)code * width + k0 + j] = bc;
+                if (logp_out != nullptr) logp_out[(int64_t)code * width + k0 + j] = lp;
+                if (groups > 1 && bc > -INFINITY && made < BEAM_MAX_WIDTH) pick_note[made] = bv;
+            }
+            made += groups > 1 && bc > -INFINITY ? 1 : 0;
+            pc = bc; pk = bk; pv = bv;
         }
-        if (!found) { bc = -INFINITY; bk = 0; bv = first_on; }
-        if (lane == 0) {
-            parents[(int64_t)code * width + j] = bk;
-            notes[(int64_t)code * width + j] = bv;
-            scores_out[(int64_t)code * width + j] = bc;
+        if (groups > 1) {
+            __syncthreads();                                   // (one wave: the picks' notes are in LDS before the next group counts them)
+            seen = made;
         }
-        pc = bc; pk = bk; pv = bv;
     }
 }
 
@@ -159,6 +202,14 @@ struct TickBeamPlanned : TickBeam {
     int64_t row_stride, tick_stride;
 };
 
+// TickBeamPlanned served in `groups` groups of `gwidth` = width / groups beams (include/arvae_hip.h, "Diverse beam search").  Again a
+// type of its own: the two searches above keep their arguments and their code.
+struct TickBeamGroups : TickBeamPlanned {
+    int groups, gwidth;
+    float penalty;
+    float *log_probs;              // [B][W]
+};
+
 // The recurrence is tick_free_run_h2_kernel's (the same operands, products and gates in the same order: width 1 feeds back the argmax
 // run's notes), over tile rows r = (code, beam k): code = r >> wshift of the workgroup's RW >> wshift codes, k = r & (WP - 1); beams
 // k >= W of a padded width are dead (score -inf, never a parent).  What differs:
@@ -183,10 +234,25 @@ struct TickBeamPlanned : TickBeam {
 //     (c, k, v) -- which keeps equal fillers apart, and counts the slots below W only: the W * W entries of a code then have
 //     distinct ranks and the ranks 0 .. W - 1 are each written once.  Entries of -inf are DEAD beams: behind every finite one, their
 //     notes inside A(b, t), their score -inf for good (-inf + logp).
+//
+// P = TickBeamGroups (GROUPS, on the planned form): the two stages run once per group g, a barrier between the groups.  In group g's
+// turn the "code" of both stages is the pair (code, g): the rows k in [g W', (g + 1) W') of the code, W' = gwidth slots a row, W' new
+// beams at the rows g W' + rank.
+//   * `cnt` [codes of the tile][64] counts, per note, the finite picks the earlier groups made at this tick: zeroed at the tick's
+//     top, raised by stage 2 (an LDS add per finite pick).  Stage 1's key is a = c - penalty * float(cnt[v]) (the product rounded on
+//     its own), and it is what the ranks, `top` and the new score take; group 0 reads zeros, so a = c exactly.
+//   * stage 1 forms the candidates of every row in every turn (a row outside group g writes `cnd` only, bits nobody reads: its own
+//     turn writes them again) but walks and writes `top` for the rows of group g alone; a wave none of whose rows is in group g skips
+//     the unit.  (Keeping a row's M and log S from turn 0 in LDS for the later turns was measured and bought nothing: DESIGN.md
+//     item 61.)  The last turn's picks raise no count: nobody reads it.
+//   * a second float per row, `logp_s` (the unpenalised sum), is carried like `score_s`: stage 1 puts logp_s[k] + logp_v beside the
+//     key (`top_l`), stage 2 hands the winner's to its new row.  Rows of group g are written in turn g only, after stage 1 of that
+//     turn has read them.
 template <int H, int RW, class P>
 __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint4 *__restrict__ packed) {
     static_assert(RW == 16 || RW == 8 || RW == 4, "16, 8 or 4 rows: four, two or one per lane");
-    constexpr bool PLAN = std::is_same<P, TickBeamPlanned>::value;
+    constexpr bool PLAN = std::is_base_of<TickBeamPlanned, P>::value;
+    constexpr bool GROUPS = std::is_same<P, TickBeamGroups>::value;
     constexpr int E = RW / 4;
     constexpr int NW = H / 16, KS = H / 32, KQ = H / 16;
     constexpr int NGG = 9 * KS;
@@ -207,6 +273,10 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint
     __shared__ int sel_par[16], sel_note[16];
     __shared__ unsigned char hist_p[BEAM_MAX_TICKS][16], hist_v[BEAM_MAX_TICKS][16];
     __shared__ float hmax[H / 16];
+    // GROUPS only (the other instantiations never name them, so they take no LDS there)
+    __shared__ __attribute__((aligned(16))) float top_l[16][BEAM_MAX_WIDTH];
+    __shared__ float logp_s[16];
+    __shared__ int cnt[16][64];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
@@ -214,6 +284,9 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint
     const int B = p.batch, W = p.width, wsh = p.wshift, WP = 1 << wsh;
     const int code0 = blockIdx.x * (RW >> wsh);
     const int ntile = (p.vocab + 15) / 16;
+    int WS = W, NG = 1;                                        // the slots a row fills and the new beams of a stage-2 "code"; the turns
+    [[maybe_unused]] float lam = 0.f;
+    if constexpr (GROUPS) { WS = p.gwidth; NG = p.groups; lam = p.penalty; }
 
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(packed), 0, 3 * KS * NW * 6 * 64 * 16, 0x00020000);
     const int wlane = (w * 6 * 64 + lane) * 16;
@@ -235,10 +308,18 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint
     for (int e = threadIdx.x; e < 16 * BEAM_MAX_WIDTH; e += H * 4) { (&top_c[0][0])[e] = -INFINITY; (&top_v[0][0])[e] = 0; }
     if (threadIdx.x < 16) {
         const int k = threadIdx.x & (WP - 1);
-        score_s[threadIdx.x] = k == 0 ? 0.f : -INFINITY;       // tick 0: one live beam
+        if constexpr (GROUPS) {                                // tick 0: the first beam of every group is live
+            const bool head = k < W && k % WS == 0;
+            score_s[threadIdx.x] = head ? 0.f : -INFINITY;
+            logp_s[threadIdx.x] = head ? 0.f : -INFINITY;
+        } else {
+            score_s[threadIdx.x] = k == 0 ? 0.f : -INFINITY;   // tick 0: one live beam
+        }
         sel_par[threadIdx.x] = k;                              // (dead beams keep themselves and note 0)
         sel_note[threadIdx.x] = 0;
     }
+    if constexpr (GROUPS)
+        for (int e = threadIdx.x; e < 16 * BEAM_MAX_WIDTH; e += H * 4) (&top_l[0][0])[e] = -INFINITY;
     const float b0r = p.b_hh0[unit], b0z = p.b_hh0[H + unit], b0n = p.b_hh0[2 * H + unit];
     const float b1r = p.b_ih1[unit] + p.b_hh1[unit], b1z = p.b_ih1[H + unit] + p.b_hh1[H + unit];
     const float b1in = p.b_ih1[2 * H + unit], b1hn = p.b_hh1[2 * H + unit];
@@ -310,6 +391,8 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint
 #pragma unroll
             for (int i = 0; i < E; ++i) plan_b[i] = p.plan[rows[i] * p.row_stride + t * p.tick_stride + (note_ok ? note : 0)];
         }
+        if constexpr (GROUPS)                                  // (last read two barriers ago, next read behind the logits' barrier)
+            for (int e = threadIdx.x; e < 16 * 64; e += H * 4) (&cnt[0][0])[e] = 0;
         // ---- layer 0: matrix 0
         {
             f32x4 acc0[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -394,123 +477,160 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint
         lds_barrier();
         // ---- selection, stage 1: a row's candidates and each note's rank inside its row.  Unit (element i, tile q) on wave
         // (4 i + q) mod NW: the wave forms ALL the row's candidates itself (the waves that share a row write the same bits to cnd),
-        // then walks the row for its tile's 16 notes
-        for (int u = w; u < 4 * E; u += NW) {
-            const int i = u >> 2, tq = u & 3;
-            if (tq >= ntile) continue;
-            const int r = lrow(i);
-            float lv[4], c[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) lv[q] = lgs[r * FLT_LS + 16 * q + col];
-            const float big = row16_max(fmaxf(fmaxf(lv[0], lv[1]), fmaxf(lv[2], lv[3])));
-            float e[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) e[q] = lv[q] >= 0.f ? expf(lv[q] - big) : 0.f;
-            const float ls = logf(row16_sum((e[0] + e[1]) + (e[2] + e[3])));
-            const float sc = score_s[r];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                c[q] = lv[q] >= 0.f ? sc + ((lv[q] - big) - ls) : (PLAN ? __builtin_nanf("") : -INFINITY);
-                cnd[r * FLT_LS + 16 * q + col] = c[q];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            float mine = c[0];
-#pragma unroll
-            for (int q = 1; q < 4; ++q) mine = tq == q ? c[q] : mine;
-            const int v = 16 * tq + col;
-            if constexpr (PLAN) {
-                int first_on = 0;                              // the row's first allowed note (the quad's 16 lanes hold the row)
-#pragma unroll
-                for (int q = 3; q >= 0; --q) {
-                    const int bits = (int)((unsigned)(__ballot(lv[q] >= 0.f) >> (16 * quad)) & 0xffffu);
-                    first_on = bits != 0 ? 16 * q + __ffs(bits) - 1 : first_on;
+        // then walks the row for its tile's 16 notes.  GROUPS: turn g of NG, the rows of group g (above)
+        for (int g = 0;; ++g) {
+            for (int u = w; u < 4 * E; u += NW) {
+                const int i = u >> 2, tq = u & 3;
+                if (tq >= ntile) continue;
+                const int r = lrow(i);
+                [[maybe_unused]] bool in_turn = true;
+                if constexpr (GROUPS) {
+                    in_turn = (r & (WP - 1)) / WS == g;
+                    if (__ballot(in_turn) == 0) continue;
                 }
-                int rank = 0, nal = 0, nbad = 0;
+                float lv[4], c[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) lv[q] = lgs[r * FLT_LS + 16 * q + col];
+                const float big = row16_max(fmaxf(fmaxf(lv[0], lv[1]), fmaxf(lv[2], lv[3])));
+                float e[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) e[q] = lv[q] >= 0.f ? expf(lv[q] - big) : 0.f;
+                const float ls = logf(row16_sum((e[0] + e[1]) + (e[2] + e[3])));
+                const float sc = score_s[r];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    c[q] = lv[q] >= 0.f ? sc + ((lv[q] - big) - ls) : (PLAN ? __builtin_nanf("") : -INFINITY);
+                    if constexpr (GROUPS) c[q] = beam_penalised(c[q], lam, cnt[r >> wsh][16 * q + col]);
+                    cnd[r * FLT_LS + 16 * q + col] = c[q];
+                }
+                [[maybe_unused]] float lpm = -INFINITY;            // GROUPS: the unpenalised sum of (row, the lane's note)
+                if constexpr (GROUPS) {
+                    float lvm = lv[0];
+#pragma unroll
+                    for (int q = 1; q < 4; ++q) lvm = tq == q ? lv[q] : lvm;
+                    lpm = logp_s[r] + ((lvm - big) - ls);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                float mine = c[0];
+#pragma unroll
+                for (int q = 1; q < 4; ++q) mine = tq == q ? c[q] : mine;
+                const int v = 16 * tq + col;
+                if constexpr (PLAN) {
+                    int first_on = 0;                              // the row's first allowed note (the quad's 16 lanes hold the row)
+#pragma unroll
+                    for (int q = 3; q >= 0; --q) {
+                        const int bits = (int)((unsigned)(__ballot(lv[q] >= 0.f) >> (16 * quad)) & 0xffffu);
+                        first_on = bits != 0 ? 16 * q + __ffs(bits) - 1 : first_on;
+                    }
+                    int rank = 0, nal = 0, nbad = 0;
+#pragma unroll 4
+                    for (int n4 = 0; n4 < 16 * ntile; n4 += 4) {
+                        const f32x4 q4 = *reinterpret_cast<const f32x4 *>(&cnd[r * FLT_LS + n4]);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float cn = q4[j];
+                            const bool bad = cn != cn;
+                            rank += (cn > mine || (cn == mine && n4 + j < v)) ? 1 : 0;
+                            nal += bad ? 0 : 1;
+                            nbad += bad && n4 + j < v ? 1 : 0;
+                        }
+                    }
+                    const bool filler = mine != mine;
+                    const int slot = filler ? nal + nbad : rank;
+                    if constexpr (GROUPS) {
+                        if (slot < WS && in_turn) {
+                            top_c[r][slot] = filler ? -INFINITY : mine;
+                            top_v[r][slot] = filler ? first_on : v;
+                            top_l[r][slot] = filler ? -INFINITY : lpm;
+                        }
+                    } else {
+                        if (slot < W) { top_c[r][slot] = filler ? -INFINITY : mine; top_v[r][slot] = filler ? first_on : v; }
+                    }
+                    continue;
+                }
+                int rank = 0;
 #pragma unroll 4
                 for (int n4 = 0; n4 < 16 * ntile; n4 += 4) {
                     const f32x4 q4 = *reinterpret_cast<const f32x4 *>(&cnd[r * FLT_LS + n4]);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float cn = q4[j];
-                        const bool bad = cn != cn;
                         rank += (cn > mine || (cn == mine && n4 + j < v)) ? 1 : 0;
-                        nal += bad ? 0 : 1;
-                        nbad += bad && n4 + j < v ? 1 : 0;
                     }
                 }
-                const bool filler = mine != mine;
-                const int slot = filler ? nal + nbad : rank;
-                if (slot < W) { top_c[r][slot] = filler ? -INFINITY : mine; top_v[r][slot] = filler ? first_on : v; }
-                continue;
+                if (rank < W) { top_c[r][rank] = mine; top_v[r][rank] = v; }
             }
-            int rank = 0;
-#pragma unroll 4
-            for (int n4 = 0; n4 < 16 * ntile; n4 += 4) {
-                const f32x4 q4 = *reinterpret_cast<const f32x4 *>(&cnd[r * FLT_LS + n4]);
+            lds_barrier();
+            // ---- stage 2: a code's first W are among its W rows' first W each (top: every row's in its own order, slots >= W -inf).
+            // Every (row, slot) entry counts the entries of its code ordered before it, Q lanes an entry (each a share of the code's
+            // rows, 16 slots a row in four 16-byte reads), the lanes' counts added by the xor butterfly; rank j < W: new beam j
+            {
+                constexpr int NT = 4 * H;
+                const int nent = RW << wsh;
+                int qsh = 0;
+                while ((nent << (qsh + 1)) <= NT && qsh < wsh) ++qsh;
+                const int Q = 1 << qsh, span = WP >> qsh, per = NT >> qsh;
+                const int part = threadIdx.x & (Q - 1);
+                for (int e0 = 0; e0 < nent; e0 += per) {
+                    const int en = e0 + ((int)threadIdx.x >> qsh);
+                    const bool in = en < nent;
+                    const int r = in ? en >> wsh : 0, s = en & (WP - 1);
+                    const int k = r & (WP - 1), cb = r & ~(WP - 1);
+                    const float c = top_c[r][s];
+                    const int v = top_v[r][s];
+                    int rank = 0;
+                    int klo = part * span, khi = min((part + 1) * span, W);
+                    if constexpr (GROUPS) { klo = max(klo, g * WS); khi = min(khi, (g + 1) * WS); }
+                    for (int k2 = klo; k2 < khi; ++k2) {
+                        const f32x4 *pc = reinterpret_cast<const f32x4 *>(&top_c[cb + k2][0]);
+                        const beam_i32x4 *pv = reinterpret_cast<const beam_i32x4 *>(&top_v[cb + k2][0]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float cn = q4[j];
-                    rank += (cn > mine || (cn == mine && n4 + j < v)) ? 1 : 0;
-                }
-            }
-            if (rank < W) { top_c[r][rank] = mine; top_v[r][rank] = v; }
-        }
-        lds_barrier();
-        // ---- stage 2: a code's first W are among its W rows' first W each (top: every row's in its own order, slots >= W -inf).
-        // Every (row, slot) entry counts the entries of its code ordered before it, Q lanes an entry (each a share of the code's
-        // rows, 16 slots a row in four 16-byte reads), the lanes' counts added by the xor butterfly; rank j < W: new beam j
-        {
-            constexpr int NT = 4 * H;
-            const int nent = RW << wsh;
-            int qsh = 0;
-            while ((nent << (qsh + 1)) <= NT && qsh < wsh) ++qsh;
-            const int Q = 1 << qsh, span = WP >> qsh, per = NT >> qsh;
-            const int part = threadIdx.x & (Q - 1);
-            for (int e0 = 0; e0 < nent; e0 += per) {
-                const int en = e0 + ((int)threadIdx.x >> qsh);
-                const bool in = en < nent;
-                const int r = in ? en >> wsh : 0, s = en & (WP - 1);
-                const int k = r & (WP - 1), cb = r & ~(WP - 1);
-                const float c = top_c[r][s];
-                const int v = top_v[r][s];
-                int rank = 0;
-                for (int k2 = part * span; k2 < min((part + 1) * span, W); ++k2) {
-                    const f32x4 *pc = reinterpret_cast<const f32x4 *>(&top_c[cb + k2][0]);
-                    const beam_i32x4 *pv = reinterpret_cast<const beam_i32x4 *>(&top_v[cb + k2][0]);
+                        for (int j = 0; j < 4; ++j) {
+                            const f32x4 c4 = pc[j];
+                            const beam_i32x4 v4 = pv[j];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const f32x4 c4 = pc[j];
-                        const beam_i32x4 v4 = pv[j];
-#pragma unroll
-                        for (int m = 0; m < 4; ++m) {
-                            const float c2 = c4[m];
-                            const int v2 = v4[m];
-                            if constexpr (PLAN) {
-                                const int s2 = 4 * j + m;
-                                rank += s2 < W && (c2 > c || (c2 == c && (k2 < k || (k2 == k && s2 < s)))) ? 1 : 0;
-                            } else {
-                                rank += beam_before(c2, k2, v2, c, k, v) ? 1 : 0;
+                            for (int m = 0; m < 4; ++m) {
+                                const float c2 = c4[m];
+                                const int v2 = v4[m];
+                                if constexpr (PLAN) {
+                                    const int s2 = 4 * j + m;
+                                    rank += s2 < WS && (c2 > c || (c2 == c && (k2 < k || (k2 == k && s2 < s)))) ? 1 : 0;
+                                } else {
+                                    rank += beam_before(c2, k2, v2, c, k, v) ? 1 : 0;
+                                }
                             }
                         }
                     }
+                    for (int off = 1; off < Q; off <<= 1) rank += __shfl_xor(rank, off, 64);
+                    if (!in || part != 0 || k >= W || s >= WS || rank >= WS) continue;
+                    if constexpr (GROUPS) {
+                        if (k < g * WS || k >= (g + 1) * WS) continue;
+                        rank += g * WS;                            // the new beam's index inside its code
+                        logp_s[cb + rank] = top_l[r][s];
+                        if (c > -INFINITY && g + 1 < NG)       // a finite pick: the groups behind this one pay for its note
+                            __hip_atomic_fetch_add(&cnt[r >> wsh][min(v, 63)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    const int nr = cb + rank, vv = min(v, p.vocab - 1);
+                    sel_par[nr] = k;
+                    sel_note[nr] = vv;
+                    score_s[nr] = c;                               // (read by stage 1 only: free by now)
+                    hist_p[t][nr] = (unsigned char)k;
+                    hist_v[t][nr] = (unsigned char)vv;
+                    const int code = code0 + (r >> wsh);
+                    if (code < B) {
+                        const int64_t o = ((int64_t)code * ticks + t) * W + rank;
+                        p.parents[o] = k;
+                        p.tokens[o] = vv;
+                        p.scores_hist[o] = c;
+                    }
                 }
-                for (int off = 1; off < Q; off <<= 1) rank += __shfl_xor(rank, off, 64);
-                if (!in || part != 0 || k >= W || s >= W || rank >= W) continue;
-                const int nr = cb + rank, vv = min(v, p.vocab - 1);
-                sel_par[nr] = k;
-                sel_note[nr] = vv;
-                score_s[nr] = c;                               // (read by stage 1 only: free by now)
-                hist_p[t][nr] = (unsigned char)k;
-                hist_v[t][nr] = (unsigned char)vv;
-                const int code = code0 + (r >> wsh);
-                if (code < B) {
-                    const int64_t o = ((int64_t)code * ticks + t) * W + rank;
-                    p.parents[o] = k;
-                    p.tokens[o] = vv;
-                    p.scores_hist[o] = c;
-                }
+            }
+            if constexpr (!GROUPS) break;
+            else {
+                if (g + 1 >= NG) break;
+                lds_barrier();                                     // the next group's stage 1 reads cnt
             }
         }
         lds_barrier();
@@ -540,6 +660,7 @@ __global__ __launch_bounds__(H * 4) void tick_beam_search_kernel(P p, const uint
                 at = hist_p[t][cb + at];
             }
             p.scores[(int64_t)code * W + k] = score_s[r];
+            if constexpr (GROUPS) p.log_probs[(int64_t)code * W + k] = logp_s[r];
         }
     }
 }
@@ -570,7 +691,7 @@ extern "C" int arvae_beam_select(const float *logits, const float *scores_in, in
     ARVAE_REQUIRE((int64_t)live * allowed >= width, "beam_select: %d live beams of %d allowed notes give fewer than width = %d candidates",
                   live, allowed, width);
     ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live, allow, (int64_t)0,
-                 parents, notes, scores_out);
+                 parents, notes, scores_out, 1, 0.f, (const float *)nullptr, (float *)nullptr);
     return check_launch("beam_select_kernel");
 }
 
@@ -585,7 +706,34 @@ extern "C" int arvae_beam_select_planned(const float *logits, const float *score
     if (const int rc = note_plan_check("beam_select_planned", plan, ticks, vocab)) return rc;
     ARVAE_REQUIRE(tick >= 0 && tick < ticks, "beam_select_planned: tick %d is outside [0, %d)", tick, ticks);
     ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live,
-                 plan->allow + tick * plan->tick_stride, plan->row_stride, parents, notes, scores_out);
+                 plan->allow + tick * plan->tick_stride, plan->row_stride, parents, notes, scores_out, 1, 0.f, (const float *)nullptr,
+                 (float *)nullptr);
+    return check_launch("beam_select_kernel");
+}
+
+// what the grouped entry points check of (width, groups, penalty)
+static int beam_groups_check(const char *who, int32_t width, int32_t groups, float penalty) {
+    ARVAE_REQUIRE(width >= 1 && width <= BEAM_MAX_WIDTH, "%s: width %d is outside [1, %d]", who, width, BEAM_MAX_WIDTH);
+    ARVAE_REQUIRE(groups >= 1 && groups <= width, "%s: groups %d is outside [1, width = %d]", who, groups, width);
+    ARVAE_REQUIRE(width % groups == 0, "%s: groups %d does not divide width %d", who, groups, width);
+    ARVAE_REQUIRE(std::isfinite(penalty) && penalty >= 0.f, "%s: penalty %g is not a finite number >= 0", who, (double)penalty);
+    return ARVAE_OK;
+}
+
+extern "C" int arvae_beam_select_groups(const float *logits, const float *scores_in, const float *logp_in, int32_t codes, int32_t width,
+                                        int32_t groups, float penalty, int32_t vocab, int32_t live, const arvae_note_plan_t *plan,
+                                        int32_t ticks, int32_t tick, int32_t *parents, int64_t *notes, float *scores_out, float *logp_out,
+                                        arvae_stream_t stream) {
+    ARVAE_REQUIRE(logits && scores_in && logp_in && parents && notes && scores_out && logp_out, "beam_select_groups: null pointer");
+    ARVAE_REQUIRE(codes >= 1, "beam_select_groups: codes %d is not positive", codes);
+    if (const int rc = beam_groups_check("beam_select_groups", width, groups, penalty)) return rc;
+    ARVAE_REQUIRE(vocab >= 1, "beam_select_groups: vocab %d is not positive", vocab);
+    ARVAE_REQUIRE(live >= 1 && live <= width / groups, "beam_select_groups: live %d is outside [1, width / groups = %d]", live,
+                  width / groups);
+    if (const int rc = note_plan_check("beam_select_groups", plan, ticks, vocab)) return rc;
+    ARVAE_REQUIRE(tick >= 0 && tick < ticks, "beam_select_groups: tick %d is outside [0, %d)", tick, ticks);
+    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live,
+                 plan->allow + tick * plan->tick_stride, plan->row_stride, parents, notes, scores_out, groups, penalty, logp_in, logp_out);
     return check_launch("beam_select_kernel");
 }
 
@@ -616,14 +764,20 @@ extern "C" int arvae_tick_beam_search_supported(int32_t hidden, int32_t vocab, i
     return arvae_tick_free_run_supported(hidden, vocab) && width >= 1 && width <= BEAM_MAX_WIDTH;
 }
 
+extern "C" int arvae_tick_beam_search_groups_supported(int32_t hidden, int32_t vocab, int32_t width, int32_t groups) {
+    return arvae_tick_beam_search_supported(hidden, vocab, width) && groups >= 1 && groups <= width && width % groups == 0;
+}
+
 extern "C" int64_t arvae_tick_beam_search_ws_floats(int32_t hidden) { return arvae_tick_free_run_ws_floats(hidden); }
 
-// the two one-launch searches: plan null = arvae_tick_beam_search's mask and count, else the plan (no count: dead slots exist)
+// the three one-launch searches: plan null = arvae_tick_beam_search's mask and count, else the plan (no count: dead slots exist);
+// groups 0 = not grouped, else the planned search in that many groups (log_probs then required)
 static int tick_beam_search_launch(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
                                    const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat,
                                    int32_t hidden, int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed,
                                    const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens, float *scores_hist,
-                                   int64_t *sequences, float *scores, float *ws, arvae_stream_t stream) {
+                                   int64_t *sequences, float *scores, float *ws, arvae_stream_t stream, int32_t groups = 0,
+                                   float penalty = 0.f, float *log_probs = nullptr) {
     ARVAE_REQUIRE(wts && h0_l0 && h0_l1 && gib && ptab, "tick_beam_search: null pointer");
     ARVAE_REQUIRE(wts->w_hh0 && wts->b_hh0 && wts->w_ih1 && wts->b_ih1 && wts->w_hh1 && wts->b_hh1 && wts->w_out && wts->b_out,
                   "tick_beam_search: null weight pointer");
@@ -646,7 +800,7 @@ static int tick_beam_search_launch(const arvae_tick_weights_t *wts, const float 
     ARVAE_REQUIRE(h0_stride == 0 || h0_stride >= hidden, "tick_beam_search: h0_stride %lld is below the hidden size %d",
                   (long long)h0_stride, hidden);
     ARVAE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "tick_beam_search: workspace must be 16-byte aligned");
-    TickBeamPlanned p{};
+    TickBeamGroups p{};
     p.w_hh0 = wts->w_hh0; p.b_hh0 = wts->b_hh0; p.w_ih1 = wts->w_ih1; p.b_ih1 = wts->b_ih1;
     p.w_hh1 = wts->w_hh1; p.b_hh1 = wts->b_hh1; p.w_out = wts->w_out; p.b_out = wts->b_out;
     p.h0_l0 = h0_l0; p.h0_l1 = h0_l1; p.h0_stride = h0_stride != 0 ? h0_stride : hidden; p.gib = gib; p.ptab = ptab; p.allow = allow;
@@ -654,6 +808,7 @@ static int tick_beam_search_launch(const arvae_tick_weights_t *wts, const float 
     while ((1 << p.wshift) < width) ++p.wshift;
     p.parents = parents; p.tokens = tokens; p.scores_hist = scores_hist; p.sequences = sequences; p.scores = scores;
     if (plan != nullptr) { p.plan = plan->allow; p.row_stride = plan->row_stride; p.tick_stride = plan->tick_stride; }
+    if (groups != 0) { p.groups = groups; p.gwidth = width / groups; p.penalty = penalty; p.log_probs = log_probs; }
     TickPrep tp{};
     tp.w[0] = wts->w_hh0; tp.w[1] = wts->w_ih1; tp.w[2] = wts->w_hh1;
     tp.nmat = 3;
@@ -669,7 +824,10 @@ static int tick_beam_search_launch(const arvae_tick_weights_t *wts, const float 
         tick_prep_launch<decltype(HH)::value>(tp, ws, st);
         rw_known = with_int<4, 8, 16>(rw, [&](auto RW) {
             constexpr int H = decltype(HH)::value, R = decltype(RW)::value;
-            if (plan != nullptr) ARVAE_LAUNCH((tick_beam_search_kernel<H, R, TickBeamPlanned>), gr, dim3(4 * H), 0, st, p, packed);
+            if (groups != 0) ARVAE_LAUNCH((tick_beam_search_kernel<H, R, TickBeamGroups>), gr, dim3(4 * H), 0, st, p, packed);
+            else if (plan != nullptr)
+                ARVAE_LAUNCH((tick_beam_search_kernel<H, R, TickBeamPlanned>), gr, dim3(4 * H), 0, st,
+                             static_cast<const TickBeamPlanned &>(p), packed);
             else ARVAE_LAUNCH((tick_beam_search_kernel<H, R, TickBeam>), gr, dim3(4 * H), 0, st, static_cast<const TickBeam &>(p), packed);
         });
     });
@@ -694,4 +852,16 @@ extern "C" int arvae_tick_beam_search_planned(const arvae_tick_weights_t *wts, c
     ARVAE_REQUIRE(plan != nullptr, "tick_beam_search_planned: null plan");
     return tick_beam_search_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, batch, beats, ticks_per_beat, hidden, vocab, width, nullptr,
                                    vocab, plan, parents, tokens, scores_hist, sequences, scores, ws, stream);
+}
+
+extern "C" int arvae_tick_beam_search_groups(const arvae_tick_weights_t *wts, const float *h0_l0, const float *h0_l1, int64_t h0_stride,
+                                             const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat,
+                                             int32_t hidden, int32_t vocab, int32_t width, int32_t groups, float penalty,
+                                             const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens, float *scores_hist,
+                                             int64_t *sequences, float *scores, float *log_probs, float *ws, arvae_stream_t stream) {
+    ARVAE_REQUIRE(plan != nullptr, "tick_beam_search_groups: null plan");
+    if (const int rc = beam_groups_check("tick_beam_search_groups", width, groups, penalty)) return rc;
+    ARVAE_REQUIRE(log_probs != nullptr, "tick_beam_search_groups: null log_probs");
+    return tick_beam_search_launch(wts, h0_l0, h0_l1, h0_stride, gib, ptab, batch, beats, ticks_per_beat, hidden, vocab, width, nullptr,
+                                   vocab, plan, parents, tokens, scores_hist, sequences, scores, ws, stream, groups, penalty, log_probs);
 }

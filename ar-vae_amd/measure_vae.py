@@ -528,18 +528,22 @@ class HierarchicalDecoder(Decoder):
             return self.tick_rnn_sequence(tokens, beat_out, 6, True)[0]
         return self.forward_tick_rnn(tokens, list(torch.unbind(beat_out, 0)), 6, True, 'argmax')[0]
 
-    def _beam_history(self, beat_out, width, mask, count, plan=None):
+    def _beam_history(self, beat_out, width, mask, count, plan=None, groups=None):
         """-> (parents (B, 24, W) int32, tokens (B, 24, W) int64, scores (B, 24, W), sequences (B, W, 24) int64, scores (B, W)): one
         launch (csrc/beam_decoder.hip, tick_beam_search_kernel) where it is offered, else tick by tick with the existing dense and
         gate launches, ops.beam_select and a gather of the states (ARVAE_TICK_STEPWISE=1, other layer counts, hidden sizes, V > 64).
-        plan (B, 24, V) uint8 on the device: the planned forms of both (mask and count are then not read)."""
+        plan (B, 24, V) uint8 on the device: the planned forms of both (mask and count are then not read).
+        groups (G, penalty): the diverse search (include/arvae_hip.h, "Diverse beam search") -- ops.tick_beam_search_groups where
+        offered, else ops.beam_select_groups per tick --, plan then always given (B, 24, V) or one mask (V,); a sixth tensor, the
+        log_probs (B, W), is returned."""
         nb, b, hid = beat_out.shape
         layers, vocab = self.num_layers, self.num_notes
         h0, beat_emb = self._tick_restart(beat_out.reshape(nb * b, hid))
         w_ih0, w_hh0, b_ih0, b_hh0 = self.rnn_tick.cell(0)
         out = self.tick_emb_to_note_emb[0]
         stepwise = os.environ.get('ARVAE_TICK_STEPWISE', '0') == '1'
-        if not stepwise and layers == 2 and ops.tick_beam_search_supported(hid, vocab, width):
+        if not stepwise and layers == 2 and (ops.tick_beam_search_supported(hid, vocab, width) if groups is None else
+                                            ops.tick_beam_search_groups_supported(hid, vocab, width, groups[0])):
             emb_dim = self.note_embedding_dim
             w_note, w_beat = w_ih0[:, :emb_dim].contiguous(), w_ih0[:, emb_dim:].contiguous()
             gib = ops.dense(beat_emb, w_beat, b_ih0, Link.dense(hid, 3 * hid), ACT_NONE)
@@ -547,6 +551,9 @@ class HierarchicalDecoder(Decoder):
             ptab = ops.dense(table, w_note, None, Link.dense(emb_dim, 3 * hid), ACT_NONE)
             w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
             weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias)
+            if groups is not None:
+                return ops.tick_beam_search_groups(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, groups[0],
+                                                   groups[1], plan)
             if plan is not None:
                 return ops.tick_beam_search_planned(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, plan)
             return ops.tick_beam_search(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, mask, count)
@@ -555,6 +562,7 @@ class HierarchicalDecoder(Decoder):
         base = (torch.arange(b, device=dev) * width)[:, None]
         prev = self.x_0[None].expand(b * width, -1).contiguous()
         scores = torch.zeros(b, width, device=dev)
+        logp = torch.zeros(b, width, device=dev)               # (groups only; at tick 0 the first beam of every group is read)
         parents, tokens, hist = [], [], []
         for i in range(nb):
             h = [s[i * b:(i + 1) * b].index_select(0, rows) for s in h0]
@@ -564,7 +572,10 @@ class HierarchicalDecoder(Decoder):
                 h = self._stack_step(self.rnn_tick, gi0, h, None)
                 probs = _lin(h[-1], out, ACT_RELU)
                 live = 1 if i == 0 and j == 0 else width
-                if plan is not None:
+                if groups is not None:
+                    par, note, scores, logp = ops.beam_select_groups(probs, scores, logp, min(live, width // groups[0]), groups[0], groups[1],
+                                                                     plan, i * 6 + j, nb * 6)
+                elif plan is not None:
                     par, note, scores = ops.beam_select_planned(probs, scores, live, plan, i * 6 + j)
                 else:
                     par, note, scores = ops.beam_select(probs, scores, live, mask, count)
@@ -578,9 +589,50 @@ class HierarchicalDecoder(Decoder):
         for t in range(nb * 6 - 1, -1, -1):                                       # backtracking: a gather per tick
             seq.append(tokens[:, t].gather(1, at))
             at = parents[:, t].to(torch.int64).gather(1, at)
-        return parents, tokens, hist, torch.stack(seq[::-1], 2), scores
+        res = parents, tokens, hist, torch.stack(seq[::-1], 2), scores
+        return res if groups is None else res + (logp,)
 
-    def beam_search(self, z, beam_width=4, allowed=None, return_history=False, plan=None):
+    def check_beam_groups(self, beam_width, beam_groups, diversity):
+        """beam_search's grouping, validated on the host -> (W, G, the penalty)"""
+        for name, n in (('beam_width', beam_width), ('beam_groups', beam_groups)):
+            if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+                raise TypeError(f'{name} must be an integer, got {type(n).__name__}')
+        if not 1 <= beam_width <= 16:
+            raise ValueError(f'beam_width must lie in [1, 16], got {beam_width}')
+        if not 1 <= beam_groups <= beam_width or beam_width % beam_groups:
+            raise ValueError(f'beam_groups must lie in [1, beam_width] and divide beam_width = {beam_width}, got {beam_groups}')
+        return int(beam_width), int(beam_groups), self._diversity(diversity)
+
+    @staticmethod
+    def _diversity(diversity):
+        if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real):
+            raise TypeError(f'diversity must be a number, got {type(diversity).__name__}')
+        if not math.isfinite(diversity) or diversity < 0:
+            raise ValueError(f'diversity must be a finite number >= 0, got {diversity}')
+        return float(diversity)
+
+    def _diverse_beam_search(self, z, beam_width, beam_groups, diversity, allowed, return_history, plan):
+        width, groups, lam = self.check_beam_groups(beam_width, beam_groups, diversity)
+        planned = self.note_plan(plan, z.size(0), allowed)
+        if planned is None:                                    # one mask for every (row, tick): the plan with both strides 0
+            flt = self.sampling_filter(None, None, allowed)
+            planned = torch.ones(self.num_notes, dtype=torch.uint8) if flt is None else flt[2]
+            count = int(planned.count_nonzero())
+            if width // groups > count:
+                raise ValueError(f'a group of {width // groups} beams is above the {count} allowed notes: fewer distinct hypotheses '
+                                 f'exist after the first tick')
+        planned = planned.to(z.device)                         # the one upload of the call
+
+        def run():
+            beat_out = self._beats(z)
+            parents, tokens, hist, seqs, scores, logp = self._beam_history(beat_out, width, None, None, planned, (groups, lam))
+            best = seqs[:, 0].contiguous()
+            weights = self._teacher_forced_weights(beat_out, best)
+            res = (weights, best[:, None, :], scores[:, 0].contiguous(), seqs, scores, logp)
+            return res + ((parents, tokens, hist),) if return_history else res
+        return self._eval_no_grad(run)
+
+    def beam_search(self, z, beam_width=4, allowed=None, return_history=False, plan=None, beam_groups=None, diversity=0.0):
         """The beam_width most likely measures of latent codes z (B, z_dim) under the decoder, without autograd and with dropout off
         (include/arvae_hip.h, "Beam search"): -> (weights (B, 24, V), samples (B, 1, 24), scores (B,)) of the best beam -- the weights
         from the whole-sequence kernels evaluated on its tokens --, sequences (B, W, 24) best first and scores (B, W) = their
@@ -588,7 +640,17 @@ class HierarchicalDecoder(Decoder):
         allowed: a mask of V flags (`sampling_filter`), at least beam_width of them set.
         plan (`note_plan`): the allowed notes per (row, tick), intersected with `allowed`; the candidates and the softmax of a tick are
         over that set.  Fewer than beam_width hypotheses may then exist (a forced first tick leaves one): the slots without one are
-        dead -- score -inf, listed last, their tokens inside the plan -- and beam_width need not be below the allowed notes' count."""
+        dead -- score -inf, listed last, their tokens inside the plan -- and beam_width need not be below the allowed notes' count.
+        beam_groups=G (dividing beam_width), diversity=L >= 0: the diverse search (include/arvae_hip.h, "Diverse beam search") -- the
+        beams in G groups served in order at every tick, a group paying L for every earlier-group beam that has just taken the same
+        note -> (weights, samples, score, sequences, scores, log_probs[, history]): sequences group-major and best first within a
+        group, scores the ranking scores, log_probs (B, W) the log p(x | z); weights and samples are those of group 0's best beam.
+        Without a plan a group's width must not exceed the allowed notes' count.  beam_groups=None is the call without groups."""
+        if beam_groups is None:
+            if self._diversity(diversity) != 0.0:
+                raise ValueError(f'diversity {diversity} needs beam_groups: without groups nothing pays it')
+        else:
+            return self._diverse_beam_search(z, beam_width, beam_groups, diversity, allowed, return_history, plan)
         planned = self.note_plan(plan, z.size(0), allowed)
         if planned is not None:
             if isinstance(beam_width, bool) or not isinstance(beam_width, numbers.Integral):

@@ -386,6 +386,38 @@ class MeasureVAETrainer(Trainer):
         return self.decode_latent_codes(z, sampling=sampling, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
                                         beam_width=beam_width, plan=plan)
 
+    def decode_alternatives(self, latent_codes, beam_width, beam_groups, diversity, allowed=None, playable=False, plan=None):
+        """(n, z_dim) latent codes -> (sequences (n, W, 24) int64, log_probs (n, W)): W = beam_width different likely measures per code
+        by the diverse beam search (HierarchicalDecoder.beam_search with beam_groups / diversity), group-major and best first within
+        a group, each with its log p(x | z) over the allowed notes.  allowed / playable / plan as decode_latent_codes."""
+        dev = next(self.model.parameters()).device
+        z = torch.as_tensor(latent_codes, dtype=torch.float32, device=dev).contiguous()
+        if playable:
+            allowed = self.playable_mask(allowed)
+        res = self.model.decoder.beam_search(z, beam_width=beam_width, allowed=allowed, plan=plan, beam_groups=beam_groups,
+                                             diversity=diversity)
+        return res[3], res[5]
+
+    def infill_alternatives(self, score, keep=None, keep_rhythm=False, allowed=None, playable=False, beam_width=4, beam_groups=2,
+                            diversity=0.5):
+        """Several ways to rewrite measures around what is kept of them: `score` is encoded to its posterior mean and decoded under
+        build_note_plan(score, keep, keep_rhythm, allowed, playable) by decode_alternatives.  The kept ticks come back as they were in
+        every alternative.  -> (sequences (n, W, 24) int64, log_probs (n, W))"""
+        if keep is None and not keep_rhythm:
+            raise ValueError('infill_alternatives keeps something of the score: give keep (the ticks to keep) or keep_rhythm=True')
+        self.model.decoder.check_beam_groups(beam_width, beam_groups, diversity)      # refused before the encoder runs
+        plan = self.build_note_plan(score, keep, keep_rhythm, allowed, playable)
+        dev = next(self.model.parameters()).device
+        notes = torch.as_tensor(score).reshape(plan.shape[0], 24).to(device=dev, dtype=torch.int64).contiguous()
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                z = self.model.encoder.encode_params(notes)[0]
+        finally:
+            self.model.train(was_training)
+        return self.decode_alternatives(z, beam_width, beam_groups, diversity, plan=plan)
+
     def sample_measures(self, num, temperature=1.0, top_k=None, top_p=None, allowed=None, playable=False, beam_width=None):
         """num measures drawn from the model: z ~ N(0, I) from the library's generator, every note drawn from
         softmax(probs / temperature) over the notes top_k / top_p / allowed / playable leave (decode_latent_codes).

@@ -1109,6 +1109,74 @@ def beam_select_planned(logits, scores, live, plan, tick):
     return parents, notes, out
 
 
+def _groups_plan(plan, rows, ticks, vocab):
+    """note_plan, and a uniform mask uint8 (vocab,) as the plan with both strides 0 (the grouped searches take every mask as a plan)"""
+    if plan.dim() == 1:
+        if plan.dtype != torch.uint8 or tuple(plan.shape) != (vocab,):
+            raise ValueError(f'a uniform allowed-note mask must be uint8 of shape ({vocab},), got {plan.dtype} {tuple(plan.shape)}')
+        _dev(plan)
+        plan = plan.contiguous()
+        return _lib.NotePlan(_ptr(plan), 0, 0), plan
+    return note_plan(plan, rows, ticks, vocab)
+
+
+def tick_beam_search_groups_supported(hidden, vocab, width, groups):
+    """True when the one-launch diverse beam search is offered for (hidden, vocab, width, groups); else go tick by tick
+    (beam_select_groups)."""
+    return bool(_lib.load().arvae_tick_beam_search_groups_supported(int(hidden), int(vocab), int(width), int(groups)))
+
+
+def tick_beam_search_groups(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, width, groups, penalty, plan):
+    """tick_beam_search_planned in `groups` groups of width / groups beams, a group paying `penalty` per earlier-group beam that took
+    the same note at the tick (arvae_tick_beam_search_groups; include/arvae_hip.h, "Diverse beam search") -> the planned call's five
+    tensors, group-major, and log_probs (B, W).  plan: uint8 (B, T, V), (T, V) or one mask (V,) on the device."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    ticks, dev = beats * ticks_per_beat, gib.device
+    npl, plan = _groups_plan(plan, batch, ticks, vocab)
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    parents = torch.empty(batch, ticks, width, device=dev, dtype=torch.int32)
+    tokens = torch.empty(batch, ticks, width, device=dev, dtype=torch.int64)
+    hist = torch.empty(batch, ticks, width, device=dev, dtype=torch.float32)
+    seqs = torch.empty(batch, width, ticks, device=dev, dtype=torch.int64)
+    scores = torch.empty(batch, width, device=dev, dtype=torch.float32)
+    logp = torch.empty(batch, width, device=dev, dtype=torch.float32)
+    ws = torch.empty(lib.arvae_tick_beam_search_ws_floats(hid), device=dev, dtype=torch.float32)
+    with _timed('tick_beam_search_groups', 2.0 * batch * width * ticks * (9 * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_beam_search_groups(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), batch, beats,
+                                                     ticks_per_beat, hid, vocab, int(width), int(groups), float(penalty),
+                                                     ctypes.byref(npl), _ptr(parents), _ptr(tokens), _ptr(hist), _ptr(seqs), _ptr(scores),
+                                                     _ptr(logp), _ptr(ws), _stream()), 'tick_beam_search_groups')
+    return parents, tokens, hist, seqs, scores, logp
+
+
+def beam_select_groups(logits, scores, logp, live, groups, penalty, plan, tick, ticks=None):
+    """beam_select_planned in `groups` groups served in order (arvae_beam_select_groups): scores and logp (codes, W), of every group the
+    first `live` beams live; plan as tick_beam_search_groups (ticks: the plan's, needed with a (V,) mask) -> (parents (codes, W) int32, notes (codes, W) int64, scores (codes, W), logp (codes, W))."""
+    _dev(logits, scores, logp)
+    lib = _lib.load()
+    logits, scores, logp = logits.contiguous(), scores.contiguous(), logp.contiguous()
+    codes, width = scores.shape
+    vocab = logits.shape[1]
+    if (logits.shape[0] != codes * width or scores.dtype != torch.float32 or logits.dtype != torch.float32 or logp.dtype != torch.float32
+            or tuple(logp.shape) != (codes, width)):
+        raise ValueError(f'beam_select_groups takes float32 logits ({codes * width}, V) for scores and logp ({codes}, {width}), got '
+                         f'{tuple(logits.shape)} and {tuple(logp.shape)}')
+    if ticks is None and plan.dim() == 1:
+        raise ValueError('beam_select_groups with one mask (V,) needs `ticks`, the number of ticks the search runs over')
+    ticks = int(ticks) if ticks is not None else plan.shape[-2]
+    npl, plan = _groups_plan(plan, codes, ticks, vocab)
+    parents = torch.empty(codes, width, device=logits.device, dtype=torch.int32)
+    notes = torch.empty(codes, width, device=logits.device, dtype=torch.int64)
+    out = torch.empty(codes, width, device=logits.device, dtype=torch.float32)
+    lp = torch.empty(codes, width, device=logits.device, dtype=torch.float32)
+    _lib.check(lib.arvae_beam_select_groups(_ptr(logits), _ptr(scores), _ptr(logp), codes, width, int(groups), float(penalty), vocab,
+                                            int(live), ctypes.byref(npl), ticks, int(tick), _ptr(parents), _ptr(notes), _ptr(out),
+                                            _ptr(lp), _stream()), 'beam_select_groups')
+    return parents, notes, out, lp
+
+
 def sequence_log_prob_planned(weights, tokens, plan):
     """sequence_log_prob with the softmax of row r at tick t over the notes of plan[r, t] (arvae_sequence_log_prob_planned)."""
     _dev(weights, tokens)

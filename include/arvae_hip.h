@@ -512,6 +512,44 @@ int arvae_tick_beam_search_planned(const arvae_tick_weights_t *weights, const fl
                                    int32_t *parents, int64_t *tokens, float *scores_hist, int64_t *sequences, float *scores, float *ws,
                                    arvae_stream_t stream);
 
+/* Diverse beam search of the free-running decoder (generation; beyond the reference; Vijayakumar et al. 2016): the W beams of a code
+ * in G groups that are served in order at every tick, a group paying `penalty` for every earlier-group beam that has just taken the
+ * same note -- a few DIFFERENT likely measures instead of the W most likely ones.  One definition for the entry points below.
+ *   Inputs per code: everything arvae_tick_beam_search_planned takes (the allowed notes always as a note plan A(b, t): a uniform mask
+ *   is the plan with both strides 0, "every note" a mask of vocab ones with both strides 0), width W in [1, 16], groups G with
+ *   1 <= G <= W and G dividing W, penalty: a finite fp32 >= 0.
+ *   Group g holds the beams g W' .. (g + 1) W' - 1, W' = W / G.  A beam carries `score` (what it is ranked by), `logp` (the sum of its
+ *   notes' log-softmax), its previous note and its states.  At tick 0 only the first beam of each group is live (score 0, logp 0).
+ *   At tick t the groups are served in order; for group g:
+ *     1. n_v = the number of beams chosen AT THIS TICK by the groups 0 .. g - 1 of the same code that have a finite score and note v;
+ *     2. the candidates are (k, v), k in group g, v in A(b, t); logp_v is the planned search's log-softmax over A(b, t);
+ *     3. the key a = (score_k + logp_v) - penalty * float(n_v) in fp32, in that order, each operation rounded (no fused multiply-add);
+ *     4. the group's new beams are its first W' candidates by (a descending, k ascending, v ascending); new beam j of the group takes
+ *        parent k (the index within the code), note v, score = a and logp = logp_k + logp_v;
+ *     5. slots without a finite candidate are dead as in the planned search -- score and logp -inf, listed last WITHIN THEIR GROUP,
+ *        their tokens inside the plan, their parent inside the group -- and are never counted in n_v.
+ *   Outputs: parents [batch][ticks][W] int32 (always a beam of the same group), tokens [batch][ticks][W] int64, scores_hist
+ *   [batch][ticks][W] (the ranking scores); sequences [batch][W][ticks] group-major, best first within a group; scores [batch][W] (the
+ *   last tick's ranking scores) and log_probs [batch][W] = log p(x | z) over the plan.
+ *   Consequences: G = 1 is the planned search.  Group 0 never pays (n_v = 0 gives a = c exactly): it is the planned search of width
+ *   W'.  With penalty 0 every group repeats group 0.  scores - log_probs = -penalty * (the sum over t of n_t(v_t) along the path).
+ * arvae_beam_select_groups: one tick's selection on given logits [codes*W][vocab], scores_in and logp_in [codes][W] -- of every group
+ *   the first `live` beams are read (1 at tick 0, W' afterwards) -> parents / notes / scores_out / logp_out [codes][W]; the whole plan,
+ *   `ticks` and the tick as arvae_beam_select_planned.  Any vocab >= 1: the tick-by-tick path.
+ * arvae_tick_beam_search_groups: the whole search in one launch at the shapes of arvae_tick_beam_search_groups_supported(hidden,
+ *   vocab, width, groups) = those of the planned search with G dividing W; ws as arvae_tick_beam_search.
+ * ARVAE_E_INVALID with a message before any launch: groups < 1 or above the width or not dividing it, a penalty that is negative or
+ * not finite, a null log_probs (logp_in / logp_out), and whatever the planned call refuses. */
+int arvae_beam_select_groups(const float *logits, const float *scores_in, const float *logp_in, int32_t codes, int32_t width,
+                             int32_t groups, float penalty, int32_t vocab, int32_t live, const arvae_note_plan_t *plan, int32_t ticks,
+                             int32_t tick, int32_t *parents, int64_t *notes, float *scores_out, float *logp_out, arvae_stream_t stream);
+int arvae_tick_beam_search_groups_supported(int32_t hidden, int32_t vocab, int32_t width, int32_t groups);
+int arvae_tick_beam_search_groups(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1,
+                                  int64_t h0_stride /* 0 = hidden */, const float *gib, const float *ptab, int32_t batch, int32_t beats,
+                                  int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int32_t width, int32_t groups, float penalty,
+                                  const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens, float *scores_hist,
+                                  int64_t *sequences, float *scores, float *log_probs, float *ws, arvae_stream_t stream);
+
 /* out[r] = [a[r] | b[r]] (torch.cat along dim 1/2, decoder.py:503) and its adjoint (db optionally accumulated) */
 int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,
                       arvae_stream_t stream);

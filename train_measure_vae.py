@@ -80,6 +80,14 @@ INFILL_HELP = (f'{INFILL_FLAG} N {KEEP_TICKS_FLAG} SPEC [{KEEP_RHYTHM_FLAG}]: ad
                f'The notes are the best allowed ones, drawn with {TEMPERATURE_FLAG} / {TOP_K_FLAG} / {TOP_P_FLAG}, or searched with '
                f'{BEAM_FLAG} W; {PLAYABLE_FLAG} keeps START, END and None out of the rewritten ticks.')
 num_infill, keep_ticks, keep_rhythm, drew_notes = 0, None, False, False
+# diverse beam search (MeasureVAETrainer.decode_alternatives / infill_alternatives): several different measures per code
+BEAM_GROUPS_FLAG, DIVERSITY_FLAG = '--beam_groups', '--diversity'
+ALTERNATIVES_HELP = (f'{BEAM_FLAG} W {BEAM_GROUPS_FLAG} G {DIVERSITY_FLAG} L (both, and only with {BEAM_FLAG}; G divides W, L >= 0): the '
+                     'W beams are searched in G groups, a group paying L for every note an earlier group has just taken.  '
+                     f'{SAMPLE_FLAG} then adds `alternatives` to the summary and {INFILL_FLAG} to its `infill` entry: per measure the W '
+                     'measures as note names, group by group and best first within a group, and their `log_probs`; `samples` / '
+                     '`infilled` hold the first of them.  G and L are echoed as `beam_groups` and `diversity`.')
+beam_groups, diversity = None, None
 TICKS = 24
 
 
@@ -106,7 +114,7 @@ def parse_keep_ticks(spec):
 def with_options(fn):
     for names, kwargs in reversed(MEASURE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP + '  ' + INFILL_HELP)(fn)
+    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP + '  ' + INFILL_HELP + '  ' + ALTERNATIVES_HELP)(fn)
 
 
 @with_options
@@ -180,8 +188,17 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         if num_samples > 0:
             trainer.cuda()
             model.eval()
-            _, notes = trainer.sample_measures(num_samples, temperature, top_k=top_k, top_p=top_p, playable=playable, beam_width=beam)
-            if beam is not None:
+            if beam_groups is not None:
+                from arvae_amd import ops
+                z = ops.normal_noise((num_samples, latent_space_dim), next(model.parameters()).device)
+                seqs, log_probs = trainer.decode_alternatives(z, beam, beam_groups, diversity, playable=playable)
+                notes = seqs[:, :1]
+                summary['alternatives'] = _alternatives(dataset.index2note_dicts, seqs, log_probs)
+            else:
+                _, notes = trainer.sample_measures(num_samples, temperature, top_k=top_k, top_p=top_p, playable=playable, beam_width=beam)
+            if beam_groups is not None:
+                summary['sampling'] = {'beam': beam, 'beam_groups': beam_groups, 'diversity': diversity, 'playable': playable}
+            elif beam is not None:
                 summary['sampling'] = {'beam': beam, 'playable': playable}
             elif top_k is not None or top_p is not None or playable:        # the cuts are echoed beside the measures they shaped
                 summary['sampling'] = {'temperature': temperature, 'top_k': top_k, 'top_p': top_p, 'playable': playable}
@@ -194,15 +211,28 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
             if score.shape[0] < num_infill:
                 raise SystemExit(f'{INFILL_FLAG} {num_infill}: an evaluation batch holds {score.shape[0]} measures')
             mode = 'beam' if beam is not None else ('multinomial' if drew_notes else 'argmax')
-            _, notes = trainer.infill_measures(score, keep=None if keep_ticks is None else torch.tensor(keep_ticks), keep_rhythm=keep_rhythm,
-                                               sampling=mode, temperature=temperature, top_k=top_k, top_p=top_p, playable=playable,
-                                               beam_width=4 if beam is None else beam)
+            keep = None if keep_ticks is None else torch.tensor(keep_ticks)
+            if beam_groups is not None:
+                seqs, log_probs = trainer.infill_alternatives(score, keep=keep, keep_rhythm=keep_rhythm, playable=playable, beam_width=beam,
+                                                              beam_groups=beam_groups, diversity=diversity)
+                notes = seqs[:, :1]
+            else:
+                _, notes = trainer.infill_measures(score, keep=keep, keep_rhythm=keep_rhythm, sampling=mode, temperature=temperature,
+                                                   top_k=top_k, top_p=top_p, playable=playable, beam_width=4 if beam is None else beam)
             names = dataset.index2note_dicts
             summary['infill'] = {'sampling': mode, 'keep_ticks': [t for t in range(TICKS) if keep_ticks is not None and keep_ticks[t]],
                                  'keep_rhythm': keep_rhythm, 'playable': playable,
                                  'original': [[names[int(i)] for i in row] for row in score.tolist()],
                                  'infilled': [[names[int(i)] for i in row] for row in notes.squeeze(1).tolist()]}
+            if beam_groups is not None:
+                summary['infill'].update(beam_groups=beam_groups, diversity=diversity, alternatives=_alternatives(names, seqs, log_probs))
         print(json.dumps(summary, indent=2))
+
+
+def _alternatives(names, seqs, log_probs):
+    """the summary's form of decode_alternatives' result: per measure its W measures as names and their log_probs"""
+    return [{'measures': [[names[int(i)] for i in row] for row in code], 'log_probs': [float(x) for x in lp]}
+            for code, lp in zip(seqs.tolist(), log_probs.tolist())]
 
 
 def _take_value(argv, flag, cast, default):
@@ -224,9 +254,11 @@ def _take_value(argv, flag, cast, default):
 
 def run(argv=None):
     """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p,
-    --playable and --beam.  Values of --top_k / --top_p outside their ranges raise the decoder's ValueError (sampling_filter); --beam
-    takes a width in [1, 16] and is refused together with --top_k, --top_p or --temperature (beam search draws nothing)."""
+    --playable, --beam and --beam_groups / --diversity.  Values of --top_k / --top_p outside their ranges raise the decoder's
+    ValueError (sampling_filter); --beam takes a width in [1, 16] and is refused together with --top_k, --top_p or --temperature
+    (beam search draws nothing); --beam_groups and --diversity come together and only with --beam."""
     global with_metrics, num_samples, temperature, top_k, top_p, playable, beam, num_infill, keep_ticks, keep_rhythm, drew_notes
+    global beam_groups, diversity
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
     playable = PLAYABLE_FLAG in argv
@@ -242,6 +274,17 @@ def run(argv=None):
         if top_k is not None or top_p is not None or drew:
             raise ValueError(f'{BEAM_FLAG} decodes by beam search, which draws no note: it cannot be combined with {TOP_K_FLAG}, '
                              f'{TOP_P_FLAG} or {TEMPERATURE_FLAG}')
+    beam_groups, argv = _take_value(argv, BEAM_GROUPS_FLAG, int, None)
+    diversity, argv = _take_value(argv, DIVERSITY_FLAG, float, None)
+    if beam_groups is not None or diversity is not None:       # refused here, before anything is loaded
+        if beam is None:
+            raise ValueError(f'{BEAM_GROUPS_FLAG} and {DIVERSITY_FLAG} group the beams of {BEAM_FLAG} W: give {BEAM_FLAG}')
+        if beam_groups is None or diversity is None:
+            raise ValueError(f'{BEAM_GROUPS_FLAG} G and {DIVERSITY_FLAG} L are given together')
+        if not 1 <= beam_groups <= beam or beam % beam_groups:
+            raise ValueError(f'{BEAM_GROUPS_FLAG} takes a count in [1, {beam}] that divides {BEAM_FLAG} {beam}, got {beam_groups}')
+        if not (diversity >= 0 and diversity != float('inf')):
+            raise ValueError(f'{DIVERSITY_FLAG} takes a finite number >= 0, got {diversity}')
     num_infill, argv = _take_value(argv, INFILL_FLAG, int, 0)
     spec, argv = _take_value(argv, KEEP_TICKS_FLAG, str, None)
     keep_rhythm = KEEP_RHYTHM_FLAG in argv
