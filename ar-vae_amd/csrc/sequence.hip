@@ -133,7 +133,10 @@ __global__ __launch_bounds__(256) void embed_bwd_partial_kernel(const int64_t *_
             const int b = (int)(pos / steps), t = (int)(pos % steps);
             const int64_t row = time_major ? (int64_t)t * batch + b : pos;
             v = g[row * dim + d];
-            if (d == 0) sidx[slot] = (int)idx[pos];
+            if (d == 0) {                                    // clamped as the forward kernels clamp it, before it is narrowed
+                const int64_t x = idx[pos];
+                sidx[slot] = (int)(x < 0 ? 0 : (x >= vocab ? vocab - 1 : x));
+            }
         } else if (d == 0) {
             sidx[slot] = -1;
         }
@@ -194,20 +197,20 @@ __global__ __launch_bounds__(256) void embed_bwd_wide_kernel(const int64_t *__re
     int *srow = reinterpret_cast<int *>(acc + vocab * 256), *sidx = srow + per;
     for (int i = threadIdx.x; i < cnt; i += 256) {
         const int pos = p_lo + i;
-        int v;
+        int64_t v;                                           // (the int64 token is clamped before it is narrowed, as going forward)
         if (time_major == 2) {
             const int j = pos / (beats * batch), rem = pos - j * beats * batch, beat = rem / batch, b = rem - beat * batch;
             const int t = tpb * beat + j;
             srow[i] = pos;
-            v = t == 0 ? vocab - 1 : (int)idx[b * steps + t - 1];
+            v = t == 0 ? vocab - 1 : idx[b * steps + t - 1];
             v = v < 0 ? 0 : (v >= vocab - 1 && t != 0 ? vocab - 2 : v);
         } else {
             const int b = pos / steps, t = pos - b * steps;
             srow[i] = time_major ? t * batch + b : pos;
-            v = (int)idx[pos];
+            v = idx[pos];
             v = v < 0 ? 0 : (v >= vocab ? vocab - 1 : v);
         }
-        sidx[i] = v;
+        sidx[i] = (int)v;
     }
     for (int v = 0; v < vocab; ++v) acc[v * 256 + threadIdx.x] = 0.f;
     __syncthreads();

@@ -63,7 +63,7 @@ class FusedMeasureVAE(_ArenaBound):
     def fits(self, batch):
         """the segment sums over the batch's positions keep their token indices in LDS (csrc/sequence.hip)"""
         m = self.model
-        return (m.num_notes + 1) * 1024 + (m.num_ticks_per_measure * batch + 15) // 16 * 8 <= 65536
+        return ops.segment_sum_fits(m.num_notes + 1, m.num_ticks_per_measure * batch)
 
     def descriptor(self):
         arena = self.optimizer.ensure_arena()

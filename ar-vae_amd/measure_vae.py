@@ -186,6 +186,9 @@ class Encoder(Model):
             dirs.append((gi.view(steps, b, -1), w_hh, b_hh, None, suffix != ''))
         return ops.gru_sequence(steps, dirs)
 
+    def _lookup_fits(self, steps, b):
+        return ops.segment_sum_fits(self.num_notes, steps * b)
+
     def _first_layer_by_lookup(self, score_tensor, steps, b):
         """Layer 0 sees embedded tokens, so its input projection takes only `num_notes` distinct values: P = table W_ih^T + b_ih
         (both directions side by side, num_notes x 6H: one small product) and gi[t, b] = P[score[b, t]] (a lookup, no
@@ -195,7 +198,7 @@ class Encoder(Model):
         two directions' projections are not adjacent in memory (ops.dense_pair)."""
         # the lookup's backward is the wide-row segment sum (csrc/sequence.hip, embed_bwd_wide_kernel): its per-token accumulators
         # and this batch's positions must fit 64 KB of LDS -- the decoder's lookup and FusedMeasureVAE.fits() test the same bound
-        if self.num_notes * 1024 + (steps * b + 15) // 16 * 8 > 65536:
+        if not self._lookup_fits(steps, b):
             return None, None
         wf, whf, bf, bhf = self.lstm.cell(0, '')
         wr, whr, br, bhr = self.lstm.cell(0, '_reverse')
@@ -722,6 +725,10 @@ class HierarchicalDecoder(Decoder):
             return _split_layers(flat, hid, self.num_layers), beat_emb
         return self.hidden_init(bo, 'tick'), _lin(bo, lb, ACT_SELU)
 
+    def _tick_lookup_fits(self, positions):
+        """the segment sum's LDS holds the vocabulary, x_0 and this batch's ticks; gate rows are multiples of four floats"""
+        return (3 * self.rnn_hidden_size) % 4 == 0 and ops.segment_sum_fits(self.num_notes + 1, positions)
+
     def tick_rnn_sequence(self, score_tensor, beat_out, tick_seq_len, teacher_forced, mask=None, uniforms=None):
         """The tick RNN restarts from a beat-dependent hidden state at every beat (decoder.py:459-525), so given the
         fed-back tokens the four beats are independent 6-step sequences: they run as ONE sequence launch per layer over
@@ -741,7 +748,7 @@ class HierarchicalDecoder(Decoder):
             with torch.no_grad():
                 tokens = self._free_running_tokens(beat_out.detach(), h0, beat_emb, mask, uniforms)
         w_ih0, _, b_ih0, _ = self.rnn_tick.cell(0)
-        if (3 * hid) % 4 == 0 and (self.num_notes + 1) * 1024 + (steps * nb * b + 15) // 16 * 8 <= 65536:    # (the segment sum's LDS)
+        if self._tick_lookup_fits(steps * nb * b):
             # layer-0 input projection by lookup: W_ih0 applied once to the vocabulary's embeddings, x_0 and the beat embeddings
             # (num_notes + 1 + 4B rows), each tick's row gathered and added (ops.tick_input_projection)
             gi0 = ops.tick_input_projection(self.note_embedding_layer.weight, self.x_0, beat_emb, w_ih0, b_ih0, tokens, nb, steps)

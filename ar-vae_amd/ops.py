@@ -1232,6 +1232,13 @@ class _EmbedFn(Function):
         return None, (None if direct else buf), None
 
 
+def segment_sum_fits(entries, positions):
+    """Does the wide-row segment sum (csrc/sequence.hip, embed_bwd_wide_kernel) hold `entries` table rows x `positions` gradient rows
+    in its 64 KB of LDS?  256 fp32 accumulators per entry and two ints per position of one of its 16 position groups: the bound
+    arvae_embed_bwd (dim > 128) and arvae_tick_gi_bwd (entries = vocab + 1) refuse beyond."""
+    return entries * 1024 + (positions + 15) // 16 * 8 <= 65536
+
+
 def embed(idx, table, time_major=False):
     """nn.Embedding lookup of int64 idx [B, T] -> [B, T, D] (or [T, B, D] when time_major)."""
     if idx.dtype != torch.int64:

@@ -352,7 +352,10 @@ int arvae_tick_free_run_layers(const arvae_tick_stack_t *stack, const float *gib
  * a workspace of arvae_embed_bwd_ws_floats() floats.  `table` may also be a per-vocabulary PROJECTION table: a Linear layer
  * applied to embedded tokens is a lookup of table W^T + b (the encoder's layer-0 input projection of both directions,
  * 768 columns at hidden 128: encoder.py:27-37,111-114 computes it per position) -- any `dim`; rows wider than 128 take a
- * column-parallel segment-sum kernel in embed_bwd (vocab * 1 KB + 256 B of LDS <= 64 KB). */
+ * column-parallel segment-sum kernel in embed_bwd (vocab * 1 KB + 256 B of LDS <= 64 KB).
+ * An index outside [0, vocab) is read from, and credited to, the nearest valid row (0 or vocab - 1) in every form: forward and
+ * backward, any dim, either row order; the int64 is clamped before it is narrowed.  arvae_tick_gi_fwd / _bwd clamp a fed-back
+ * token the same way (row `vocab`, x_0, is reached at tick 0 only). */
 int arvae_embed_fwd(const int64_t *idx, const float *table, int32_t batch, int32_t steps, int32_t dim, int32_t vocab,
                     int32_t time_major, float *out, arvae_stream_t stream);
 int64_t arvae_embed_bwd_ws_floats(int32_t batch, int32_t steps, int32_t dim, int32_t vocab);

@@ -13,12 +13,13 @@ RHY_COEFFS = np.array([0.20, 1, 2, 0.5, 2, 1, 0.67, 1, 2, 0.5, 2, 1,
                        0.25, 1, 2, 0.5, 2, 1, 0.67, 1, 2, 0.5, 2, 1], np.float64)
 
 
-def attribute_labels(score, midi_lut, is_note, is_density_note):
-    """score (B,24) int -> (B,4) float32 [rhy_complexity, pitch_range, note_density, contour]."""
+def attribute_labels(score, midi_lut, is_note, is_density_note, rhythm_weights=None):
+    """score (B,T) int -> (B,4) float32 [rhy_complexity, pitch_range, note_density, contour].
+    rhythm_weights: T weights for measures of another length than 24 ticks (default: RHY_COEFFS)."""
     score = np.asarray(score)
     b, t = score.shape
     onset = is_note[score].astype(bool)
-    w = RHY_COEFFS.astype(np.float32)
+    w = (RHY_COEFFS if rhythm_weights is None else np.asarray(rhythm_weights)).astype(np.float32)
     out = np.zeros((b, 4), np.float32)
     out[:, 0] = (w[None, :] * onset.astype(np.float32)).sum(1, dtype=np.float32) / w.sum(dtype=np.float32)
     out[:, 2] = is_density_note[score].sum(1).astype(np.float32) / np.float32(t)
