@@ -44,6 +44,21 @@ class DeviceLoader:
     def __len__(self):
         return len(self.plan(self.hi - self.lo, self.batch_size, self.world, self.drop_last))
 
+    def batch_at(self, number):
+        """the number-th batch of an unshuffled, unsharded walk without assembling the ones before it; None past the end"""
+        if self.shuffle or self.world > 1:
+            raise RuntimeError('batch_at() needs a loader that walks its rows in order')
+        plan = self.plan(self.hi - self.lo, self.batch_size, 1, self.drop_last)
+        if not 0 <= number < len(plan):
+            return None
+        offset, rows = plan[number]
+        idx = torch.arange(self.lo + offset, self.lo + offset + rows, device=self.columns[0].device)
+        return self._gather(idx)
+
+    def _gather(self, idx):
+        return tuple(ops.gather_rows_u8(c, idx, self.u8_scale) if c.dtype == torch.uint8 else c.index_select(0, idx)
+                     for c in self.columns)
+
     def __iter__(self):
         dev = self.columns[0].device
         n = self.hi - self.lo
@@ -57,5 +72,4 @@ class DeviceLoader:
             order = torch.arange(self.lo, self.hi, device=dev)
         for offset, rows in self.plan(n, self.batch_size, self.world, self.drop_last):
             idx = order[offset + self.rank * rows:offset + (self.rank + 1) * rows]
-            yield tuple(ops.gather_rows_u8(c, idx, self.u8_scale) if c.dtype == torch.uint8 else c.index_select(0, idx)
-                        for c in self.columns)
+            yield self._gather(idx)

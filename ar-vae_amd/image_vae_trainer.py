@@ -203,6 +203,134 @@ class ImageVAETrainer(Trainer):
         with torch.no_grad():
             return torch.sigmoid(self.model.decode(z.contiguous()))
 
+    # -- figures (image_vae_trainer.py:405-552): decoder logits -> file bytes in one render launch per figure
+    #    (ops.render_frames: sigmoid, make_grid and the cast to uint8), written by arvae_amd.figures.  Every method returns the
+    #    paths it wrote.  deterministic=True decodes the posterior mean instead of the sampled code: reproducible figures -----
+    def _interpretability(self):
+        """{attribute: (latent dimension, score)} of the evaluation metrics (results_dict.json, or computed now)"""
+        if 'interpretability' not in self.metrics:
+            self.compute_eval_metrics()
+        if 'interpretability' not in self.metrics:
+            raise RuntimeError('the figures sweep the dimensions of the interpretability metric, which this evaluation split was '
+                               'too small to compute')
+        return self.metrics['interpretability']
+
+    def _eval_batch(self, number, batch_size=1):
+        """(inputs, labels) of the number-th evaluation batch, without touching the batches before it; None past the end"""
+        import itertools
+        loader = self.dataset.data_loaders(batch_size=batch_size)[2]
+        if hasattr(loader, 'batch_at'):
+            batch = loader.batch_at(number)
+        else:
+            batch = next(itertools.islice(iter(loader), number, None), None)
+        if batch is None:
+            print(f'evaluation batch {number} (batch size {batch_size}) is past the end of the split: no figure')
+            return None
+        return self.process_batch_data(batch)
+
+    def _code_and_logits(self, inputs, deterministic):
+        """(z (B, z_dim), reconstruction logits (B, 1, H, W)): the forward pass's sampled code, or the posterior mean"""
+        self.model.eval()
+        with torch.no_grad():
+            if deterministic:
+                z = self.model.encode(inputs).loc
+                return z, self.model.decode(z.contiguous())
+            out = self.model(inputs)
+            return out[3], out[0]
+
+    def _decode_sweeps(self, z, sweeps):
+        """logits of ONE decoder batch: for every entry of `sweeps`, a {latent dimension: values (P,)}, the code z (1, z_dim)
+        repeated P times with those dimensions overwritten; the entries follow one another in the batch"""
+        parts = []
+        for sweep in sweeps:
+            zs = z.repeat(next(iter(sweep.values())).numel(), 1)
+            for d, values in sweep.items():
+                zs[:, d] = values
+            parts.append(zs)
+        with torch.no_grad():
+            return self.model.decode(torch.cat(parts).contiguous())
+
+    def _save_dir(self):
+        return Trainer.get_save_dir(self.model)
+
+    def _write_original_and_recons(self, sample_id, inputs, recons_logits, rounding):
+        from . import figures
+        paths = []
+        for name, src, logits in (('original', inputs, False), ('recons', recons_logits.view(inputs.size()), True)):
+            frame = ops.render_frames(src.contiguous(), [[0]], nrow=1, pad_value=1.0, logits=logits, rounding=rounding)
+            paths.append(figures.write_png(frame, os.path.join(self._save_dir(), f'{name}_{sample_id}.png')))
+        return paths
+
+    def create_latent_gifs(self, sample_id=9, num_points=10, deterministic=False):
+        """gif_interpolations_{dataset_type}_{sample_id}.gif: num_points frames; frame n shows, side by side, the sample decoded
+        with each attribute's latent dimension (attr_dict order) set to linspace(-4, 4, num_points)[n].  All attributes' sweeps
+        leave the decoder as one batch."""
+        from . import figures
+        interp = self._interpretability()
+        dims = [int(interp[a][0]) for a in self.attr_dict if a not in ('digit_identity', 'color')]
+        batch = self._eval_batch(sample_id)
+        if batch is None:
+            return []
+        z, _ = self._code_and_logits(batch[0], deterministic)
+        sweep = torch.linspace(-4.0, 4.0, num_points, device=z.device)
+        logits = self._decode_sweeps(z, [{d: sweep} for d in dims])                    # attribute-major: image a * num_points + n
+        cells = np.arange(len(dims) * num_points).reshape(len(dims), num_points).T     # cells[n][a] = a * num_points + n
+        frames = ops.render_frames(logits, cells, nrow=8, padding=2, pad_value=1.0, logits=True, rounding=False)
+        path = os.path.join(self._save_dir(), f'gif_interpolations_{self.dataset_type}_{sample_id}.gif')
+        return [figures.write_gif(frames, path)]
+
+    def plot_latent_interpolations(self, attr_str='slant', num_points=10, sample_ids=(5, 1, 30, 19, 23, 21, 17, 61, 9, 28),
+                                   deterministic=False, rounding=True):
+        """per sample: latent_interpolations_{attr_str}_{id}.png (one row: the attribute's dimension over linspace(-4, 4,
+        num_points)), original_{id}.png and recons_{id}.png.  Samples past the end of the evaluation split are left out, as in the
+        reference's loop."""
+        from . import figures
+        dim = int(self._interpretability()[attr_str][0])
+        paths = []
+        for sample_id in sample_ids:
+            batch = self._eval_batch(sample_id)
+            if batch is None:
+                continue
+            z, recons = self._code_and_logits(batch[0], deterministic)
+            logits = self._decode_sweeps(z, [{dim: torch.linspace(-4.0, 4.0, num_points, device=z.device)}])
+            frame = ops.render_frames(logits, [list(range(num_points))], nrow=num_points, pad_value=1.0, rounding=rounding)
+            paths.append(figures.write_png(frame, os.path.join(self._save_dir(), f'latent_interpolations_{attr_str}_{sample_id}.png')))
+            paths += self._write_original_and_recons(sample_id, batch[0], recons, rounding)
+        return paths
+
+    def plot_latent_interpolations2d(self, attr_str1, attr_str2, num_points=10, sample_id=9, deterministic=False, rounding=True):
+        """latent_interpolations_2d_({attr_str1},{attr_str2})_{id}.png: the num_points x num_points grid of
+        compute_latent_interpolations2d ('ij': attr_str1's dimension changes down the rows, attr_str2's along them), with
+        original_{id}.png and recons_{id}.png"""
+        from . import figures
+        interp = self._interpretability()
+        dim1, dim2 = int(interp[attr_str1][0]), int(interp[attr_str2][0])
+        batch = self._eval_batch(sample_id)
+        if batch is None:
+            return []
+        z, recons = self._code_and_logits(batch[0], deterministic)
+        x = torch.linspace(-4.0, 4.0, num_points, device=z.device)
+        z1, z2 = torch.meshgrid([x, x], indexing='ij')
+        logits = self._decode_sweeps(z, [{dim1: z1.reshape(-1), dim2: z2.reshape(-1)}])
+        frame = ops.render_frames(logits, [list(range(num_points * num_points))], nrow=num_points, pad_value=1.0, rounding=rounding)
+        path = os.path.join(self._save_dir(), f'latent_interpolations_2d_({attr_str1},{attr_str2})_{sample_id}.png')
+        return [figures.write_png(frame, path)] + self._write_original_and_recons(sample_id, batch[0], recons, rounding)
+
+    def plot_latent_reconstructions(self, num_points=10, deterministic=False, rounding=True):
+        """r_original_0.png / r_recons_0.png: the first evaluation batch of num_points images and its reconstructions, one row each"""
+        from . import figures
+        batch = self._eval_batch(0, batch_size=num_points)
+        if batch is None:
+            return []
+        inputs = batch[0]
+        _, recons = self._code_and_logits(inputs, deterministic)
+        cells = [list(range(inputs.size(0)))]
+        paths = []
+        for name, src, logits in (('r_original_0', inputs, False), ('r_recons_0', recons.view(inputs.size()), True)):
+            frame = ops.render_frames(src.contiguous(), cells, nrow=num_points, pad_value=1.0, logits=logits, rounding=rounding)
+            paths.append(figures.write_png(frame, os.path.join(self._save_dir(), f'{name}.png')))
+        return paths
+
     def save_representations(self, path, data_loader=None, batch_size=128):
         """Write the record the reference's compute_eval_metrics consumes (image_vae_trainer.py:289-317): latent codes,
         attribute columns and attribute names as JSON, from the encoder-only pass.  compute_eval_metrics computes the

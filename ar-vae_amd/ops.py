@@ -1621,6 +1621,57 @@ def gather_rows_u8(src, idx, scale=1.0):
     return out
 
 
+RENDER_SRC_LOGITS, RENDER_ROUND, RENDER_RGB = 1, 2, 4
+
+
+def render_geometry(h, w, cells_per_frame, nrow, padding):
+    """(Hg, Wg) of torchvision.utils.make_grid for cells_per_frame images of h x w"""
+    xmaps = min(nrow, cells_per_frame)
+    ymaps = -(-cells_per_frame // xmaps)
+    return ymaps * (h + padding) + padding, xmaps * (w + padding) + padding
+
+
+def render_frames(src, cells, nrow=8, padding=2, pad_value=1.0, logits=True, rounding=False, rgb=True, out=None):
+    """Image grids as bytes, one launch for all frames (arvae_render_frames): sigmoid (logits=True), make_grid and the cast to
+    uint8 of the reference's figure code.
+    src (N, H, W) or (N, 1, H, W) fp32 on the device; cells (F, cells_per_frame) CPU integers, the source image of every cell of every
+    frame, -1 = a blank cell -> (F, Hg, Wg, 3 if rgb else 1) uint8, what PIL.Image.fromarray takes.  rounding: floor(255 v + 0.5)
+    (torchvision's save_image) instead of truncation (the .byte() of the GIF code).  One cell in one frame is rendered without
+    padding, as make_grid returns a lone image.  out: a contiguous uint8 tensor of the result's size to write into."""
+    import numpy as np
+    if not torch.is_tensor(src) or src.dtype != torch.float32:
+        raise TypeError('render_frames needs an fp32 tensor of images')
+    if src.dim() == 4 and src.shape[1] == 1:
+        src = src[:, 0]
+    if src.dim() != 3 or src.numel() == 0:
+        raise ValueError(f'render_frames needs (N, H, W) or (N, 1, H, W) images, got {tuple(src.shape)}')
+    cells = np.asarray(cells.cpu() if torch.is_tensor(cells) else cells)
+    if cells.ndim != 2 or cells.size == 0 or not np.issubdtype(cells.dtype, np.integer):
+        raise ValueError('render_frames needs cells as a non-empty (frames, cells_per_frame) integer array')
+    n, h, w = src.shape
+    if cells.min() < -1 or cells.max() >= n:
+        raise ValueError(f'render_frames: cells must lie in [-1, {n}) (-1 = blank), got [{cells.min()}, {cells.max()}]')
+    _dev(src)
+    frames, per_frame = cells.shape
+    nrow, padding = int(nrow), 0 if frames == 1 and per_frame == 1 else int(padding)
+    channels = 3 if rgb else 1
+    lib = _lib.load()
+    if lib.arvae_render_frame_bytes(h, w, per_frame, nrow, padding, channels) < 0:
+        _lib.check(-1, 'render_frame_bytes')
+    hg, wg = render_geometry(h, w, per_frame, nrow, padding)
+    if out is None:
+        out = torch.empty((frames, hg, wg, channels), device=src.device, dtype=torch.uint8)
+    else:
+        _dev(out)
+        if out.dtype != torch.uint8 or out.numel() != frames * hg * wg * channels or out.device != src.device:
+            raise ValueError(f'render_frames: out must hold {frames} x {hg} x {wg} x {channels} bytes on {src.device}')
+    cells_dev = torch.from_numpy(np.ascontiguousarray(cells, dtype=np.int32)).to(src.device)
+    flags = (RENDER_SRC_LOGITS if logits else 0) | (RENDER_ROUND if rounding else 0) | (RENDER_RGB if rgb else 0)
+    _lib.check(lib.arvae_render_frames(_ptr(src), n, h, w, _ptr(cells_dev), frames, per_frame, nrow, padding, float(pad_value),
+                                       flags, _ptr(out), _stream()), 'render_frames')
+    return out.view(frames, hg, wg, channels)
+
+
 def measure_attributes(score, tables, rhythm_weights, rhythm_norm):
     """(B, 24) int64 measures -> (B, 4) [rhythmic complexity, pitch range, note density, contour]."""
     _dev(score)

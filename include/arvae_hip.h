@@ -572,6 +572,33 @@ int arvae_broadcast_rows(const float *v, int64_t rows, int32_t cols, float *y, a
 int arvae_gather_rows_u8(const uint8_t *src, int64_t n_rows, int64_t row_elems, const int64_t *idx, int64_t count,
                          float scale, float *out, arvae_stream_t stream);
 
+/* Figures of the image models (added under ABI 16: symbols only).  One launch turns decoder outputs into the bytes of
+ * n_frames image grids: sigmoid, grid assembly and the cast to bytes in one pass.  Replaces torch.sigmoid +
+ * torchvision.utils.make_grid + .mul(255).clamp(0, 255).byte().permute(1, 2, 0) of create_latent_gifs, and the save_image
+ * calls of the plot_latent_* methods (imagevae/image_vae_trainer.py:405-552).
+ *   src    [n_images, h, w] fp32
+ *   cells  [n_frames, cells_per_frame] int32: the source image of every cell of every frame; -1 (or any index outside
+ *          [0, n_images)) leaves the cell blank, i.e. filled with the pad value
+ *   out    [n_frames, Hg, Wg, C] uint8 (what PIL.Image.fromarray takes), any alignment; C = 3 with ARVAE_RENDER_RGB, else 1
+ * Grid geometry of make_grid: xmaps = min(nrow, cells_per_frame), ymaps = ceil(cells_per_frame / xmaps),
+ * Hg = ymaps (h + padding) + padding, Wg = xmaps (w + padding) + padding; cell k's top-left corner is
+ * (padding + (k / xmaps)(h + padding), padding + (k % xmaps)(w + padding)); the cells of a ragged last row are pad.
+ * flags:
+ *   ARVAE_RENDER_SRC_LOGITS  v = 1 / (1 + expf(-src)) (exactly 1 from src = 20 on); otherwise v = src
+ *   ARVAE_RENDER_ROUND       byte = floor(255 v + 0.5) clamped to [0, 255] (save_image); otherwise 255 v clamped and truncated
+ *                            (the .byte() of the GIF code).  Product and sum are rounded to fp32 one after the other.
+ *   ARVAE_RENDER_RGB         three equal channels (make_grid's expansion of a 1-channel image)
+ * The pad byte is the same quantiser applied to pad_value.
+ * arvae_render_frame_bytes: Hg * Wg * channels, or -1 (bad argument, channels outside {1, 3}, or 2^31 bytes and more:
+ * such a frame cannot be rendered). */
+#define ARVAE_RENDER_SRC_LOGITS 1
+#define ARVAE_RENDER_ROUND 2
+#define ARVAE_RENDER_RGB 4
+int64_t arvae_render_frame_bytes(int h, int w, int cells_per_frame, int nrow, int padding, int channels);
+int arvae_render_frames(const float *src, int64_t n_images, int h, int w, const int32_t *cells, int n_frames,
+                        int cells_per_frame, int nrow, int padding, float pad_value, int flags, uint8_t *out,
+                        arvae_stream_t stream);
+
 /* Attribute labels of a batch of measures.  Replaces MeasureVAETrainer.compute_attribute_labels
  * (measurevae/measure_vae_trainer.py:167-186 -> data/dataloaders/bar_dataset.py:338-500):
  *   out[b] = [rhythmic complexity, pitch range/26, note density, contour/26]

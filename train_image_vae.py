@@ -8,8 +8,10 @@ second epoch, and after training the script prints a representation summary comp
 attributes of the evaluation split, test loss and accuracy); `--metrics` adds the reference's disentanglement metrics
 (Interpretability, SCC, Modularity, MIG, SAP: arvae_amd.evaluation, KSG estimator in HIP) to it, and `--digit_acc` (Morpho-MNIST
 only) the reference's digit_pred_acc: the accuracy of the ResNet-18 digit classifier (arvae_amd.mnist_resnet, HIP) on the
-inputs, the reconstructions and the latent sweeps; it needs the classifier's checkpoint, models/MnistRESNET/MnistRESNET.pt.  The
-GIF plots stay outside this build's scope.
+inputs, the reconstructions and the latent sweeps; it needs the classifier's checkpoint, models/MnistRESNET/MnistRESNET.pt.
+`--gifs` writes the reference's latent-traversal GIFs (create_latent_gifs for samples 0, 1 and 4) and `--plots` the PNG figures of
+its commented-out block (plot_latent_reconstructions, plot_latent_interpolations per attribute, plot_latent_interpolations2d)
+into models/<repr>/results/, rendered on the device (arvae_amd.ops.render_frames, HIP).
 """
 import json
 import os
@@ -61,12 +63,35 @@ DIGIT_ACC_FLAG = '--digit_acc'
 DIGIT_ACC_HELP = (f'{DIGIT_ACC_FLAG}: (mnist only) add digit_pred_acc, the ResNet-18 digit classifier\'s accuracy on inputs, '
                   'reconstructions and latent sweeps, to the evaluation summary; needs models/MnistRESNET/MnistRESNET.pt.')
 with_digit_acc = False
+GIFS_FLAG = '--gifs'
+GIFS_HELP = (f'{GIFS_FLAG}: write the latent-traversal GIFs of evaluation samples 0, 1 and 4 (create_latent_gifs) into '
+             'models/<repr>/results/.')
+with_gifs = False
+PLOTS_FLAG = '--plots'
+PLOTS_HELP = (f'{PLOTS_FLAG}: write the PNG figures (reconstructions, the latent interpolations of every attribute, the 2-d grid '
+              'of slant / thickness for mnist, posx / posy for dsprites) into models/<repr>/results/.')
+with_plots = False
 
 
 def with_options(fn):
     for names, kwargs in reversed(IMAGE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP + '\n\n' + DIGIT_ACC_HELP)(fn)
+    return click.command(epilog='\n\n'.join((METRICS_HELP, DIGIT_ACC_HELP, GIFS_HELP, PLOTS_HELP)))(fn)
+
+
+def write_figures(trainer, dataset_type, gifs, plots):
+    """the reference script's figure calls (train_image_vae.py:127-153); -> the paths written"""
+    paths = []
+    if gifs:
+        for sample_id in (0, 1, 4):
+            paths += trainer.create_latent_gifs(sample_id=sample_id)
+    if plots:
+        paths += trainer.plot_latent_reconstructions()
+        for attr_str in trainer.attr_dict:
+            if attr_str not in ('digit_identity', 'color'):
+                paths += trainer.plot_latent_interpolations(attr_str)
+        paths += trainer.plot_latent_interpolations2d(*(('slant', 'thickness') if dataset_type == 'mnist' else ('posx', 'posy')))
+    return paths
 
 
 @with_options
@@ -128,7 +153,8 @@ def main(dataset_type, batch_size, num_epochs, lr, beta, capacity, gamma, delta,
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'latent_mean_abs': [float(v) for v in abs(codes).mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
-        metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or (with_digit_acc and dataset_type == 'mnist') else {}
+        want_figures = with_gifs or with_plots
+        metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or want_figures or (with_digit_acc and dataset_type == 'mnist') else {}
         if with_metrics:
             summary.update(metrics)
         if with_digit_acc and dataset_type != 'mnist':
@@ -137,15 +163,24 @@ def main(dataset_type, batch_size, num_epochs, lr, beta, capacity, gamma, delta,
             trainer.metrics = dict(metrics)              # the sweeps run over the interpretability metric's dimensions
             summary.update(trainer.get_resnet_accuracy(batch_size=eval_bs))
         print(json.dumps(summary, indent=2))
+        if want_figures and 'interpretability' not in metrics:
+            print(f'{GIFS_FLAG} / {PLOTS_FLAG}: the figures sweep the dimensions of the interpretability metric, which this evaluation '
+                  f'split ({codes.shape[0]} codes) was too small to compute; skipped')
+        elif want_figures:
+            trainer.metrics = dict(metrics)
+            for path in write_figures(trainer, dataset_type, with_gifs, with_plots):
+                print('wrote', path)
 
 
 def run(argv=None):
-    """the command line: the reference's flags (main) plus this build's opt-in --metrics and --digit_acc"""
-    global with_metrics, with_digit_acc
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --digit_acc, --gifs and --plots"""
+    global with_metrics, with_digit_acc, with_gifs, with_plots
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
     with_digit_acc = DIGIT_ACC_FLAG in argv
-    main(args=[a for a in argv if a not in (METRICS_FLAG, DIGIT_ACC_FLAG)])
+    with_gifs = GIFS_FLAG in argv
+    with_plots = PLOTS_FLAG in argv
+    main(args=[a for a in argv if a not in (METRICS_FLAG, DIGIT_ACC_FLAG, GIFS_FLAG, PLOTS_FLAG)])
 
 
 if __name__ == '__main__':
