@@ -208,6 +208,9 @@ SIGNATURES = {
     'arvae_gather_rows_u8': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_vp, c_vp]),
     'arvae_render_frame_bytes': (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     'arvae_render_frames': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp]),
+    'arvae_measure_notes': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    'arvae_render_pianoroll_bytes': (c_i64, [c_i32] * 9),
+    'arvae_render_pianoroll': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_f32, c_f32] + [c_i32] * 8 + [c_vp, c_vp]),
     'arvae_measure_attributes': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp]),
     'arvae_image_vae_ws_floats': (c_i64, [_P(ImageVaeDesc), c_i32, c_i64]),
     'arvae_image_vae_forward': (c_i32, [_P(ImageVaeDesc), c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, _P(c_vp), c_vp, c_vp,

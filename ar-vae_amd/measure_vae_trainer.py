@@ -12,25 +12,14 @@ import numpy as np
 import torch
 
 from . import ops
+from .midi import NON_NOTES as _NON_NOTES, pitch_to_midi      # (plain Python: the MIDI reader needs both without torch)
 from .trainer import Trainer
 
 MUSIC_REG_TYPE = {'rhy_complexity': 0, 'pitch_range': 1, 'note_density': 2, 'contour': 3}
 
 # reference data/dataloaders/bar_dataset_helpers.py:21-30
 RHY_COMPLEXITY_COEFFS = [0.20, 1, 2, 0.5, 2, 1, 0.67, 1, 2, 0.5, 2, 1, 0.25, 1, 2, 0.5, 2, 1, 0.67, 1, 2, 0.5, 2, 1]
-_NON_NOTES = ('__', 'START', 'END', 'rest', None)
 _PADDING_SYMBOLS = ('START', 'END', None, 'None')        # vocabulary entries that are not music: never part of a playable measure
-_PITCH = {'C': 0, 'D': 2, 'E': 4, 'F': 5, 'G': 7, 'A': 9, 'B': 11}
-
-
-def pitch_to_midi(name):
-    """'G3', 'F#4', 'B-4' / 'Bb4' -> MIDI number (what music21.pitch.Pitch(name).midi gives)."""
-    step, rest = name[0].upper(), name[1:]
-    acc = 0
-    while rest and rest[0] in '#-b':
-        acc += 1 if rest[0] == '#' else -1
-        rest = rest[1:]
-    return 12 * (int(rest) + 1) + _PITCH[step] + acc
 
 
 def build_measure_tables(dataset, device):
@@ -455,6 +444,85 @@ class MeasureVAETrainer(Trainer):
                 parts[num_points // 2] = original_score
             score = concat(parts)
         return score, tensor_score
+
+    # -- listening and looking: MIDI files and piano-roll PNGs (measure_vae_trainer.py:256-279, utils/plotting.py:307-362) ----------
+    def _note_tables(self, device):
+        """(build_measure_tables' tables, the slur's index): what ops.measure_notes / ops.render_pianoroll take"""
+        slur = self.dataset.note2index_dicts.get('__')
+        if slur is None:
+            raise ValueError("the dataset's vocabulary has no slur symbol '__'")
+        return self._attr_tables(device)[0], int(slur)
+
+    def _look(self, look):
+        """the reference's y-range of the dataset (utils/plotting.py:338-341) under the caller's look"""
+        return {'pitch_lo': 55, 'pitch_hi': 90 if self.dataset_type == 'bach' else 84, **look}
+
+    def write_measures(self, tensor_score, stem, values=None, attr_str=None, **look):
+        """A sequence of measures -- note indices (K, 24), (K, 1, 24) or (24,) -- as <stem>.mid and <stem>.png: the note events and
+        the piano roll come from one launch each (ops.measure_notes, ops.render_pianoroll) and reach the host in one copy each.
+        values (K,): a number per measure, drawn as dots in a panel beside the roll; attr_str without values: that attribute's
+        labels of the measures (compute_attribute_labels).  look: render_pianoroll's keywords.  -> (midi path, png path)"""
+        import os
+        from . import figures, midi
+        dev = next(self.model.parameters()).device
+        score = torch.as_tensor(tensor_score)
+        score = score.reshape(-1, score.shape[-1]).to(device=dev, dtype=torch.int64).contiguous()
+        tables, slur = self._note_tables(dev)
+        events = ops.measure_notes(score, tables, slur=slur)
+        if values is not None:
+            values = torch.as_tensor(values, dtype=torch.float32).to(dev).reshape(1, score.shape[0])
+        elif attr_str is not None:
+            values = self.compute_attribute_labels(score, [attr_str]).reshape(1, score.shape[0])
+        frame = ops.render_pianoroll(score[None], tables, values, slur=slur, **self._look(look))
+        folder = os.path.dirname(stem)
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        return midi.write_midi(stem + '.mid', events.cpu().numpy()), figures.write_png(frame, stem + '.png')
+
+    def plot_latent_interpolations(self, latent_codes, attr_str, num_points=10, dim=None, sweep_points=5, **look):
+        """For each of the first n = min(num_points, len(latent_codes)) codes: original_{i}.mid (the code decoded),
+        latent_interpolations_{attr_str}_{i}.mid (the code with latent dimension `dim` swept over linspace(-4, 4, sweep_points), the
+        middle measure replaced by the original) and latent_interpolations_{attr_str}_{i}.png (that sequence's piano roll with the
+        attribute's value of each of its measures beside it) under Trainer.get_save_dir(model).  dim: by default the attribute's
+        dimension of the interpretability metric (compute_eval_metrics).  All n * sweep_points + n codes are decoded in one batch,
+        the labels come from one compute_attribute_labels call, the events from one launch and the n figures from one launch and
+        one copy.  -> the paths written, per code in the order above"""
+        import os
+        from . import figures, midi
+        if sweep_points % 2 != 1:
+            raise AssertionError('sweep_points must be odd')
+        if attr_str not in self.attr_dict:
+            raise ValueError('Invalid regularization attribute')
+        dev = next(self.model.parameters()).device
+        codes = torch.as_tensor(latent_codes, dtype=torch.float32, device=dev)
+        n = min(int(num_points), codes.shape[0])
+        if n <= 0:
+            return []
+        if dim is None:
+            metrics = self.metrics if 'interpretability' in self.metrics else self.compute_eval_metrics()
+            if 'interpretability' not in metrics:
+                raise RuntimeError('the figures sweep the dimension of the interpretability metric, which this evaluation split was '
+                                   'too small to compute: give dim')
+            dim = metrics['interpretability'][attr_str][0]
+        p, codes = int(sweep_points), codes[:n]
+        z = codes[:, None, :].repeat(1, p, 1)
+        z[:, :, int(dim)] = torch.linspace(-4.0, 4.0, p, device=dev)
+        tokens = self.decode_latent_codes(torch.cat([z.reshape(n * p, -1), codes]))[1].squeeze(1)
+        t = tokens.shape[1]
+        sweeps, originals = tokens[:n * p].reshape(n, p, t).clone(), tokens[n * p:]
+        sweeps[:, p // 2] = originals
+        labels = self.compute_attribute_labels(sweeps.reshape(n * p, t), [attr_str]).reshape(n, p)
+        tables, slur = self._note_tables(dev)
+        events = ops.measure_notes(torch.cat([sweeps.reshape(n * p, t), originals]), tables, slur=slur).cpu().numpy()
+        frames = ops.render_pianoroll(sweeps, tables, labels.contiguous(), slur=slur, **self._look(look)).cpu().numpy()
+        folder = Trainer.get_save_dir(self.model)
+        paths = []
+        for i in range(n):
+            paths.append(midi.write_midi(os.path.join(folder, f'original_{i}.mid'), events[n * p + i:n * p + i + 1]))
+            stem = os.path.join(folder, f'latent_interpolations_{attr_str}_{i}')
+            paths.append(midi.write_midi(stem + '.mid', events[i * p:(i + 1) * p]))
+            paths.append(figures.write_png(frames[i], stem + '.png'))
+        return paths
 
     def loss_and_acc_test(self, data_loader):
         """mean RECONSTRUCTION loss (no KL / regulariser terms) and mean top-1 accuracy over the loader's batches

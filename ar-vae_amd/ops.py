@@ -1672,6 +1672,97 @@ def render_frames(src, cells, nrow=8, padding=2, pad_value=1.0, logits=True, rou
     return out.view(frames, hg, wg, channels)
 
 
+def _note_tables(tables, slur, device):
+    """(midi int32[V], is_note uint8[V], V) of build_measure_tables' result, with the slur index checked"""
+    midi, is_note = tables[0], tables[1]
+    v = midi.numel()
+    if midi.dtype != torch.int32 or is_note.dtype != torch.uint8 or is_note.numel() != v or v == 0:
+        raise TypeError('tables are (midi int32[V], is_note uint8[V], ...) as build_measure_tables returns them')
+    if midi.device != device or is_note.device != device:
+        raise ValueError(f'tables must live on {device}, where the measures are')
+    if not 0 <= int(slur) < v:
+        raise ValueError(f'slur index {slur} outside the vocabulary [0, {v})')
+    return midi.contiguous(), is_note.contiguous(), v
+
+
+def measure_notes(score, tables, *, slur, out=None):
+    """(M, T) or (M, 1, T) int64 measures, T % 6 == 0 -> (M, T, 3) int32 note events per tick (arvae_measure_notes): the MIDI pitch
+    sounding during the tick (0 = silence), the tick at which that element began (-1 inside leading slurs), and on a tick that
+    begins an element its duration in twelfths of a quarter note (0 elsewhere).  tables: build_measure_tables' result; slur: the
+    index of '__' in the vocabulary (required: the tables do not identify it, and it differs from dataset to dataset).  out: a contiguous int32 tensor of the result's size to write into."""
+    if not torch.is_tensor(score) or score.dtype != torch.int64:
+        raise TypeError('measure_notes needs an int64 tensor of vocabulary indices')
+    if score.dim() == 3 and score.shape[1] == 1:
+        score = score[:, 0]
+    if score.dim() != 2 or score.numel() == 0 or score.shape[1] % 6:
+        raise ValueError(f'measure_notes needs (M, T) measures with T a multiple of 6, got {tuple(score.shape)}')
+    _dev(score)
+    midi, is_note, v = _note_tables(tables, slur, score.device)
+    score = score.contiguous()
+    m, t = score.shape
+    if out is None:
+        out = torch.empty((m, t, 3), device=score.device, dtype=torch.int32)
+    else:
+        if out.dtype != torch.int32 or out.numel() != m * t * 3 or out.device != score.device or not out.is_contiguous():
+            raise ValueError(f'measure_notes: out must hold {m} x {t} x 3 int32 on {score.device}')
+    _lib.check(_lib.load().arvae_measure_notes(_ptr(score), m, t, _ptr(midi), _ptr(is_note), v, int(slur), _ptr(out), _stream()),
+               'measure_notes')
+    return out.view(m, t, 3)
+
+
+def pianoroll_geometry(k, t, with_panel=False, pitch_lo=55, pitch_hi=84, px_per_twelfth=2, px_per_pitch=4, panel_cell=12, gap=8):
+    """(H, W) of a piano-roll figure of k measures of t ticks (arvae_render_pianoroll)"""
+    w = k * (t // 6) * 12 * px_per_twelfth
+    return (pitch_hi - pitch_lo + 1) * px_per_pitch, w + (gap + k * panel_cell if with_panel else 0)
+
+
+def render_pianoroll(score, tables, values=None, vmin=None, vmax=None, pitch_lo=55, pitch_hi=84, px_per_twelfth=2, px_per_pitch=4,
+                     mark=None, panel_cell=12, gap=8, dot_radius=3, *, slur, out=None):
+    """Piano-roll figures as bytes, one launch for all of them (arvae_render_pianoroll).
+    score (F, K, T) int64 on the device: F figures of K measures each -> (F, H, W, 3) uint8, what PIL.Image.fromarray takes.
+    H = (pitch_hi - pitch_lo + 1) px_per_pitch with row 0 at pitch_hi (55..84 is the reference's folk range, 55..90 its bach range);
+    the roll is K (T / 6) 12 px_per_twelfth pixels wide.  values (F, K) fp32 on the device: a panel beside the roll with one dot per
+    measure at the height of its value between vmin and vmax (default: the finite minimum and maximum of values; a non-finite
+    value draws no dot).  mark: the pixel columns of an onset mark, by default 5 % of a beat, at least 1.  tables / slur as
+    measure_notes.  out: a contiguous uint8 tensor of the result's size to write into."""
+    if not torch.is_tensor(score) or score.dtype != torch.int64:
+        raise TypeError('render_pianoroll needs an int64 tensor of vocabulary indices')
+    if score.dim() != 3 or score.numel() == 0:
+        raise ValueError(f'render_pianoroll needs (F, K, T) measures, got {tuple(score.shape)}')
+    _dev(score)
+    midi, is_note, v = _note_tables(tables, slur, score.device)
+    score = score.contiguous()
+    f, k, t = score.shape
+    look = [int(x) for x in (pitch_lo, pitch_hi, px_per_twelfth, px_per_pitch)]
+    if mark is None:
+        mark = max(1, 12 * look[2] // 20)
+    lo, hi = 0.0, 0.0
+    if values is not None:
+        if not torch.is_tensor(values) or values.dtype != torch.float32 or tuple(values.shape) != (f, k) or values.device != score.device:
+            raise ValueError(f'render_pianoroll: values must be fp32 ({f}, {k}) on {score.device}')
+        values = values.contiguous()
+        if vmin is None or vmax is None:
+            finite = values[torch.isfinite(values)]
+            bounds = (float(finite.min()), float(finite.max())) if finite.numel() else (0.0, 0.0)
+            lo, hi = (bounds[0] if vmin is None else float(vmin)), (bounds[1] if vmax is None else float(vmax))
+        else:
+            lo, hi = float(vmin), float(vmax)
+    lib = _lib.load()
+    if lib.arvae_render_pianoroll_bytes(k, t, *look, int(values is not None), int(panel_cell), int(gap)) < 0:
+        _lib.check(-1, 'render_pianoroll_bytes')
+    h, w = pianoroll_geometry(k, t, values is not None, *look, int(panel_cell), int(gap))
+    if out is None:
+        out = torch.empty((f, h, w, 3), device=score.device, dtype=torch.uint8)
+    else:
+        _dev(out)
+        if out.dtype != torch.uint8 or out.numel() != f * h * w * 3 or out.device != score.device or not out.is_contiguous():
+            raise ValueError(f'render_pianoroll: out must hold {f} x {h} x {w} x 3 contiguous bytes on {score.device}')
+    _lib.check(lib.arvae_render_pianoroll(_ptr(score), f, k, t, _ptr(midi), _ptr(is_note), v, int(slur),
+                                          None if values is None else _ptr(values), lo, hi, *look, int(mark), int(panel_cell), int(gap),
+                                          int(dot_radius), _ptr(out), _stream()), 'render_pianoroll')
+    return out.view(f, h, w, 3)
+
+
 def measure_attributes(score, tables, rhythm_weights, rhythm_norm):
     """(B, 24) int64 measures -> (B, 4) [rhythmic complexity, pitch range, note density, contour]."""
     _dev(score)

@@ -599,6 +599,39 @@ int arvae_render_frames(const float *src, int64_t n_images, int h, int w, const 
                         int cells_per_frame, int nrow, int padding, float pad_value, int flags, uint8_t *out,
                         arvae_stream_t stream);
 
+/* Decoded measures as note events and as piano-roll figures (added under ABI 16: symbols only; csrc/pianoroll.hip).  Integer
+ * restatement of tensor_to_m21score / concatenate_scores (data/dataloaders/bar_dataset.py:224-268) and of the shaded roll of
+ * plot_pianoroll_from_midi (utils/plotting.py:307-362).  Time is counted in twelfths of a quarter note: tick t of a measure lies in
+ * beat t / 6 at sub-position s = t % 6, starts at twelfth 12 (t / 6) + {0, 3, 4, 6, 8, 9}[s] and lasts {3, 1, 2, 2, 1, 3}[s]; a measure
+ * of T ticks (T % 6 == 0) has 2 T twelfths.  An element begins at every tick whose token is not `slur` and lasts to the next such
+ * tick or the measure's end; leading slurs are silence, nothing ties across measures, an element sounds only where is_note marks
+ * its token, and a token outside [0, V) is silence and indexes no table.
+ *
+ * arvae_measure_notes: score [M, T] int64 -> out [M, T, 3] int32, per tick
+ *   pitch   the MIDI number sounding during the tick, 0 = silence
+ *   start   the tick at which that element began, -1 inside leading slurs
+ *   length  on a tick that begins an element its duration in twelfths, 0 elsewhere
+ *
+ * arvae_render_pianoroll: score [F, K, T] -> out [F, H, W, 3] uint8 (any alignment), F figures of K measures in one launch.
+ *   H = (pitch_hi - pitch_lo + 1) px_per_pitch, row 0 at pitch_hi; the roll is K (T / 6) 12 px_per_twelfth pixels wide; with
+ *   `values` (fp32 [F, K], may be null) a white gap of `gap` pixels and a panel of K panel_cell pixels follow it.
+ *   Roll pixel: shade v from the first layer that applies -- 127 on the first `mark` pixel columns of a sounding element (no
+ *   further than the element reaches) on the rows of pitch - 1 .. pitch + 1; 90 on the element's extent on the rows of its pitch;
+ *   100 on a measure's first column; 50 on a beat's first column; 30 on the rows of even pitches; else 0 -- and
+ *   channel = 255 - (v (255 - dark) + 63) / 127 with dark = (8, 48, 107).  Rows outside [pitch_lo, pitch_hi] do not exist.
+ *   Panel: measure k gets a black disc dx^2 + dy^2 <= dot_radius^2 (inside its own cell of panel_cell columns) around column
+ *   k panel_cell + panel_cell / 2 and row H - 1 - (int)floorf(c (H - 1) + 0.5f), c = (value - vmin) / (vmax - vmin) clamped to
+ *   [0, 1] (0.5 when vmax == vmin), each operation rounded to fp32 by itself; a non-finite value draws no disc.
+ * arvae_render_pianoroll_bytes: H * W * 3, or -1 (bad argument, or 2^31 bytes and more: such a figure cannot be rendered). */
+int arvae_measure_notes(const int64_t *score, int64_t M, int32_t T, const int32_t *midi_lut, const uint8_t *is_note, int32_t V,
+                        int32_t slur, int32_t *out, arvae_stream_t stream);
+int64_t arvae_render_pianoroll_bytes(int32_t K, int32_t T, int32_t pitch_lo, int32_t pitch_hi, int32_t px_per_twelfth,
+                                     int32_t px_per_pitch, int32_t with_panel, int32_t panel_cell, int32_t gap);
+int arvae_render_pianoroll(const int64_t *score, int32_t F, int32_t K, int32_t T, const int32_t *midi_lut, const uint8_t *is_note,
+                           int32_t V, int32_t slur, const float *values, float vmin, float vmax, int32_t pitch_lo,
+                           int32_t pitch_hi, int32_t px_per_twelfth, int32_t px_per_pitch, int32_t mark, int32_t panel_cell,
+                           int32_t gap, int32_t dot_radius, uint8_t *out, arvae_stream_t stream);
+
 /* Attribute labels of a batch of measures.  Replaces MeasureVAETrainer.compute_attribute_labels
  * (measurevae/measure_vae_trainer.py:167-186 -> data/dataloaders/bar_dataset.py:338-500):
  *   out[b] = [rhythmic complexity, pitch range/26, note density, contour/26]

@@ -5,7 +5,10 @@ building it from ABC files with music21, and the `bach` chorales, are offline st
 reference's disentanglement metrics (arvae_amd.evaluation) to the evaluation summary; `--sample N [--temperature T] [--top_k K]
 [--top_p P] [--playable]` adds N measures drawn from the model (z from the prior, every note from softmax(probs / T) over the notes a
 top-k cut, a nucleus cut and the playable-note mask leave) as lists of note names; `--infill N --keep_ticks SPEC [--keep_rhythm]`
-rewrites N measures of the evaluation split around the ticks SPEC keeps (MeasureVAETrainer.infill_measures)."""
+rewrites N measures of the evaluation split around the ticks SPEC keeps (MeasureVAETrainer.infill_measures); `--write_midi DIR` writes
+what these two decode into DIR as MIDI files and piano-roll PNGs, `--from_midi FILE` lets `--infill` rewrite the measures of a MIDI
+file, and `--plots` writes the reference's latent-interpolation MIDI files and piano rolls of every attribute
+(MeasureVAETrainer.plot_latent_interpolations) into models/<repr>/results/."""
 import json
 import os
 import sys
@@ -88,6 +91,16 @@ ALTERNATIVES_HELP = (f'{BEAM_FLAG} W {BEAM_GROUPS_FLAG} G {DIVERSITY_FLAG} L (bo
                      'measures as note names, group by group and best first within a group, and their `log_probs`; `samples` / '
                      '`infilled` hold the first of them.  G and L are echoed as `beam_groups` and `diversity`.')
 beam_groups, diversity = None, None
+# listening and looking: MIDI files and piano-roll PNGs of what the model decodes (arvae_amd.midi, ops.render_pianoroll)
+PLOTS_FLAG, WRITE_MIDI_FLAG, FROM_MIDI_FLAG = '--plots', '--write_midi', '--from_midi'
+FILES_HELP = (f'{PLOTS_FLAG}: for every attribute and the first 20 evaluation codes write original_{{i}}.mid, '
+              'latent_interpolations_{attr}_{i}.mid and the piano roll latent_interpolations_{attr}_{i}.png into models/<repr>/results/ '
+              f'(listed as `plots` in the summary).  {WRITE_MIDI_FLAG} DIR: write what {SAMPLE_FLAG} and {INFILL_FLAG} decode into DIR, one '
+              '.mid and one .png each: the samples, the original and the rewritten measures, and the beam alternatives with their '
+              f'log_probs beside the roll (listed as `written`).  {FROM_MIDI_FLAG} FILE: {INFILL_FLAG} N rewrites the first N measures of '
+              'a monophonic MIDI file on the 24-tick grid instead of the evaluation split; the file has as many measures of 4/4 as its '
+              'track is long, silent ones included.')
+with_plots, midi_dir, from_midi = False, None, None
 TICKS = 24
 
 
@@ -114,7 +127,7 @@ def parse_keep_ticks(spec):
 def with_options(fn):
     for names, kwargs in reversed(MEASURE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP + '  ' + INFILL_HELP + '  ' + ALTERNATIVES_HELP)(fn)
+    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP + '  ' + INFILL_HELP + '  ' + ALTERNATIVES_HELP + '  ' + FILES_HELP)(fn)
 
 
 @with_options
@@ -183,8 +196,10 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'attribute_means': [float(v) for v in attrs.mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
+        metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or with_plots else {}      # (once: --plots sweeps what --metrics prints)
         if with_metrics:
-            summary.update(eval_metrics_or_warn(codes, attrs, names))
+            summary.update(metrics)
+        written = []
         if num_samples > 0:
             trainer.cuda()
             model.eval()
@@ -203,13 +218,23 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
             elif top_k is not None or top_p is not None or playable:        # the cuts are echoed beside the measures they shaped
                 summary['sampling'] = {'temperature': temperature, 'top_k': top_k, 'top_p': top_p, 'playable': playable}
             summary['samples'] = [[dataset.index2note_dicts[int(i)] for i in row] for row in notes.squeeze(1).tolist()]
+            if midi_dir is not None:
+                for i in range(num_samples):
+                    written += trainer.write_measures(notes[i], os.path.join(midi_dir, f'sample_{i}'))
+                    if beam_groups is not None:
+                        written += trainer.write_measures(seqs[i], os.path.join(midi_dir, f'sample_{i}_alternatives'), values=log_probs[i])
         if num_infill > 0:
             trainer.cuda()
             model.eval()
-            score = next(iter(eval_loader))[0]
-            score = score.view(-1, score.shape[-1])[:num_infill]
-            if score.shape[0] < num_infill:
-                raise SystemExit(f'{INFILL_FLAG} {num_infill}: an evaluation batch holds {score.shape[0]} measures')
+            if from_midi is not None:
+                score = measures_of_midi(from_midi, dataset.note2index_dicts)[:num_infill]
+                if score.shape[0] < num_infill:
+                    raise SystemExit(f'{INFILL_FLAG} {num_infill}: {from_midi} holds {score.shape[0]} measures')
+            else:
+                score = next(iter(eval_loader))[0]
+                score = score.view(-1, score.shape[-1])[:num_infill]
+                if score.shape[0] < num_infill:
+                    raise SystemExit(f'{INFILL_FLAG} {num_infill}: an evaluation batch holds {score.shape[0]} measures')
             mode = 'beam' if beam is not None else ('multinomial' if drew_notes else 'argmax')
             keep = None if keep_ticks is None else torch.tensor(keep_ticks)
             if beam_groups is not None:
@@ -226,7 +251,34 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
                                  'infilled': [[names[int(i)] for i in row] for row in notes.squeeze(1).tolist()]}
             if beam_groups is not None:
                 summary['infill'].update(beam_groups=beam_groups, diversity=diversity, alternatives=_alternatives(names, seqs, log_probs))
+            if midi_dir is not None:
+                for i in range(num_infill):
+                    written += trainer.write_measures(score[i], os.path.join(midi_dir, f'infill_{i}_original'))
+                    written += trainer.write_measures(notes[i], os.path.join(midi_dir, f'infill_{i}_infilled'))
+                    if beam_groups is not None:
+                        written += trainer.write_measures(seqs[i], os.path.join(midi_dir, f'infill_{i}_alternatives'), values=log_probs[i])
+        if midi_dir is not None:
+            summary['written'] = written
+        if with_plots:
+            if 'interpretability' not in metrics:
+                print(f'{PLOTS_FLAG}: the figures sweep the dimensions of the interpretability metric, which this evaluation split '
+                      f'({codes.shape[0]} codes) was too small to compute; skipped')
+            else:
+                trainer.cuda()
+                model.eval()
+                trainer.metrics = dict(metrics)
+                summary['plots'] = []
+                for attr_str in trainer.attr_dict:           # the reference script's live loop (train_measure_vae.py:199-211)
+                    summary['plots'] += trainer.plot_latent_interpolations(codes, attr_str=attr_str, num_points=20)
         print(json.dumps(summary, indent=2))
+
+
+def measures_of_midi(path, note2index):
+    """the measures of a monophonic MIDI file on the 24-tick grid as canonical tokens, (measures, 24) int64 (arvae_amd.midi)"""
+    from arvae_amd import midi
+    division, notes, length = midi.read_midi(path, with_length=True)       # (the track's length: silent measures at the end count)
+    count = max(1, -(-max([length] + [on + dur for on, dur, _ in notes]) // (4 * division)))
+    return torch.tensor(midi.tokens_from_notes(notes, note2index, count, division=division), dtype=torch.int64)
 
 
 def _alternatives(names, seqs, log_probs):
@@ -254,13 +306,16 @@ def _take_value(argv, flag, cast, default):
 
 def run(argv=None):
     """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p,
-    --playable, --beam and --beam_groups / --diversity.  Values of --top_k / --top_p outside their ranges raise the decoder's
+    --playable, --beam, --beam_groups / --diversity, --infill, --plots, --write_midi and --from_midi.  Values of --top_k / --top_p outside their ranges raise the decoder's
     ValueError (sampling_filter); --beam takes a width in [1, 16] and is refused together with --top_k, --top_p or --temperature
     (beam search draws nothing); --beam_groups and --diversity come together and only with --beam."""
     global with_metrics, num_samples, temperature, top_k, top_p, playable, beam, num_infill, keep_ticks, keep_rhythm, drew_notes
-    global beam_groups, diversity
+    global beam_groups, diversity, with_plots, midi_dir, from_midi
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
+    with_plots = PLOTS_FLAG in argv
+    midi_dir, argv = _take_value(argv, WRITE_MIDI_FLAG, str, None)
+    from_midi, argv = _take_value(argv, FROM_MIDI_FLAG, str, None)
     playable = PLAYABLE_FLAG in argv
     num_samples, argv = _take_value(argv, SAMPLE_FLAG, int, 0)
     drew = any(a == TEMPERATURE_FLAG or a.startswith(TEMPERATURE_FLAG + '=') for a in argv)
@@ -296,10 +351,16 @@ def run(argv=None):
         raise ValueError(f'{INFILL_FLAG} keeps something of every measure: give {KEEP_TICKS_FLAG} SPEC or {KEEP_RHYTHM_FLAG}')
     if num_infill == 0 and (keep_ticks is not None or keep_rhythm):
         raise ValueError(f'{KEEP_TICKS_FLAG} and {KEEP_RHYTHM_FLAG} belong to {INFILL_FLAG} N')
+    if midi_dir is not None and num_infill == 0 and num_samples <= 0:
+        raise ValueError(f'{WRITE_MIDI_FLAG} writes what {SAMPLE_FLAG} N and {INFILL_FLAG} N decode: give one of them')
+    if from_midi is not None and num_infill == 0:
+        raise ValueError(f'{FROM_MIDI_FLAG} gives {INFILL_FLAG} N its measures: give {INFILL_FLAG}')
+    if from_midi is not None and not os.path.isfile(from_midi):
+        raise ValueError(f'{FROM_MIDI_FLAG}: no file {from_midi}')
     if num_samples < 0 or not temperature > 0:
         raise SystemExit(f'{SAMPLE_FLAG} takes a count >= 0 and {TEMPERATURE_FLAG} a positive number')
     check_sampling_cuts(top_k, top_p)          # the decoder's own ValueError, before anything is loaded or trained
-    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG, KEEP_RHYTHM_FLAG)])
+    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG, KEEP_RHYTHM_FLAG, PLOTS_FLAG)])
 
 
 if __name__ == '__main__':
