@@ -121,8 +121,15 @@ class ResnetWeights(ctypes.Structure):
                 [(n, c_vp * RESNET_CONVS) for n in ('conv_w', 'bn_w', 'bn_b', 'bn_mean', 'bn_var')] + [('fc_w', c_vp), ('fc_b', c_vp)])
 
 
+class ScatterMark(ctypes.Structure):
+    """arvae_scatter_mark_t"""
+    _fields_ = [('x', ctypes.c_int16), ('y', ctypes.c_int16), ('glyph', ctypes.c_uint8), ('rot', ctypes.c_uint8), ('figure', ctypes.c_int16)]
+
+
+SCATTER_MAX_FIGURES, SCATTER_MAX_MARKS = 16, 384
+
 _P = ctypes.POINTER
-# name -> (restype, argtypes); must list every symbol declared in include/arvae_hip.h
+# name ->(restype, argtypes); must list every symbol declared in include/arvae_hip.h
 SIGNATURES = {
     'arvae_abi_version': (c_i32, []),
     'arvae_last_error_string': (ctypes.c_char_p, []),
@@ -211,6 +218,8 @@ SIGNATURES = {
     'arvae_measure_notes': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     'arvae_render_pianoroll_bytes': (c_i64, [c_i32] * 9),
     'arvae_render_pianoroll': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_f32, c_f32] + [c_i32] * 8 + [c_vp, c_vp]),
+    'arvae_render_scatter_bytes': (c_i64, [c_i32, c_i32, c_i32, _P(c_i32)]),
+    'arvae_render_scatter': (c_i32, [c_vp, c_vp, c_i32, c_i64, _P(c_f32), c_i32, c_i32, c_i32, c_i32, _P(ScatterMark), c_i32, c_vp, c_vp]),
     'arvae_measure_attributes': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp]),
     'arvae_image_vae_ws_floats': (c_i64, [_P(ImageVaeDesc), c_i32, c_i64]),
     'arvae_image_vae_forward': (c_i32, [_P(ImageVaeDesc), c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, _P(c_vp), c_vp, c_vp,

@@ -2,6 +2,8 @@
 
 The reference goes through torchvision's save_image and utils/plotting.py:377-383 (save_gif_from_list); here the grid and the
 cast to bytes are already done by the render launch, so a figure costs one device-to-host copy of its uint8 frames.
+The piano rolls (ops.render_pianoroll) and the scatter figures of the latent plane (ops.render_scatter; write_data_dist is both
+trainers' plot_data_dist) are written the same way.
 """
 import numpy as np
 import torch
@@ -32,6 +34,35 @@ def write_png(frame_u8, path):
         a = a[0]
     _image(a).save(path)
     return path
+
+
+def write_data_dist(trainer, latent_codes, attributes, names, columns, dim1, dim2, look):
+    """data_dist_{name}.png for every name (both trainers' plot_data_dist; the reference's plot_dim with xlim = ylim = 4,
+    utils/plotting.py:41-63): figure i shows the codes in the plane (dim1[i], dim2[i]) coloured by column columns[i] of
+    `attributes`.  dim1 / dim2: one dimension for all figures or one each.  All figures of a call (16 at most a launch) are
+    rendered by one ops.render_scatter launch and reach the host in one copy.  -> the paths written"""
+    import os
+    from . import ops
+    from .trainer import Trainer
+    codes = np.asarray(latent_codes.detach().cpu() if torch.is_tensor(latent_codes) else latent_codes, dtype=np.float32)
+    attrs = np.asarray(attributes.detach().cpu() if torch.is_tensor(attributes) else attributes, dtype=np.float32)
+    if codes.ndim != 2 or attrs.ndim != 2 or codes.shape[0] != attrs.shape[0]:
+        raise ValueError(f'plot_data_dist takes codes (n, z_dim) and attributes (n, k), got {codes.shape} and {attrs.shape}')
+    f = len(names)
+    dims = [[int(d)] * f if np.ndim(d) == 0 else [int(x) for x in d] for d in (dim1, dim2)]
+    if len(dims[0]) != f or len(dims[1]) != f:
+        raise ValueError(f'plot_data_dist: dim1 and dim2 are one dimension or {f} of them')
+    dev = next(trainer.model.parameters()).device
+    folder = Trainer.get_save_dir(trainer.model)
+    paths = []
+    for at in range(0, f, 16):
+        part = range(at, min(at + 16, f))
+        points = torch.from_numpy(np.stack([codes[:, [dims[0][i], dims[1][i]]] for i in part])).to(dev)
+        values = torch.from_numpy(np.stack([attrs[:, columns[i]] for i in part])).to(dev)
+        labels = [(f'dimension: {dims[0][i]}', f'dimension: {dims[1][i]}') for i in part]
+        frames = ops.render_scatter(points.contiguous(), values.contiguous(), (-4.0, 4.0), (-4.0, 4.0), **{'labels': labels, **look}).cpu().numpy()
+        paths += [write_png(frames[k], os.path.join(folder, f'data_dist_{names[i]}.png')) for k, i in enumerate(part)]
+    return paths
 
 
 def write_gif(frames_u8, path, delay=100):

@@ -331,6 +331,29 @@ class ImageVAETrainer(Trainer):
             paths.append(figures.write_png(frame, os.path.join(self._save_dir(), f'{name}.png')))
         return paths
 
+    def plot_data_dist(self, latent_codes, attributes, attr_str, dim1=0, dim2=1, **look):
+        """data_dist_{attr_str}.png under Trainer.get_save_dir(model) (image_vae_trainer.py:370-379): the codes in the plane
+        (dim1, dim2), limits -4..4, coloured by the attribute, as a scatter figure rendered on the device (ops.render_scatter).
+        attributes: compute_representations' columns (the attributes without digit_identity / color, in attr_dict's order) or all
+        of the dataset's label columns (indexed by attr_dict).  attr_str may be a list of names, dim1 and dim2 then one dimension
+        for all or one a name: all figures come from one launch and one copy.  look: render_scatter's keywords.
+        -> the path written (a list of paths for a list of names)"""
+        from . import figures
+        names = [attr_str] if isinstance(attr_str, str) else list(attr_str)
+        relevant = [a for a in self.attr_dict if a not in ('digit_identity', 'color')]
+        width = np.shape(attributes)[1]
+        if width == len(relevant) and width != len(self.attr_dict):
+            column = {a: i for i, a in enumerate(relevant)}
+        elif width > max(self.attr_dict.values()):
+            column = dict(self.attr_dict)
+        else:
+            raise ValueError(f'attributes holds {width} columns: neither the {len(relevant)} of compute_representations nor the labels')
+        for name in names:
+            if name not in column:
+                raise ValueError('Invalid regularization attribute')
+        paths = figures.write_data_dist(self, latent_codes, attributes, names, [column[a] for a in names], dim1, dim2, look)
+        return paths[0] if isinstance(attr_str, str) else paths
+
     def save_representations(self, path, data_loader=None, batch_size=128):
         """Write the record the reference's compute_eval_metrics consumes (image_vae_trainer.py:289-317): latent codes,
         attribute columns and attribute names as JSON, from the encoder-only pass.  compute_eval_metrics computes the

@@ -524,6 +524,82 @@ class MeasureVAETrainer(Trainer):
             paths.append(figures.write_png(frames[i], stem + '.png'))
         return paths
 
+    # -- the latent plane: where the data lies in it and what the decoder makes of it (measure_vae_trainer.py:245-254, 310-352,
+    #    utils/plotting.py:41-63): scatter figures rendered on the device (ops.render_scatter), written by arvae_amd.figures ----------
+    def plot_data_dist(self, latent_codes, attributes, attr_str, dim1=0, dim2=1, **look):
+        """data_dist_{attr_str}.png under Trainer.get_save_dir(model): the codes in the plane (dim1, dim2), limits -4..4, coloured by
+        the attribute's column of `attributes` (compute_representations' arrays).  attr_str may be a list of names, dim1 and dim2
+        then one dimension for all or one a name: all figures come from one launch and one copy.  look: render_scatter's keywords.
+        -> the path written (a list of paths for a list of names)"""
+        from . import figures
+        names = [attr_str] if isinstance(attr_str, str) else list(attr_str)
+        for name in names:
+            if name not in self.attr_dict:
+                raise ValueError('Invalid regularization attribute')
+        paths = figures.write_data_dist(self, latent_codes, attributes, names, [self.attr_dict[a] for a in names], dim1, dim2, look)
+        return paths[0] if isinstance(attr_str, str) else paths
+
+    def compute_latent_surface(self, dim1=0, dim2=1, grid_res=0.05, base_code=None, attr_list=None, chunk=4096):
+        """The attributes of what the decoder makes of the plane (dim1, dim2): x = torch.arange(-5., 5., grid_res), n = len(x), code
+        (i, j) of the grid holds x[i] in dimension dim1 and x[j] in dim2 (the reference's meshgrid) and base_code (z_dim,) elsewhere
+        -- by default one standard-normal draw from the library's generator.  The n * n codes are decoded `chunk` at a time
+        (decode_latent_codes, argmax) and labelled by compute_attribute_labels; every one of them is kept.
+        -> (grid (n, n, 2), labels (n, n, A)) on the device, A = len(attr_list), by default all attributes"""
+        dev = next(self.model.parameters()).device
+        names = list(self.attr_dict) if attr_list is None else list(attr_list)
+        if int(chunk) < 1:
+            raise ValueError(f'chunk {chunk} must be positive')
+        x = torch.arange(-5., 5., grid_res)
+        z1, z2 = torch.meshgrid([x, x], indexing='ij')
+        n = x.numel()
+        if base_code is None:
+            base = ops.normal_noise((1, self.model.latent_space_dim), dev)
+        else:
+            base = torch.as_tensor(base_code, dtype=torch.float32).reshape(1, -1).to(dev)
+            if base.shape[1] != self.model.latent_space_dim:
+                raise ValueError(f'base_code holds {base.shape[1]} numbers, a code {self.model.latent_space_dim}')
+        grid = torch.stack([z1, z2], dim=2).to(dev)
+        z = base.repeat(n * n, 1)
+        z[:, int(dim1)], z[:, int(dim2)] = grid[:, :, 0].reshape(-1), grid[:, :, 1].reshape(-1)
+        labels = []
+        for at in range(0, n * n, int(chunk)):
+            tokens = self.decode_latent_codes(z[at:at + int(chunk)])[1]
+            labels.append(self.compute_attribute_labels(tokens.reshape(tokens.shape[0], -1), names))
+        return grid, torch.cat(labels).reshape(n, n, len(names))
+
+    def plot_latent_surface(self, attr_str, dim1=0, dim2=1, grid_res=0.05, base_code=None, **look):
+        """latent_surface_{attr_str}.png under Trainer.get_save_dir(model): the grid of compute_latent_surface in the plane
+        (dim1, dim2), limits -5..5, every code coloured by the attribute of the measure it decodes to.  attr_str may be a list of
+        names: the grid is decoded once and all figures come from one launch and one copy; dim1 / dim2 may then hold one
+        dimension a name, and every distinct plane is decoded once, around the same base code.  look: render_scatter's keywords.
+        -> the path written (a list of paths for a list of names)"""
+        import os
+        from . import figures
+        names = [attr_str] if isinstance(attr_str, str) else list(attr_str)
+        for name in names:
+            if name not in self.attr_dict:
+                raise ValueError('Invalid regularization attribute')
+        f = len(names)
+        dims = [[int(d)] * f if np.ndim(d) == 0 else [int(x) for x in d] for d in (dim1, dim2)]
+        if len(dims[0]) != f or len(dims[1]) != f:
+            raise ValueError(f'plot_latent_surface: dim1 and dim2 are one dimension or {f} of them')
+        if base_code is None:                                  # one draw for all planes
+            base_code = ops.normal_noise((self.model.latent_space_dim,), next(self.model.parameters()).device)
+        planes = sorted(set(zip(*dims)))                       # names that share a plane share its decode pass
+        values = [None] * f
+        for plane in planes:
+            members = [i for i in range(f) if (dims[0][i], dims[1][i]) == plane]
+            grid, labels = self.compute_latent_surface(plane[0], plane[1], grid_res, base_code, [names[i] for i in members])
+            for k, i in enumerate(members):
+                values[i] = labels[:, :, k].reshape(-1)
+        n = grid.shape[0] * grid.shape[1]
+        points = grid.reshape(1, n, 2).expand(f, n, 2).contiguous()          # (the grid is the same in every plane)
+        look = {'labels': [(f'dimension: {a}', f'dimension: {b}') for a, b in zip(*dims)], **look}
+        frames = ops.render_scatter(points, torch.stack(values).contiguous(), (-5.0, 5.0), (-5.0, 5.0), **look).cpu().numpy()
+        folder = Trainer.get_save_dir(self.model)
+        paths = [figures.write_png(frames[i], os.path.join(folder, f'latent_surface_{name}.png')) for i, name in enumerate(names)]
+        return paths[0] if isinstance(attr_str, str) else paths
+
     def loss_and_acc_test(self, data_loader):
         """mean RECONSTRUCTION loss (no KL / regulariser terms) and mean top-1 accuracy over the loader's batches
         (measure_vae_trainer.py:367-397); accumulated on the device, one host sync at the end."""

@@ -8,7 +8,7 @@ Activation tensors are channels-last ([N, H, W, C]; [B, F] for dense layers).
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch.autograd import Function
@@ -1930,3 +1930,167 @@ def resnet18_forward(prep, x):
         _lib.check(lib.arvae_resnet18_forward(_ptr(prep), _ptr(x), n, _ptr(logits), _ptr(probs), _ptr(pred), _ptr(ws), _stream()),
                    'resnet18_forward')
     return logits, probs, pred
+
+
+# ------------------------------------------------------------------------------------------------
+# scatter figures of the latent plane (csrc/scatter.hip); at the end of the file because tests/workspace_cases.py names an
+# allocation above by its line number
+# ------------------------------------------------------------------------------------------------
+SCATTER_FONT = '0123456789-.: dimenso'                 # the glyphs of csrc/scatter.hip's font, a glyph's number its place here
+SCATTER_TICK_X, SCATTER_TICK_Y = 21, 22                # the two tick marks (ARVAE_SCATTER_TICK_X / _Y)
+SCATTER_LABEL_CHARS = 6                                # a tick's label of more characters is left out: the margins hold six
+ScatterGeometry = NamedTuple('ScatterGeometry', [(k, int) for k in ('plot_x', 'plot_y', 'plot_w', 'plot_h', 'bar_x', 'bar_w')])
+
+
+def scatter_geometry(width=485, height=360, radius=2):
+    """Where arvae_render_scatter puts things on a canvas of width x height: the plot area's first pixel (plot_x, plot_y) and its
+    extent plot_w x plot_h, and the colour bar's first column bar_x and width bar_w (its rows are the plot area's).  Each of the
+    two has a frame one pixel wide around it.  Raises for a canvas too small for the margins."""
+    g = (ctypes.c_int32 * 6)()
+    if _lib.load().arvae_render_scatter_bytes(int(width), int(height), int(radius), g) < 0:
+        _lib.check(-1, 'render_scatter_bytes')
+    return ScatterGeometry(*g)
+
+
+def scatter_ticks(lo, hi, most=6):
+    """[(value, label)] of an axis from lo to hi: the multiples of the smallest step among 1, 2, 5 x 10^k that leaves at most
+    most + 1 of them, written with as many decimals as the step has; lo == hi gives that one value with two decimals"""
+    import math
+    lo, hi = float(lo), float(hi)
+    if lo == hi:
+        return [(lo, f'{lo:.2f}')]
+    raw = (hi - lo) / most
+    k = math.floor(math.log10(raw))
+    for m in (1, 2, 5, 10):
+        step = m * 10.0 ** k
+        if step >= raw:
+            break
+    decimals = max(0, -(k + (1 if m == 10 else 0)))
+    ticks = []
+    for i in range(math.ceil(lo / step - 1e-9), math.floor(hi / step + 1e-9) + 1):
+        label = f'{i * step:.{decimals}f}'
+        ticks.append((i * step, label.lstrip('-') if float(label) == 0 else label))
+    return ticks
+
+
+def _scatter_tick_pixel(t, lo, hi, extent):
+    """the pixel 0..extent - 1 of an axis of `extent` pixels at which the value t lies (the middle one when lo == hi)"""
+    import math
+    if lo == hi:
+        return (extent - 1) // 2
+    return min(extent - 1, max(0, int(math.floor((t - lo) / (hi - lo) * (extent - 1) + 0.5))))
+
+
+def scatter_marks(geometry, xlim, ylim, vlim, labels):
+    """The marks of one figure, a set of (x, y, glyph, rot) as arvae_scatter_mark_t holds them: tick marks and their labels on both
+    axes and on the colour bar (whose values run from vlim[0] at the bottom to vlim[1] at the top), the x-axis title labels[0]
+    centred below the plot and the y-axis title labels[1] turned a quarter to the left beside it.  Blanks take no mark."""
+    g = geometry
+    marks = set()
+
+    def text(s, x, y, rot=0):
+        for i, ch in enumerate(s):
+            if ch not in SCATTER_FONT:
+                raise ValueError(f'render_scatter: {ch!r} of {s!r} is not in the font {SCATTER_FONT!r}')
+            if ch != ' ':
+                marks.add((x, y - 6 * i - 4, SCATTER_FONT.index(ch), 1) if rot else (x + 6 * i, y, SCATTER_FONT.index(ch), 0))
+
+    for t, label in scatter_ticks(*xlim):
+        cx = g.plot_x + _scatter_tick_pixel(t, xlim[0], xlim[1], g.plot_w)
+        marks.add((cx, g.plot_y + g.plot_h + 1, SCATTER_TICK_X, 0))
+        if len(label) <= SCATTER_LABEL_CHARS:
+            text(label, cx - (6 * len(label) - 1) // 2, g.plot_y + g.plot_h + 7)
+    for lim, tick_x, right in ((ylim, g.plot_x - 5, False), (vlim, g.bar_x + g.bar_w + 1, True)):
+        for t, label in scatter_ticks(*lim):
+            cy = g.plot_y + g.plot_h - 1 - _scatter_tick_pixel(t, lim[0], lim[1], g.plot_h)
+            marks.add((tick_x, cy, SCATTER_TICK_Y, 0))
+            if len(label) <= SCATTER_LABEL_CHARS:
+                text(label, tick_x + 6 if right else tick_x - 2 - (6 * len(label) - 1), cy - 3)
+    text(labels[0], g.plot_x + g.plot_w // 2 - (6 * len(labels[0]) - 1) // 2, g.plot_y + g.plot_h + 18)
+    text(labels[1], 3, g.plot_y + g.plot_h // 2 + (6 * len(labels[1]) - 1) // 2, rot=1)
+    return marks
+
+
+def _per_figure(what, given, f, width):
+    """`given` as an (f, width) float32 array: one row for all figures, or one a figure"""
+    import numpy as np
+    a = np.asarray(given.detach().cpu() if torch.is_tensor(given) else given, dtype=np.float32)
+    if width == 1 and a.shape == (f,):
+        a = a.reshape(f, 1)
+    elif a.shape == (width,) or (width == 1 and a.shape == ()):
+        a = np.broadcast_to(a.reshape(1, width), (f, width))
+    if a.shape != (f, width):
+        raise ValueError(f'render_scatter: {what} is one {"value" if width == 1 else "(lo, hi) pair"} or {f} of them, got shape {a.shape}')
+    return np.ascontiguousarray(a)
+
+
+def render_scatter(points, values, xlim, ylim, vmin=None, vmax=None, *, width=485, height=360, radius=2, alpha=0.5,
+                   labels=('dimension: 0', 'dimension: 1'), out=None):
+    """Scatter figures as bytes, one launch for all of them (arvae_render_scatter): the matplotlib scatter of the reference's
+    plot_dim (utils/plotting.py:41-63) in this library's own look.
+    points (F, N, 2) and values (F, N) fp32 on the device: F figures (at most 16) of N points -> (F, height, width, 3) uint8, what
+    PIL.Image.fromarray takes.  xlim / ylim: a (lo, hi) pair for all figures or one a figure.  vmin / vmax: a number or one a
+    figure; by default the finite minimum and maximum of each figure's values (one host read; 0 and 0 where none is finite).
+    A point is a filled disc of `radius` pixels in the viridis colour of its value, composited over what lies below with `alpha`
+    in the order of the input (the later point on top) and clipped at the frame; a point whose coordinate or value is not
+    finite draws nothing.  labels: the axis titles, a pair of strings or one pair a figure, in the characters of SCATTER_FONT.
+    out: a contiguous uint8 tensor of the result's size to write into (any start address)."""
+    import math
+    import numpy as np
+    if not torch.is_tensor(points) or not torch.is_tensor(values) or points.dtype != torch.float32 or values.dtype != torch.float32:
+        raise TypeError('render_scatter needs fp32 tensors of points and values')
+    if values.dim() != 2 or tuple(points.shape) != (values.shape[0], values.shape[1], 2):
+        raise ValueError(f'render_scatter needs points (F, N, 2) and values (F, N), got {tuple(points.shape)} and {tuple(values.shape)}')
+    f, n = values.shape
+    if not 1 <= f <= _lib.SCATTER_MAX_FIGURES:
+        raise ValueError(f'render_scatter renders 1 to {_lib.SCATTER_MAX_FIGURES} figures a launch, got {f}')
+    limits = np.zeros((f, 6), np.float32)
+    limits[:, 0:2], limits[:, 2:4] = _per_figure('xlim', xlim, f, 2), _per_figure('ylim', ylim, f, 2)
+    if not (np.isfinite(limits[:, :4]).all() and (limits[:, 0] < limits[:, 1]).all() and (limits[:, 2] < limits[:, 3]).all()):
+        raise ValueError('render_scatter: xlim and ylim are finite (lo, hi) pairs with lo < hi')
+    if int(radius) != radius or radius < 1:
+        raise ValueError(f'render_scatter: radius {radius} must be a whole number of pixels >= 1')
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f'render_scatter: alpha {alpha} outside [0, 1]')
+    if len(labels) == 2 and all(isinstance(s, str) for s in labels):
+        labels = [tuple(labels)] * f
+    if len(labels) != f or not all(len(pair) == 2 and all(isinstance(s, str) for s in pair) for pair in labels):
+        raise ValueError(f'render_scatter: labels is a pair of axis titles or {f} pairs')
+    _dev(points, values)
+    if points.device != values.device:
+        raise ValueError('render_scatter: points and values live on different devices')
+    for column, given in ((4, vmin), (5, vmax)):
+        if given is not None:
+            limits[:, column] = _per_figure('vmin' if column == 4 else 'vmax', given, f, 1)[:, 0]
+    if vmin is None or vmax is None:                     # as render_pianoroll finds its bounds: the finite values' extremes
+        finite = torch.isfinite(values)
+        lo = torch.where(finite, values, torch.full_like(values, math.inf)).amin(1) if n else torch.full((f,), math.inf)
+        hi = torch.where(finite, values, torch.full_like(values, -math.inf)).amax(1) if n else torch.full((f,), -math.inf)
+        bounds = torch.stack([lo, hi]).cpu().numpy()
+        bounds[:, ~np.isfinite(bounds).all(0)] = 0.0
+        if vmin is None:
+            limits[:, 4] = bounds[0]
+        if vmax is None:
+            limits[:, 5] = bounds[1]
+    if not (np.isfinite(limits[:, 4:]).all() and (limits[:, 4] <= limits[:, 5]).all()):
+        raise ValueError('render_scatter: vmin and vmax are finite with vmin <= vmax')
+    g = scatter_geometry(width, height, radius)
+    per_figure = [scatter_marks(g, limits[i, 0:2].tolist(), limits[i, 2:4].tolist(), limits[i, 4:6].tolist(), labels[i]) for i in range(f)]
+    shared = set.intersection(*per_figure)
+    table = [(m, -1) for m in sorted(shared)] + [(m, i) for i in range(f) for m in sorted(per_figure[i] - shared)]
+    if len(table) > _lib.SCATTER_MAX_MARKS:
+        raise ValueError(f'render_scatter: the figures need {len(table)} marks (ticks and glyphs), the table holds {_lib.SCATTER_MAX_MARKS}: '
+                         'render fewer figures a call')
+    marks = (_lib.ScatterMark * max(len(table), 1))(*[_lib.ScatterMark(x, y, glyph, rot, fig) for (x, y, glyph, rot), fig in table])
+    width, height = int(width), int(height)
+    if out is None:
+        out = torch.empty((f, height, width, 3), device=values.device, dtype=torch.uint8)
+    else:
+        _dev(out)
+        if out.dtype != torch.uint8 or out.numel() != f * height * width * 3 or out.device != values.device or not out.is_contiguous():
+            raise ValueError(f'render_scatter: out must hold {f} x {height} x {width} x 3 contiguous bytes on {values.device}')
+    _lib.check(_lib.load().arvae_render_scatter(_ptr(points) if n else None, _ptr(values) if n else None, f, n,
+                                                limits.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), width, height, int(radius),
+                                                int(math.floor(alpha * 256 + 0.5)), marks, len(table), _ptr(out), _stream()),
+               'render_scatter')
+    return out.view(f, height, width, 3)

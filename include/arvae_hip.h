@@ -632,6 +632,48 @@ int arvae_render_pianoroll(const int64_t *score, int32_t F, int32_t K, int32_t T
                            int32_t pitch_hi, int32_t px_per_twelfth, int32_t px_per_pitch, int32_t mark, int32_t panel_cell,
                            int32_t gap, int32_t dot_radius, uint8_t *out, arvae_stream_t stream);
 
+/* Latent-space scatter figures (added under ABI 16: symbols only; csrc/scatter.hip): N points with a value each -> the bytes of a
+ * figure, F figures in one launch.  Replaces the matplotlib scatter of plot_dim (utils/plotting.py:41-63) behind plot_data_dist
+ * and MeasureVAETrainer.plot_latent_surface.  The look is this library's own:
+ *   canvas  width x height, white.  The plot area is pw x ph = (width - 125) x (height - 39) pixels with its first pixel at
+ *           (px0, py0) = (57, 11) and a black frame one pixel wide around it; a colour bar of bar_w = 12 columns and ph rows starts
+ *           at column bar_x = px0 + pw + 12, framed likewise, row j of it (from the top) showing table entry
+ *           ((ph - 1 - j) 255 + (ph - 1) / 2) / (ph - 1).
+ *   marker  point i of figure f lies at X = (int)floorf((x - xlo) * kx + 0.5f) sixteenths of a pixel from the plot area's left edge,
+ *           kx = (float)(16 pw) / (xhi - xlo), and Y = 16 ph - (int)floorf((y - ylo) * ky + 0.5f) from its top edge, every operation
+ *           rounded to fp32 by itself.  It covers the pixels (i, j) of the plot area with
+ *           (16 i + 8 - X)^2 + (16 j + 8 - Y)^2 <= (16 radius)^2: markers are clipped at the frame.  Its colour is entry
+ *           (int)floorf(c * 255.f + 0.5f) of matplotlib's 256-level viridis table, c = (value - vmin) / (vmax - vmin) clamped to
+ *           [0, 1]; entry 128 when vmax == vmin.  A point whose value is not finite, or whose position is not inside
+ *           (-2^20, 2^20) sixteenths on both axes (a non-finite coordinate among them), draws nothing.
+ *   blend   a channel is held in 1/256ths, white = 255 * 256; the markers that cover a pixel change it in the order of the input,
+ *           c = (c (256 - a) + 256 colour a + 128) >> 8 with a = alpha256, and the byte written is (c + 128) >> 8: the later
+ *           point is on top, and the picture depends on the order of the points alone.
+ *   marks   everything else is a table of at most ARVAE_SCATTER_MAX_MARKS cells laid out by the caller, on the host: a glyph of the
+ *           5 x 7 font "0123456789-.: dimenso" (glyph = its index there; rot = 1: turned a quarter to the left, a cell of 7 x 5
+ *           whose columns are the glyph's rows and whose rows, from the bottom, its columns), a tick mark below an axis
+ *           (ARVAE_SCATTER_TICK_X, 1 x 4) or beside one (ARVAE_SCATTER_TICK_Y, 4 x 1).  (x, y) is the cell's top-left pixel; `figure`
+ *           the figure it belongs to, -1 for all.  Marks are black and drawn outside the two frames only.
+ * points [F, N, 2] fp32 (8-byte aligned), values [F, N] fp32, both on the device (null allowed when N = 0); limits [F][6] on the
+ * HOST: xlo, xhi, ylo, yhi, vmin, vmax per figure (finite, lo < hi, vmin <= vmax); marks on the HOST; out [F, height, width, 3]
+ * uint8 on the device, any alignment.  F <= ARVAE_SCATTER_MAX_FIGURES, 1 <= radius <= 64, 0 <= alpha256 <= 256.
+ * arvae_render_scatter_bytes: height * width * 3, or -1 (a canvas too small for the margins or with 2^31 bytes and more, a bad
+ * radius); `geometry`, unless null, receives px0, py0, pw, ph, bar_x, bar_w. */
+#define ARVAE_SCATTER_MAX_FIGURES 16
+#define ARVAE_SCATTER_MAX_MARKS 384
+#define ARVAE_SCATTER_GLYPHS 21
+#define ARVAE_SCATTER_TICK_X 21
+#define ARVAE_SCATTER_TICK_Y 22
+typedef struct {
+    int16_t x, y;
+    uint8_t glyph, rot;
+    int16_t figure;
+} arvae_scatter_mark_t;
+int64_t arvae_render_scatter_bytes(int32_t width, int32_t height, int32_t radius, int32_t *geometry);
+int arvae_render_scatter(const float *points, const float *values, int32_t F, int64_t N, const float *limits, int32_t width,
+                         int32_t height, int32_t radius, int32_t alpha256, const arvae_scatter_mark_t *marks, int32_t n_marks,
+                         uint8_t *out, arvae_stream_t stream);
+
 /* Attribute labels of a batch of measures.  Replaces MeasureVAETrainer.compute_attribute_labels
  * (measurevae/measure_vae_trainer.py:167-186 -> data/dataloaders/bar_dataset.py:338-500):
  *   out[b] = [rhythmic complexity, pitch range/26, note density, contour/26]

@@ -11,7 +11,9 @@ only) the reference's digit_pred_acc: the accuracy of the ResNet-18 digit classi
 inputs, the reconstructions and the latent sweeps; it needs the classifier's checkpoint, models/MnistRESNET/MnistRESNET.pt.
 `--gifs` writes the reference's latent-traversal GIFs (create_latent_gifs for samples 0, 1 and 4) and `--plots` the PNG figures of
 its commented-out block (plot_latent_reconstructions, plot_latent_interpolations per attribute, plot_latent_interpolations2d)
-into models/<repr>/results/, rendered on the device (arvae_amd.ops.render_frames, HIP).
+into models/<repr>/results/, rendered on the device (arvae_amd.ops.render_frames, HIP).  `--data_dist` writes data_dist_<attr>.png
+there for every attribute (plot_data_dist: the test codes in the plane of the attribute's dimension and a free one, a scatter figure
+rendered on the device, arvae_amd.ops.render_scatter).
 """
 import json
 import os
@@ -71,12 +73,29 @@ PLOTS_FLAG = '--plots'
 PLOTS_HELP = (f'{PLOTS_FLAG}: write the PNG figures (reconstructions, the latent interpolations of every attribute, the 2-d grid '
               'of slant / thickness for mnist, posx / posy for dsprites) into models/<repr>/results/.')
 with_plots = False
+DATA_DIST_FLAG = '--data_dist'
+DATA_DIST_HELP = (f'{DATA_DIST_FLAG}: for every attribute write data_dist_{{attr}}.png into models/<repr>/results/, the codes of the '
+                  'test split (batches of 128, at most 100 of them) in the plane of the attribute\'s dimension of the interpretability '
+                  'metric and the last dimension that belongs to no attribute, coloured by the attribute (plot_data_dist).')
+with_data_dist = False
 
 
 def with_options(fn):
     for names, kwargs in reversed(IMAGE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog='\n\n'.join((METRICS_HELP, DIGIT_ACC_HELP, GIFS_HELP, PLOTS_HELP)))(fn)
+    return click.command(epilog='\n\n'.join((METRICS_HELP, DIGIT_ACC_HELP, GIFS_HELP, PLOTS_HELP, DATA_DIST_HELP)))(fn)
+
+
+def write_data_dist(trainer, dataset, metrics, batch_size):
+    """plot_data_dist for every attribute the interpretability metric names, as the reference's music script does it
+    (train_measure_vae.py:188-197): batches of 128 of the test split, at most 100 of them; -> the paths written"""
+    interp = metrics['interpretability']
+    attr_names = [a for a in trainer.attr_dict if a in interp]
+    attr_dims = [int(interp[a][0]) for a in attr_names]
+    other = [d for d in range(trainer.model.z_dim) if d not in attr_dims][-1]
+    _, _, loader = dataset.data_loaders(batch_size=min(128, batch_size))
+    codes, attrs, _ = trainer.compute_representations(loader, num_batches=min(100, len(loader)))
+    return trainer.plot_data_dist(codes, attrs, attr_names, attr_dims, other)
 
 
 def write_figures(trainer, dataset_type, gifs, plots):
@@ -153,7 +172,7 @@ def main(dataset_type, batch_size, num_epochs, lr, beta, capacity, gamma, delta,
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'latent_mean_abs': [float(v) for v in abs(codes).mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
-        want_figures = with_gifs or with_plots
+        want_figures = with_gifs or with_plots or with_data_dist
         metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or want_figures or (with_digit_acc and dataset_type == 'mnist') else {}
         if with_metrics:
             summary.update(metrics)
@@ -164,23 +183,28 @@ def main(dataset_type, batch_size, num_epochs, lr, beta, capacity, gamma, delta,
             summary.update(trainer.get_resnet_accuracy(batch_size=eval_bs))
         print(json.dumps(summary, indent=2))
         if want_figures and 'interpretability' not in metrics:
-            print(f'{GIFS_FLAG} / {PLOTS_FLAG}: the figures sweep the dimensions of the interpretability metric, which this evaluation '
-                  f'split ({codes.shape[0]} codes) was too small to compute; skipped')
+            print(f'{GIFS_FLAG} / {PLOTS_FLAG} / {DATA_DIST_FLAG}: the figures use the dimensions of the interpretability metric, which this '
+                  f'evaluation split ({codes.shape[0]} codes) was too small to compute; skipped')
         elif want_figures:
             trainer.metrics = dict(metrics)
             for path in write_figures(trainer, dataset_type, with_gifs, with_plots):
                 print('wrote', path)
+            if with_data_dist:
+                trainer.cuda()
+                for path in write_data_dist(trainer, dataset, metrics, batch_size):
+                    print('wrote', path)
 
 
 def run(argv=None):
-    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --digit_acc, --gifs and --plots"""
-    global with_metrics, with_digit_acc, with_gifs, with_plots
+    """the command line: the reference's flags (main) plus this build's opt-in --metrics, --digit_acc, --gifs, --plots and --data_dist"""
+    global with_metrics, with_digit_acc, with_gifs, with_plots, with_data_dist
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
     with_digit_acc = DIGIT_ACC_FLAG in argv
     with_gifs = GIFS_FLAG in argv
     with_plots = PLOTS_FLAG in argv
-    main(args=[a for a in argv if a not in (METRICS_FLAG, DIGIT_ACC_FLAG, GIFS_FLAG, PLOTS_FLAG)])
+    with_data_dist = DATA_DIST_FLAG in argv
+    main(args=[a for a in argv if a not in (METRICS_FLAG, DIGIT_ACC_FLAG, GIFS_FLAG, PLOTS_FLAG, DATA_DIST_FLAG)])
 
 
 if __name__ == '__main__':

@@ -8,7 +8,9 @@ top-k cut, a nucleus cut and the playable-note mask leave) as lists of note name
 rewrites N measures of the evaluation split around the ticks SPEC keeps (MeasureVAETrainer.infill_measures); `--write_midi DIR` writes
 what these two decode into DIR as MIDI files and piano-roll PNGs, `--from_midi FILE` lets `--infill` rewrite the measures of a MIDI
 file, and `--plots` writes the reference's latent-interpolation MIDI files and piano rolls of every attribute
-(MeasureVAETrainer.plot_latent_interpolations) into models/<repr>/results/."""
+(MeasureVAETrainer.plot_latent_interpolations) into models/<repr>/results/; `--data_dist` and `--surfaces` write the scatter figures
+of its commented-out blocks there, data_dist_<attr>.png and latent_surface_<attr>.png (plot_data_dist, plot_latent_surface: rendered
+on the device, arvae_amd.ops.render_scatter)."""
 import json
 import os
 import sys
@@ -101,6 +103,14 @@ FILES_HELP = (f'{PLOTS_FLAG}: for every attribute and the first 20 evaluation co
               'a monophonic MIDI file on the 24-tick grid instead of the evaluation split; the file has as many measures of 4/4 as its '
               'track is long, silent ones included.')
 with_plots, midi_dir, from_midi = False, None, None
+# the latent plane (MeasureVAETrainer.plot_data_dist / plot_latent_surface): the reference script's commented-out blocks
+DATA_DIST_FLAG, SURFACES_FLAG = '--data_dist', '--surfaces'
+PLANE_HELP = (f'{DATA_DIST_FLAG}: for every attribute write data_dist_{{attr}}.png into models/<repr>/results/, the codes of the test '
+              'split (batches of 128, at most 100 of them) in the plane of the attribute\'s dimension of the interpretability metric '
+              f'and the last dimension that belongs to no attribute, coloured by the attribute (listed as `data_dist`).  {SURFACES_FLAG}: '
+              'write latent_surface_{attr}.png of every attribute over the same planes at a grid step of 0.05, each plane decoded '
+              'once for all attributes (listed as `surfaces`).')
+with_data_dist, with_surfaces = False, False
 TICKS = 24
 
 
@@ -127,7 +137,7 @@ def parse_keep_ticks(spec):
 def with_options(fn):
     for names, kwargs in reversed(MEASURE_FLAGS):
         fn = click.option(*names, **kwargs)(fn)
-    return click.command(epilog=METRICS_HELP + '  ' + SAMPLE_HELP + '  ' + INFILL_HELP + '  ' + ALTERNATIVES_HELP + '  ' + FILES_HELP)(fn)
+    return click.command(epilog='  '.join((METRICS_HELP, SAMPLE_HELP, INFILL_HELP, ALTERNATIVES_HELP, FILES_HELP, PLANE_HELP)))(fn)
 
 
 @with_options
@@ -196,7 +206,8 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
         summary = {'model': repr(model), 'num_codes': int(codes.shape[0]), 'attributes': names,
                    'attribute_means': [float(v) for v in attrs.mean(0)]}
         summary.update(trainer.test_model(batch_size=eval_bs))
-        metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or with_plots else {}      # (once: --plots sweeps what --metrics prints)
+        with_plane = with_data_dist or with_surfaces
+        metrics = eval_metrics_or_warn(codes, attrs, names) if with_metrics or with_plots or with_plane else {}      # (once, for all of them)
         if with_metrics:
             summary.update(metrics)
         written = []
@@ -270,6 +281,23 @@ def main(dataset_type, note_embedding_dim, metadata_embedding_dim, num_encoder_l
                 summary['plots'] = []
                 for attr_str in trainer.attr_dict:           # the reference script's live loop (train_measure_vae.py:199-211)
                     summary['plots'] += trainer.plot_latent_interpolations(codes, attr_str=attr_str, num_points=20)
+        if with_plane and 'interpretability' not in metrics:
+            print(f'{DATA_DIST_FLAG} / {SURFACES_FLAG}: the planes are those of the interpretability metric\'s dimensions, which this '
+                  f'evaluation split ({codes.shape[0]} codes) was too small to compute; skipped')
+        elif with_plane:
+            # the reference script's commented-out blocks (train_measure_vae.py:188-210): the attribute's dimension against the last
+            # dimension that belongs to no attribute
+            trainer.cuda()
+            model.eval()
+            attr_names = list(trainer.attr_dict)
+            attr_dims = [int(metrics['interpretability'][a][0]) for a in attr_names]
+            other = [d for d in range(latent_space_dim) if d not in attr_dims][-1]
+            if with_data_dist:
+                _, _, loader = dataset.data_loaders(batch_size=min(128, batch_size))
+                dist_codes, dist_attrs, _ = trainer.compute_representations(loader, num_batches=min(100, len(loader)))
+                summary['data_dist'] = trainer.plot_data_dist(dist_codes, dist_attrs, attr_names, attr_dims, other)
+            if with_surfaces:
+                summary['surfaces'] = trainer.plot_latent_surface(attr_names, attr_dims, other, grid_res=0.05)
         print(json.dumps(summary, indent=2))
 
 
@@ -306,14 +334,15 @@ def _take_value(argv, flag, cast, default):
 
 def run(argv=None):
     """the command line: the reference's flags (main) plus this build's opt-in --metrics, --sample, --temperature, --top_k, --top_p,
-    --playable, --beam, --beam_groups / --diversity, --infill, --plots, --write_midi and --from_midi.  Values of --top_k / --top_p outside their ranges raise the decoder's
+    --playable, --beam, --beam_groups / --diversity, --infill, --plots, --write_midi, --from_midi, --data_dist and --surfaces.  Values of --top_k / --top_p outside their ranges raise the decoder's
     ValueError (sampling_filter); --beam takes a width in [1, 16] and is refused together with --top_k, --top_p or --temperature
     (beam search draws nothing); --beam_groups and --diversity come together and only with --beam."""
     global with_metrics, num_samples, temperature, top_k, top_p, playable, beam, num_infill, keep_ticks, keep_rhythm, drew_notes
-    global beam_groups, diversity, with_plots, midi_dir, from_midi
+    global beam_groups, diversity, with_plots, midi_dir, from_midi, with_data_dist, with_surfaces
     argv = sys.argv[1:] if argv is None else list(argv)
     with_metrics = METRICS_FLAG in argv
     with_plots = PLOTS_FLAG in argv
+    with_data_dist, with_surfaces = DATA_DIST_FLAG in argv, SURFACES_FLAG in argv
     midi_dir, argv = _take_value(argv, WRITE_MIDI_FLAG, str, None)
     from_midi, argv = _take_value(argv, FROM_MIDI_FLAG, str, None)
     playable = PLAYABLE_FLAG in argv
@@ -360,7 +389,7 @@ def run(argv=None):
     if num_samples < 0 or not temperature > 0:
         raise SystemExit(f'{SAMPLE_FLAG} takes a count >= 0 and {TEMPERATURE_FLAG} a positive number')
     check_sampling_cuts(top_k, top_p)          # the decoder's own ValueError, before anything is loaded or trained
-    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG, KEEP_RHYTHM_FLAG, PLOTS_FLAG)])
+    main(args=[a for a in argv if a not in (METRICS_FLAG, PLAYABLE_FLAG, KEEP_RHYTHM_FLAG, PLOTS_FLAG, DATA_DIST_FLAG, SURFACES_FLAG)])
 
 
 if __name__ == '__main__':
