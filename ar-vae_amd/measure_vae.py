@@ -88,9 +88,11 @@ def _boundary_masks(mask, layers, inner, what):
 
 
 def _use_sequence_kernels(hidden):
-    """whole-sequence GRU launches (csrc/gru_seq.hip) when the hidden size is built; ARVAE_GRU_STEPWISE=1 keeps the
-    one-launch-per-time-step path (A/B measurements, and the only path for other hidden sizes)."""
-    return os.environ.get('ARVAE_GRU_STEPWISE', '0') != '1' and ops.gru_sequence_supported(hidden)
+    """whole-sequence GRU calls when the hidden size is built: csrc/gru_seq.hip (32, 64, 128: resident weights, one launch) or
+    csrc/gru_wide.hip (256, 512: streamed weights, one launch per step inside one call).  ARVAE_GRU_STEPWISE=1 keeps the
+    dense + gates launch pair per time step (A/B measurements, and the only path for other hidden sizes)."""
+    return os.environ.get('ARVAE_GRU_STEPWISE', '0') != '1' and (ops.gru_sequence_supported(hidden) or
+                                                                ops.gru_sequence_wide_supported(hidden))
 
 
 class Encoder(Model):

@@ -651,7 +651,7 @@ class _GruSeqFn(Function):
             if finals is not None:
                 q.h_fin, q.h_fin_stride = finals.data_ptr() + 4 * d * hid, ndir * hid
         with _timed('gru_seq_fwd', 2.0 * ndir * steps * rows * 3 * hid * hid, 4.0 * ndir * steps * rows * 8 * hid):
-            _lib.check(lib.arvae_gru_seq_fwd(descs, ndir, steps, rows, hid, _stream()), 'gru_seq_fwd')
+            _lib.check(_gru_seq_call(lib, 'fwd', descs, ndir, steps, rows, hid, dev), 'gru_seq_fwd')
         ctx.save_for_backward(out, saved, *whs, *[h for h in h0s if h is not None])
         ctx.h0_present = [h is not None for h in h0s]
         ctx.gi_const = [g is not None and g.dim() == 2 for g in gis]
@@ -706,7 +706,7 @@ class _GruSeqFn(Function):
             q.dgh, q.dh0 = dgh[d].data_ptr(), _ptr(dh0[d])
             q.h_prev_out = h_prev[d].data_ptr()
         with _timed('gru_seq_bwd', 2.0 * ndir * steps * rows * 3 * hid * hid, 4.0 * ndir * steps * rows * 12 * hid):
-            _lib.check(lib.arvae_gru_seq_bwd(descs, ndir, steps, rows, hid, _stream()), 'gru_seq_bwd')
+            _lib.check(_gru_seq_call(lib, 'bwd', descs, ndir, steps, rows, hid, dev), 'gru_seq_bwd')
         grads = [None, None, None, dgi_all if (ctx.merged and ctx.needs_input_grad[3]) else None]
         link = Link.dense(hid, 3 * hid)
         w_refs, b_refs = ctx.refs
@@ -2094,3 +2094,24 @@ def render_scatter(points, values, xlim, ylim, vmin=None, vmax=None, *, width=48
                                                 int(math.floor(alpha * 256 + 0.5)), marks, len(table), _ptr(out), _stream()),
                'render_scatter')
     return out.view(f, height, width, 3)
+
+
+# ------------------------------------------------------------------------------------------------
+# Hidden sizes 256 and 512: the whole-sequence GRU call on streamed weights (csrc/gru_wide.hip).  (At the end of the file: call
+# sites further up are named by line in tests/workspace_cases.py.)
+# ------------------------------------------------------------------------------------------------
+def gru_sequence_wide_supported(hidden):
+    """the streamed-weights recurrences (csrc/gru_wide.hip: one launch per time step): hidden sizes 256 and 512"""
+    return bool(_lib.load().arvae_gru_seq_wide_supported(int(hidden)))
+
+
+def _gru_seq_call(lib, which, descs, ndir, steps, rows, hid, dev):
+    """_GruSeqFn's library call: arvae_gru_seq_<which> (resident weights, one launch) or, at a wide hidden size,
+    arvae_gru_seq_wide_<which> (one launch per time step inside the call) with its scratch"""
+    if not lib.arvae_gru_seq_wide_supported(hid):
+        return getattr(lib, 'arvae_gru_seq_' + which)(descs, ndir, steps, rows, hid, _stream())
+    n_ws = lib.arvae_gru_seq_wide_ws_floats(ndir, rows, hid)
+    if n_ws < 0:
+        raise RuntimeError(f'gru_seq_wide_{which}: {ndir} sequences of {rows} rows at hidden size {hid}')
+    ws = torch.empty(max(int(n_ws), 4), device=dev, dtype=torch.float32)
+    return getattr(lib, 'arvae_gru_seq_wide_' + which)(descs, ndir, steps, rows, hid, _ptr(ws), _stream())

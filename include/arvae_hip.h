@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ARVAE_ABI_VERSION 16  /* 16: arvae_resnet18_* (inference of the Morpho-MNIST ResNet-18 digit classifier: digit_pred_acc of imagevae/image_vae_trainer.py:319-368), and, added without a new number (symbols only), arvae_sample_filter_t, arvae_row_sample_filtered, arvae_tick_free_run_filtered, arvae_tick_free_run_layers_filtered (top-k, nucleus and note-mask sampling of the free-running decoder); 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
+#define ARVAE_ABI_VERSION 16  /* 16: arvae_resnet18_* (inference of the Morpho-MNIST ResNet-18 digit classifier: digit_pred_acc of imagevae/image_vae_trainer.py:319-368), and, added without a new number (symbols only), arvae_sample_filter_t, arvae_row_sample_filtered, arvae_tick_free_run_filtered, arvae_tick_free_run_layers_filtered (top-k, nucleus and note-mask sampling of the free-running decoder), and arvae_gru_seq_wide_supported / _ws_floats / arvae_gru_seq_wide_fwd / _bwd (the whole-sequence GRU recurrences at hidden sizes 256 and 512: streamed weights, one launch per time step); 15: arvae_tick_stack_t, arvae_tick_free_run_layers_supported / _ws_floats / arvae_tick_free_run_layers (the free-running tick decoder for GRU stacks of 1, 3 or 4 layers: --num_decoder_layers); 14: arvae_philox_uniform, arvae_row_sample, arvae_tick_free_run_sampled (multinomial feedback of the hierarchical decoder: measurevae/decoder.py:372,431-434,502-505); 13: arvae_wide_dense_ws_floats / arvae_wide_dense (the latent block's wide tile GEMMs as per-layer calls); 12: arvae_ksg_ws_bytes / arvae_ksg_mi (the KSG mutual-information estimator of the disentanglement metrics, fp64); 11: arvae_philox_keep_masks (several Dropout masks, one launch); arvae_adam_step(status): the update is skipped while the sticky status word is set (a pass that reported a failed hand-off never reaches the weights), ARVAE_STATUS_* re-coded so that the word survives a float SUM all-reduce beside the gradients; 10: arvae_comm_init(timeout_ms); arvae_image_vae_t.status / .flags (a sticky device status word: an in-launch hand-off between workgroups that gives up says so there instead of hanging; ARVAE_VAE_NO_CLUSTER keeps the pass on kernels without such hand-offs); 9: arvae_measure_vae_* (whole-model MeasureVAE step), row strides for h0 / dh0 / the beat embeddings (arvae_gru_seq_t, arvae_tick_*); 8: arvae_gru_seq_t.gi_rstride / dgi_rstride / h_fin (merged input projections of a bidirectional layer, final states written by the sequence launch); 7: arvae_comm_* (the data-parallel step's collectives: RCCL on the launch stream, owned by the library); 6: the 32-channel k4 s2 p1 links need caller workspace too (arvae_link_ws_floats / arvae_link_wgrad_ws_floats: the layer's weights as scaled fp16 terms and the operands' maxima); 5: arvae_adam_step(zero_grad), arvae_image_vae_finish, arvae_image_vae_t.milestones (events the executors record for the data-parallel caller's collectives); 4: arvae_philox_* and in-kernel eps (arvae_image_vae_t.rng_*), arvae_tick_free_run_supported, caller workspace for arvae_link_down/up (arvae_link_ws_floats); 3: arvae_gru_seq_*, embed_bwd workspace; 2: arvae_image_vae_backward reg_fused == 2 (unit regulariser gradient in dz_extra) */
 
 #define ARVAE_OK 0
 #define ARVAE_E_INVALID (-1)  /* bad argument (null pointer, size out of range, unsupported shape) */
@@ -287,6 +287,23 @@ int arvae_gru_seq_fwd(const arvae_gru_seq_t *seqs, int32_t nseq, int32_t steps, 
                       arvae_stream_t stream);
 int arvae_gru_seq_bwd(const arvae_gru_seq_t *seqs, int32_t nseq, int32_t steps, int32_t rows, int32_t hidden,
                       arvae_stream_t stream);
+
+/* The same recurrences at the hidden sizes the resident-weights kernels above are not built for: 256 and 512
+ * (arvae_gru_seq_wide_supported; MeasureVAE's own default is a 512-wide encoder and decoder).  W_hh is streamed from memory
+ * every step, and a call issues ONE LAUNCH PER TIME STEP on `stream` (the backward one more when any sequence has dh0): a step
+ * needs every unit of the previous state, and no kernel waits for another workgroup.  Descriptor, outputs and the layout of
+ * `saved` are those of arvae_gru_seq_fwd / _bwd; arrays are addressed with 64-bit offsets (no 2 GB limit).  w_hh, h_all, h0,
+ * saved and dgh must be 16-byte aligned, h_stride and h0_stride multiples of 4 floats.
+ * ws: arvae_gru_seq_wide_ws_floats(nseq, rows, hidden) floats of caller scratch, 16-byte aligned, contents irrelevant on entry
+ * (-1: bad arguments); both calls take it, the backward carries the state's gradient between its launches in it.
+ * The calls neither allocate nor synchronise nor read back: a captured graph can hold them.  Results are bit-identical
+ * from run to run (no float atomics). */
+int arvae_gru_seq_wide_supported(int32_t hidden);
+int64_t arvae_gru_seq_wide_ws_floats(int32_t nseq, int32_t rows, int32_t hidden);
+int arvae_gru_seq_wide_fwd(const arvae_gru_seq_t *seqs, int32_t nseq, int32_t steps, int32_t rows, int32_t hidden, float *ws,
+                           arvae_stream_t stream);
+int arvae_gru_seq_wide_bwd(const arvae_gru_seq_t *seqs, int32_t nseq, int32_t steps, int32_t rows, int32_t hidden, float *ws,
+                           arvae_stream_t stream);
 
 /* Free-running pass of the tick decoder (measurevae/decoder.py:459-525 without teacher forcing): 2-layer GRU, note
  * projection + ReLU, top-1 note (lowest index on ties) embedded as the next input, hidden state restarted from
