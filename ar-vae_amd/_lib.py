@@ -177,6 +177,10 @@ SIGNATURES = {
                                              c_vp, c_f32, _P(SampleFilter), c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_planned': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                             c_vp, c_f32, _P(SampleFilter), _P(NotePlan), c_vp, c_vp, c_vp]),
+    'arvae_tick_free_run_wide_supported': (c_i32, [c_i32, c_i32]),
+    'arvae_tick_free_run_wide_ws_floats': (c_i64, [c_i32, c_i32, c_i32]),
+    'arvae_tick_free_run_wide': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                         c_vp, c_f32, _P(SampleFilter), _P(NotePlan), c_vp, c_vp, c_vp, c_vp]),
     'arvae_tick_free_run_layers_supported': (c_i32, [c_i32, c_i32, c_i32]),
     'arvae_tick_free_run_layers_ws_floats': (c_i64, [c_i32, c_i32]),
     'arvae_tick_free_run_layers': (c_i32, [_P(TickStack), c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp,

@@ -767,7 +767,9 @@ class HierarchicalDecoder(Decoder):
 
     def _free_running_tokens(self, beat_out, h0, beat_emb, mask, uniforms=None):
         """feedback pass (no autograd): the tokens the decoder feeds itself, int64 (B, 24): the top-1 note, or with uniforms
-        (B, 24) the note drawn from softmax(probs / temperature) at that tick's uniform."""
+        (B, 24) the note drawn from softmax(probs / temperature) at that tick's uniform.  One library call where a decoder kernel is
+        built: hidden 32 / 64 / 128 one launch (csrc/tick_decoder.hip), hidden 256 / 512 with two layers three launches per tick
+        (csrc/tick_wide.hip); else, and with ARVAE_TICK_STEPWISE=1 (at 256 / 512 also ARVAE_GRU_STEPWISE=1), tick by tick."""
         nb, b = beat_out.shape[0], beat_out.shape[1]
         hid = self.rnn_hidden_size
         w_ih0, w_hh0, b_ih0, b_hh0 = self.rnn_tick.cell(0)
@@ -782,7 +784,10 @@ class HierarchicalDecoder(Decoder):
         if planned is not None:
             top_k, top_p, plan = planned if uniforms is not None else (1, None, planned[2])
             draws = uniforms if uniforms is not None else torch.ones(b, nb * 6, device=beat_out.device)
-        if one_launch:
+        # hidden 256 / 512: one call of three launches per tick (csrc/tick_wide.hip), every pick and the masked training form
+        wide = (not stepwise and not one_launch and layers == 2 and _use_sequence_kernels(hid) and
+                ops.tick_free_run_wide_supported(hid, self.num_notes))
+        if one_launch or wide:
             # one launch (csrc/tick_decoder.hip: tick_free_run_h2_kernel for two layers, tick_free_run_layers_kernel otherwise).  W_ih0
             # acts on [previous-note embedding | beat embedding]: the beat half is applied once per beat, the note half once per
             # vocabulary entry (+ x_0).
@@ -796,6 +801,12 @@ class HierarchicalDecoder(Decoder):
             if layers == 2:
                 w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
                 weights = tuple(t.detach() for t in (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias))
+                if wide:
+                    return ops.tick_free_run_wide(weights, h0[0].detach(), h0[1].detach(), gib, ptab, b, nb, 6,
+                                                  mask=None if mask is None else mask[0].contiguous(), keep_scale=keep_scale,
+                                                  uniforms=draws if planned is not None else uniforms, temperature=self.temperature,
+                                                  filter=(top_k, top_p) if planned is not None else flt,
+                                                  plan=plan if planned is not None else None)
                 if planned is not None:
                     return ops.tick_free_run_planned(weights, h0[0].detach(), h0[1].detach(), gib, ptab, b, nb, 6, draws, plan,
                                                      self.temperature, top_k, top_p)

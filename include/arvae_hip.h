@@ -532,6 +532,35 @@ int arvae_tick_beam_search_planned(const arvae_tick_weights_t *weights, const fl
                                    int32_t *parents, int64_t *tokens, float *scores_hist, int64_t *sequences, float *scores, float *ws,
                                    arvae_stream_t stream);
 
+/* The free-running pass of the two-layer tick decoder at the hidden sizes of arvae_gru_seq_wide_supported (256, 512), every pick in
+ * one entry point.  Inputs as for arvae_tick_free_run (gib / ptab pre-multiplied, the states restarted from h0_l0 / h0_l1 at every
+ * beat), any vocab in [2, 128] (arvae_tick_free_run_wide_supported).  The weights are streamed from memory and a call issues THREE
+ * LAUNCHES PER TICK on `stream` (layer 0, layer 1, logits + pick): a tick needs every unit of the tick before it, and no kernel
+ * waits for another workgroup.  The call neither allocates nor synchronises nor reads back: a captured graph can hold it; results
+ * are bit-identical from run to run.
+ *   The pick of a (row, tick) is what the row entry points above compute on that tick's logits, bit for bit:
+ *     uniforms NULL, filter NULL, plan NULL     arvae_row_argmax
+ *     uniforms, filter NULL, plan NULL          arvae_row_sample at uniforms[row][tick] and inv_temperature
+ *     uniforms, filter, plan NULL               arvae_row_sample_filtered (a filter that cuts nothing: arvae_row_sample)
+ *     uniforms, filter, plan                    arvae_row_sample_planned at that tick; top_k = 1 is the plan's argmax
+ *   mask: the keep-mask [ticks][batch][hidden] of nn.GRU's inter-layer dropout, scaled by keep_scale (the training pass's; argmax
+ *   and unfiltered draws only); NULL for generation.
+ *   tokens [batch][ticks] int64; logits_out: NULL, or [batch][ticks][vocab] = the logits relu(W_out h_l1 + b_out) every pick was
+ *   made from.
+ *   ws: arvae_tick_free_run_wide_ws_floats(batch, hidden, vocab) floats of caller scratch, 16-byte aligned, contents irrelevant on
+ *   entry (-1: bad arguments): the two layers' states of the tick before and of this one, and the rows' previous notes.
+ * ARVAE_E_INVALID with a message before any launch: a mask together with a filter or a plan, a filter or a plan without uniforms, an
+ * inv_temperature that is not positive and finite, w_hh0 / w_ih1 / w_hh1 / w_out / h0_l0 / h0_l1 / ws not 16-byte aligned, an
+ * h0_stride that is no multiple of 4 floats, and whatever arvae_row_sample_filtered / arvae_row_sample_planned refuse of a filter
+ * or a plan. */
+int arvae_tick_free_run_wide_supported(int32_t hidden, int32_t vocab);
+int64_t arvae_tick_free_run_wide_ws_floats(int32_t batch, int32_t hidden, int32_t vocab);
+int arvae_tick_free_run_wide(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1, int64_t h0_stride /* 0 = hidden */,
+                             const float *gib, const float *ptab, const uint8_t *mask, float keep_scale, int32_t batch, int32_t beats,
+                             int32_t ticks_per_beat, int32_t hidden, int32_t vocab, const float *uniforms, float inv_temperature,
+                             const arvae_sample_filter_t *filter, const arvae_note_plan_t *plan, int64_t *tokens, float *logits_out,
+                             float *ws, arvae_stream_t stream);
+
 /* Diverse beam search of the free-running decoder (generation; beyond the reference; Vijayakumar et al. 2016): the W beams of a code
  * in G groups that are served in order at every tick, a group paying `penalty` for every earlier-group beam that has just taken the
  * same note -- a few DIFFERENT likely measures instead of the W most likely ones.  One definition for the entry points below.
