@@ -7,28 +7,21 @@
 // boundary is the launch boundary: no kernel of this file waits for another workgroup (no flags, no spin loops, no grid barrier,
 // no cooperative launch).  A launch per step cannot hang.
 //
-// Tiling, forward and backward alike: a workgroup of four waves owns GW_RT = 32 batch rows x 16 hidden units of one sequence
-// (blockIdx.y) and ALL THREE GATES of those units, so the gate arithmetic needs no other workgroup.  The four waves split the
-// K dimension of the step's GEMM (K = H forward: gh = h_prev . W_hh^T; K = 3H backward: dgh' . W_hh), each on
-// v_mfma_f32_16x16x32_bf16 with THREE-TERM bf16 operands split in registers on the way from memory (splitmath.h: no scale, bf16
-// has fp32's exponent range, so W_hh entries of several hundred and states of several thousand stay finite), two 16-row blocks
-// per wave against the same weight registers.  The partial sums meet in LDS and are added in wave order 0, 1, 2, 3: no float
-// atomics, a call's results are bit-identical from run to run.  The epilogue is lane-local: two (row, unit) elements per lane.
+// Tiling, forward and backward alike: the tile of gru_wide_tile.h (GWT_RT = 32 batch rows x 16 hidden units x ALL THREE GATES per
+// workgroup of four waves, so the gate arithmetic needs no other workgroup) on one sequence (blockIdx.y).  The four waves split
+// the K dimension of the step's GEMM: K = H forward, gh = h_prev . W_hh^T (gwt_gemm3); K = 3H backward, dgh' . W_hh (this file's
+// loop).  The three-term bf16 operands have no scale: bf16 has fp32's exponent range, so W_hh entries of several hundred and
+// states of several thousand stay finite.
 // blockIdx.x = row tile * (H / 16) + unit tile: workgroups are dealt round-robin over the 8 XCDs, H / 16 is a multiple of 8, so
 // the workgroups of one unit tile share an XCD and its L2 holds only that XCD's eighth of W_hh.
 //
 // All addressing is 64-bit pointer arithmetic (a few operations per lane and launch), so there is no 2 GB-per-array limit.
 #include <algorithm>
-#include "common.h"
-#include "dispatch.h"
-#include "splitmath.h"
-#include "gru_common.h"
+#include "gru_wide_tile.h"
 
 namespace arvae {
 
 constexpr int GRU_WIDE_MAX = 4;            // sequences per call (GRU_SEQ_MAX of gru_seq.hip)
-constexpr int GW_RT = 32;                  // batch rows per workgroup
-constexpr int GW_WAVES = 4;                // waves per workgroup: each a quarter of K
 
 // arvae_gru_seq_t with the strides fill_wide() has filled in
 struct GruWideSeq {
@@ -41,49 +34,20 @@ struct GruWideBatch {
     GruWideSeq seq[GRU_WIDE_MAX];
 };
 
-// eight consecutive floats (16-byte aligned) -> their three bf16 operand registers
-__device__ __forceinline__ void gw_load_split(const float *p, bf16x8 &hi, bf16x8 &mid, bf16x8 &lo) {
-    const f32x4 v0 = *reinterpret_cast<const f32x4 *>(p), v1 = *reinterpret_cast<const f32x4 *>(p + 4);
-    const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-    split3_8(x, hi, mid, lo);
-}
-
-// The epilogue's elements: wave w takes row block w & 1 and elements 2 (w >> 1), 2 (w >> 1) + 1 of every lane's 16 x 16 result
-// registers (tile rows 4 quad + i, as in gru_seq.hip), i.e. two batch rows of one hidden unit per lane.
-struct GwElems {
-    int rb, i0, unit, row[2];
-    bool live[2];
-};
-__device__ __forceinline__ GwElems gw_elems(int w, int lane, int row0, int unit0, int R) {
-    GwElems e;
-    e.rb = w & 1;
-    e.i0 = 2 * (w >> 1);
-    e.unit = unit0 + (lane & 15);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int r = row0 + 16 * e.rb + 4 * (lane >> 4) + e.i0 + k;
-        e.live[k] = r < R;
-        e.row[k] = e.live[k] ? r : R - 1;
-    }
-    return e;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // One forward step: gh = h_prev . W_hh^T + b_hh for the tile, then r, z, n, h' (the arithmetic of gru_seq_fwd_h2_kernel's element
 // loop).  h_prev is h0 (or zeros: no GEMM at all) at the first processed step, h_all of the step processed before afterwards.
 // Writes h_all[t], saved[t] (r, z, n, gh_n per (row, unit): gru_seq.hip's layout) and, at the last processed step, h_fin.
 template <int H>
-__global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_fwd_step_kernel(GruWideBatch batch, int T, int R, int step) {
+__global__ __launch_bounds__(64 * GWT_WAVES) void gru_wide_fwd_step_kernel(GruWideBatch batch, int T, int R, int step) {
     constexpr int NU = H / 16;             // unit tiles
-    constexpr int KW = H / GW_WAVES;       // a wave's share of K
-    constexpr int KS = KW / 32;            // its MFMA k-steps
-    static_assert(NU % 8 == 0 && KS >= 1, "unit tiles in multiples of the XCD count; whole k-steps per wave");
-    __shared__ __attribute__((aligned(16))) float red[GW_WAVES][2][3][64][4];           // 24 KB
+    static_assert(NU % 8 == 0, "unit tiles in multiples of the XCD count");
+    __shared__ __attribute__((aligned(16))) GwtRed<3> red;                              // 24 KB
     const GruWideSeq &s = batch.seq[blockIdx.y];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
-    const int row0 = (blockIdx.x / NU) * GW_RT, unit0 = 16 * (blockIdx.x % NU);
+    const int row0 = (blockIdx.x / NU) * GWT_RT, unit0 = 16 * (blockIdx.x % NU);
     const int t = s.reverse ? T - 1 - step : step;
     const float *hp;                       // the state entering this step, row pitch hp_stride; null = zeros
     int64_t hp_stride;
@@ -94,13 +58,13 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_fwd_step_kernel(GruWid
     }
 
     // the epilogue's operands are requested first: they arrive while the GEMM runs
-    const GwElems e = gw_elems(w, lane, row0, unit0, R);
+    const GwtElems e = gwt_elems(w, lane, row0, unit0, R);
     float gi[2][3], hprev[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const float *g = s.gi + (int64_t)t * s.gi_tstride + (int64_t)e.row[k] * s.gi_rstride + e.unit;
+        const float *g = s.gi + (int64_t)t * s.gi_tstride + e.row[k] * s.gi_rstride + e.unit;
         gi[k][0] = g[0]; gi[k][1] = g[H]; gi[k][2] = g[2 * H];
-        hprev[k] = hp != nullptr ? hp[(int64_t)e.row[k] * hp_stride + e.unit] : 0.f;
+        hprev[k] = hp != nullptr ? hp[e.row[k] * hp_stride + e.unit] : 0.f;
     }
     const float bh_r = s.b_hh[e.unit], bh_z = s.b_hh[H + e.unit], bh_n = s.b_hh[2 * H + e.unit];
 
@@ -111,30 +75,14 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_fwd_step_kernel(GruWid
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int g = 0; g < 3; ++g) acc[rb][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // A: lane (col, quad) holds row `col` of a 16-row block, k = 8 quad .. 8 quad + 7 of the k-step; rows past R repeat row R - 1
-        const float *a_src[2];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) a_src[rb] = hp + (int64_t)min(row0 + 16 * rb + col, R - 1) * hp_stride + w * KW + 8 * quad;
-        // B: lane (col, quad) holds unit `col` of the tile, the same k; B[k][n] = W_hh[g H + unit][k]
-        const float *w_src = s.w_hh + (int64_t)(unit0 + col) * H + w * KW + 8 * quad;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 ah[2], am[2], al[2], wh[3], wm[3], wl[3];
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) gw_load_split(a_src[rb] + 32 * ks, ah[rb], am[rb], al[rb]);
-#pragma unroll
-            for (int g = 0; g < 3; ++g) gw_load_split(w_src + (int64_t)g * H * H + 32 * ks, wh[g], wm[g], wl[g]);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                GRU_MFMA6X3(acc[rb][0], acc[rb][1], acc[rb][2], ah[rb], am[rb], al[rb], ah[rb], am[rb], al[rb], ah[rb], am[rb], al[rb],
-                            wh[0], wm[0], wl[0], wh[1], wm[1], wl[1], wh[2], wm[2], wl[2]);
-            }
-        }
+        gwt_gemm3<H, false>(acc, hp, hp_stride, nullptr, 1.f, s.w_hh, row0, unit0, R, w, col, quad);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int g = 0; g < 3; ++g) *reinterpret_cast<f32x4 *>(red[w][rb][g][lane]) = acc[rb][g];
         lds_barrier();
+        // gwt_wave_sum's additions in this file's own text, here and in the backward kernel: through the helper the compiler merges
+        // the two elements' LDS reads into 64-bit ones (6 and 2 read instructions where these kernels were measured with 12 and 4)
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
@@ -142,23 +90,18 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_fwd_step_kernel(GruWid
 #pragma clang fp contract(off)
                 float sum = red[0][e.rb][g][lane][e.i0 + k];
 #pragma unroll
-                for (int q = 1; q < GW_WAVES; ++q) sum = sum + red[q][e.rb][g][lane][e.i0 + k];       // wave order: deterministic
+                for (int q = 1; q < GWT_WAVES; ++q) sum = sum + red[q][e.rb][g][lane][e.i0 + k];      // wave order: deterministic
                 gh[k][g] = sum;
             }
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-#pragma clang fp contract(off)               // GRU_ROUNDING (gru_common.h)
-        const float r = fast_sigmoid((gh[k][0] + gi[k][0]) + bh_r);
-        const float z = fast_sigmoid((gh[k][1] + gi[k][1]) + bh_z);
-        const float ghn = gh[k][2] + bh_n;
-        const float n = fast_tanh(__builtin_fmaf(r, ghn, gi[k][2]));
-        const float hn = __builtin_fmaf(z, hprev[k], (1.f - z) * n);
+        const GwtGates o = gwt_gates(gh[k][0], gh[k][1], gh[k][2], gi[k][0], gi[k][1], gi[k][2], bh_r, bh_z, bh_n, hprev[k]);
         if (e.live[k]) {
             const int64_t tr = (int64_t)t * R + e.row[k];
-            s.h_all[tr * s.h_stride + e.unit] = hn;
-            *reinterpret_cast<f32x4 *>(s.saved + (tr * H + e.unit) * 4) = f32x4{r, z, n, ghn};
-            if (step == T - 1 && s.h_fin != nullptr) s.h_fin[(int64_t)e.row[k] * s.h_fin_stride + e.unit] = hn;
+            s.h_all[tr * s.h_stride + e.unit] = o.hn;
+            *reinterpret_cast<f32x4 *>(s.saved + (tr * H + e.unit) * 4) = f32x4{o.r, o.z, o.n, o.ghn};
+            if (step == T - 1 && s.h_fin != nullptr) s.h_fin[e.row[k] * s.h_fin_stride + e.unit] = o.hn;
         }
     }
 }
@@ -172,21 +115,21 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_fwd_step_kernel(GruWid
 //   dgi[t] = [dpr, dpz, dpn];  dgh[t] = [dpr, dpz, dpn r];  h_prev_out[t] = h_prev;  carry_out = g z
 // (the element arithmetic of gru_seq_bwd_x3_kernel).  B[k = c][n = unit] = W_hh[c][unit], c over the 3H gate columns.
 template <int H>
-__global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_bwd_step_kernel(GruWideBatch batch, int T, int R, int step, const float *carry_in,
+__global__ __launch_bounds__(64 * GWT_WAVES) void gru_wide_bwd_step_kernel(GruWideBatch batch, int T, int R, int step, const float *carry_in,
                                                                            float *carry_out) {
     constexpr int NU = H / 16;
-    constexpr int KW = 3 * H / GW_WAVES;   // a wave's share of K = 3H
+    constexpr int KW = 3 * H / GWT_WAVES;  // a wave's share of K = 3H
     constexpr int KS = KW / 32;
     static_assert(NU % 8 == 0 && KS % 3 == 0, "three k-steps at a time, one per accumulator");
-    __shared__ __attribute__((aligned(16))) float red[GW_WAVES][2][64][4];              // 8 KB
+    __shared__ __attribute__((aligned(16))) GwtRed<1> red;                              // 8 KB
     const GruWideSeq &s = batch.seq[blockIdx.y];
     if (step == T && s.dh0 == nullptr) return;                                          // (uniform: the tail of a sequence without dh0)
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 15, quad = lane >> 4;
-    const int row0 = (blockIdx.x / NU) * GW_RT, unit0 = 16 * (blockIdx.x % NU);
+    const int row0 = (blockIdx.x / NU) * GWT_RT, unit0 = 16 * (blockIdx.x % NU);
     const int64_t seq_off = (int64_t)blockIdx.y * R * H;
-    const GwElems e = gw_elems(w, lane, row0, unit0, R);
+    const GwtElems e = gwt_elems(w, lane, row0, unit0, R);
 
     // the epilogue's operands first
     const int t = step < T ? (s.reverse ? step : T - 1 - step) : 0;
@@ -200,9 +143,9 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_bwd_step_kernel(GruWid
         sv[k] = step < T ? *reinterpret_cast<const f32x4 *>(s.saved + (tr * H + e.unit) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         if (step >= T) hp[k] = 0.f;
         else if (has_prev) hp[k] = s.h_all[((int64_t)(s.reverse ? t + 1 : t - 1) * R + e.row[k]) * s.h_stride + e.unit];
-        else hp[k] = s.h0 != nullptr ? s.h0[(int64_t)e.row[k] * s.h0_stride + e.unit] : 0.f;
-        if (step == 0) c_in[k] = s.dh_last != nullptr ? s.dh_last[(int64_t)e.row[k] * s.dh_last_stride + e.unit] : 0.f;
-        else c_in[k] = carry_in[seq_off + (int64_t)e.row[k] * H + e.unit];
+        else hp[k] = s.h0 != nullptr ? s.h0[e.row[k] * s.h0_stride + e.unit] : 0.f;
+        if (step == 0) c_in[k] = s.dh_last != nullptr ? s.dh_last[e.row[k] * s.dh_last_stride + e.unit] : 0.f;
+        else c_in[k] = carry_in[seq_off + e.row[k] * H + e.unit];
     }
 
     float carry[2] = {c_in[0], c_in[1]};
@@ -228,7 +171,7 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_bwd_step_kernel(GruWid
                 for (int i = 0; i < 8; ++i) x[i] = w_src[(int64_t)(32 * (ks + j) + i) * H];
                 split3_8(x, wh[j], wm[j], wl[j]);
 #pragma unroll
-                for (int rb = 0; rb < 2; ++rb) gw_load_split(a_src[rb] + 32 * (ks + j), ah[rb][j], am[rb][j], al[rb][j]);
+                for (int rb = 0; rb < 2; ++rb) gwt_load_split(a_src[rb] + 32 * (ks + j), ah[rb][j], am[rb][j], al[rb][j]);
             }
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
@@ -239,22 +182,22 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_bwd_step_kernel(GruWid
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
 #pragma clang fp contract(off)
-            *reinterpret_cast<f32x4 *>(red[w][rb][lane]) = (acc[rb][0] + acc[rb][1]) + acc[rb][2];
+            *reinterpret_cast<f32x4 *>(red[w][rb][0][lane]) = (acc[rb][0] + acc[rb][1]) + acc[rb][2];
         }
         lds_barrier();
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
 #pragma clang fp contract(off)
-            float sum = red[0][e.rb][lane][e.i0 + k];
+            float sum = red[0][e.rb][0][lane][e.i0 + k];
 #pragma unroll
-            for (int q = 1; q < GW_WAVES; ++q) sum = sum + red[q][e.rb][lane][e.i0 + k];              // wave order: deterministic
+            for (int q = 1; q < GWT_WAVES; ++q) sum = sum + red[q][e.rb][0][lane][e.i0 + k];          // wave order: deterministic
             carry[k] = c_in[k] + sum;
         }
     }
     if (step == T) {
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            if (e.live[k]) s.dh0[(int64_t)e.row[k] * s.dh0_stride + e.unit] = carry[k];
+            if (e.live[k]) s.dh0[e.row[k] * s.dh0_stride + e.unit] = carry[k];
         return;
     }
 #pragma unroll
@@ -272,7 +215,7 @@ __global__ __launch_bounds__(64 * GW_WAVES) void gru_wide_bwd_step_kernel(GruWid
             dgi[0] = dpr; dgi[H] = dpz; dgi[2 * H] = dpn;
             dgh[0] = dpr; dgh[H] = dpz; dgh[2 * H] = dhn;
             if (s.h_prev_out != nullptr) s.h_prev_out[tr * H + e.unit] = hp[k];
-            carry_out[seq_off + (int64_t)e.row[k] * H + e.unit] = g * z;
+            carry_out[seq_off + e.row[k] * H + e.unit] = g * z;
         }
     }
 }
@@ -293,13 +236,11 @@ static void fill_wide(GruWideBatch *b, const arvae_gru_seq_t *seqs, int nseq, in
     }
 }
 
-static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace arvae
 
 using namespace arvae;
 
-extern "C" int arvae_gru_seq_wide_supported(int32_t hidden) { return hidden == 256 || hidden == 512; }
+extern "C" int arvae_gru_seq_wide_supported(int32_t hidden) { return gwt_hidden_built(hidden); }
 
 // the backward pass's carried z (.) g: two buffers of [nseq][rows][hidden]
 extern "C" int64_t arvae_gru_seq_wide_ws_floats(int32_t nseq, int32_t rows, int32_t hidden) {
@@ -312,21 +253,21 @@ extern "C" int arvae_gru_seq_wide_fwd(const arvae_gru_seq_t *seqs, int32_t nseq,
     ARVAE_REQUIRE(seqs != nullptr && nseq >= 1 && nseq <= GRU_WIDE_MAX, "gru_seq_wide_fwd: 1..%d sequences per call", GRU_WIDE_MAX);
     ARVAE_REQUIRE(steps >= 1 && rows >= 1, "gru_seq_wide_fwd: empty sequence");
     ARVAE_REQUIRE(arvae_gru_seq_wide_supported(hidden), "gru_seq_wide_fwd: hidden size %d is not built (256, 512)", hidden);
-    ARVAE_REQUIRE(ws != nullptr && aligned16(ws), "gru_seq_wide_fwd: workspace missing or not 16-byte aligned (arvae_gru_seq_wide_ws_floats)");
+    ARVAE_REQUIRE(ws != nullptr && gwt_aligned16(ws), "gru_seq_wide_fwd: workspace missing or not 16-byte aligned (arvae_gru_seq_wide_ws_floats)");
     for (int i = 0; i < nseq; ++i)
         ARVAE_REQUIRE(seqs[i].gi && seqs[i].w_hh && seqs[i].b_hh && seqs[i].h_all && seqs[i].saved, "gru_seq_wide_fwd: null pointer");
     GruWideBatch b{};
     fill_wide(&b, seqs, nseq, hidden);
     for (int i = 0; i < nseq; ++i) {
         const GruWideSeq &q = b.seq[i];
-        ARVAE_REQUIRE(aligned16(q.w_hh) && aligned16(q.h_all) && aligned16(q.h0) && aligned16(q.saved) && q.h_stride % 4 == 0 &&
-                          q.h0_stride % 4 == 0,
+        ARVAE_REQUIRE(gwt_aligned16(q.w_hh) && gwt_aligned16(q.h_all) && gwt_aligned16(q.h0) && gwt_aligned16(q.saved) &&
+                          q.h_stride % 4 == 0 && q.h0_stride % 4 == 0,
                       "gru_seq_wide_fwd: w_hh, h_all, h0 and saved must be 16-byte aligned, h_stride and h0_stride multiples of 4 floats");
         ARVAE_REQUIRE(q.h_stride >= hidden, "gru_seq_wide_fwd: h_stride %lld is below the hidden size", (long long)q.h_stride);
     }
     hipStream_t st = as_stream(stream);
-    const dim3 grid((rows + GW_RT - 1) / GW_RT * (hidden / 16), nseq), block(64 * GW_WAVES);
-    const bool known = with_int<256, 512>(hidden, [&](auto HH) {
+    const dim3 grid((rows + GWT_RT - 1) / GWT_RT * (hidden / 16), nseq), block(64 * GWT_WAVES);
+    const bool known = gwt_with_hidden(hidden, [&](auto HH) {
         constexpr int H = decltype(HH)::value;
         for (int step = 0; step < steps; ++step) ARVAE_LAUNCH((gru_wide_fwd_step_kernel<H>), grid, block, 0, st, b, steps, rows, step);
     });
@@ -339,7 +280,7 @@ extern "C" int arvae_gru_seq_wide_bwd(const arvae_gru_seq_t *seqs, int32_t nseq,
     ARVAE_REQUIRE(seqs != nullptr && nseq >= 1 && nseq <= GRU_WIDE_MAX, "gru_seq_wide_bwd: 1..%d sequences per call", GRU_WIDE_MAX);
     ARVAE_REQUIRE(steps >= 1 && rows >= 1, "gru_seq_wide_bwd: empty sequence");
     ARVAE_REQUIRE(arvae_gru_seq_wide_supported(hidden), "gru_seq_wide_bwd: hidden size %d is not built (256, 512)", hidden);
-    ARVAE_REQUIRE(ws != nullptr && aligned16(ws), "gru_seq_wide_bwd: workspace missing or not 16-byte aligned (arvae_gru_seq_wide_ws_floats)");
+    ARVAE_REQUIRE(ws != nullptr && gwt_aligned16(ws), "gru_seq_wide_bwd: workspace missing or not 16-byte aligned (arvae_gru_seq_wide_ws_floats)");
     for (int i = 0; i < nseq; ++i)
         ARVAE_REQUIRE(seqs[i].w_hh && seqs[i].h_all && seqs[i].saved && seqs[i].dgi && seqs[i].dgh, "gru_seq_wide_bwd: null pointer");
     GruWideBatch b{};
@@ -347,14 +288,14 @@ extern "C" int arvae_gru_seq_wide_bwd(const arvae_gru_seq_t *seqs, int32_t nseq,
     bool any_dh0 = false;
     for (int i = 0; i < nseq; ++i) {
         const GruWideSeq &q = b.seq[i];
-        ARVAE_REQUIRE(aligned16(q.dgh) && aligned16(q.saved), "gru_seq_wide_bwd: dgh and saved must be 16-byte aligned");
+        ARVAE_REQUIRE(gwt_aligned16(q.dgh) && gwt_aligned16(q.saved), "gru_seq_wide_bwd: dgh and saved must be 16-byte aligned");
         ARVAE_REQUIRE(q.h_stride >= hidden, "gru_seq_wide_bwd: h_stride %lld is below the hidden size", (long long)q.h_stride);
         any_dh0 = any_dh0 || q.dh0 != nullptr;
     }
     hipStream_t st = as_stream(stream);
-    const dim3 grid((rows + GW_RT - 1) / GW_RT * (hidden / 16), nseq), block(64 * GW_WAVES);
+    const dim3 grid((rows + GWT_RT - 1) / GWT_RT * (hidden / 16), nseq), block(64 * GWT_WAVES);
     const int64_t half = (int64_t)nseq * rows * hidden;
-    const bool known = with_int<256, 512>(hidden, [&](auto HH) {
+    const bool known = gwt_with_hidden(hidden, [&](auto HH) {
         constexpr int H = decltype(HH)::value;
         // step T: the tail, which only completes the carry into dh0
         for (int step = 0; step < steps + (any_dh0 ? 1 : 0); ++step)

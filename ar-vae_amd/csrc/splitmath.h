@@ -183,6 +183,13 @@ template <class T> __device__ __forceinline__ T lds_tr_x8(const void *p0, const 
     ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, WH, ACC, 0, 0, 0);                \
     ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WL, ACC, 0, 0, 0);                \
     ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, WH, ACC, 0, 0, 0)
+#define GRU_MFMA6(ACC, AH, AM, AL, WH, WM, WL)                                         \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AL, WH, ACC, 0, 0, 0);               \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, WL, ACC, 0, 0, 0);               \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AM, WM, ACC, 0, 0, 0);               \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AM, WH, ACC, 0, 0, 0);               \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, WM, ACC, 0, 0, 0);               \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, WH, ACC, 0, 0, 0)
 // ... and three independent accumulators, product-major: consecutive MFMAs never hit the same accumulator (a dependent 16x16x32
 // MFMA waits for its predecessor's result, about twice the issue interval), every accumulator still sees its products in order.
 // K3: accumulator i takes A operand i (three k-steps); X3: one A operand for all three (the three gates)

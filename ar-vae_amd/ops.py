@@ -611,8 +611,25 @@ def gru_sequence_supported(hidden):
     return bool(_lib.load().arvae_gru_seq_supported(int(hidden)))
 
 
+def gru_sequence_wide_supported(hidden):
+    """the streamed-weights recurrences (csrc/gru_wide.hip: one launch per time step): hidden sizes 256 and 512"""
+    return bool(_lib.load().arvae_gru_seq_wide_supported(int(hidden)))
+
+
 def _gru_seq_descs(n):
     return (_lib.GruSeqDesc * n)()
+
+
+def _gru_seq_call(lib, which, descs, ndir, steps, rows, hid, dev):
+    """_GruSeqFn's library call: arvae_gru_seq_<which> (resident weights, one launch) or, at a wide hidden size,
+    arvae_gru_seq_wide_<which> (one launch per time step inside the call) with its scratch"""
+    if not lib.arvae_gru_seq_wide_supported(hid):
+        return getattr(lib, 'arvae_gru_seq_' + which)(descs, ndir, steps, rows, hid, _stream())
+    n_ws = lib.arvae_gru_seq_wide_ws_floats(ndir, rows, hid)
+    if n_ws < 0:
+        raise RuntimeError(f'gru_seq_wide_{which}: {ndir} sequences of {rows} rows at hidden size {hid}')
+    ws = torch.empty(max(int(n_ws), 4), device=dev, dtype=torch.float32)
+    return getattr(lib, 'arvae_gru_seq_wide_' + which)(descs, ndir, steps, rows, hid, _ptr(ws), _stream())
 
 
 class _GruSeqFn(Function):
@@ -858,6 +875,47 @@ def tick_free_run(weights, h0_l0, h0_l1, gib, ptab, mask, keep_scale, batch, bea
                                                        1.0 / float(temperature), _ptr(tokens), _ptr(ws), _stream()),
                        'tick_free_run_sampled')
     return tokens
+
+
+def tick_free_run_wide_supported(hidden, vocab):
+    """True when the streamed-weights free-running tick decoder (csrc/tick_wide.hip: three launches per tick inside one call) is built
+    for (hidden, vocab): hidden 256 or 512, 2 to 128 notes"""
+    return bool(_lib.load().arvae_tick_free_run_wide_supported(int(hidden), int(vocab)))
+
+
+def tick_free_run_wide(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, mask=None, keep_scale=1.0, uniforms=None,
+                       temperature=1.0, filter=None, plan=None, return_logits=False):
+    """tokens (B, beats*ticks_per_beat) int64 of the free-running two-layer tick decoder at hidden 256 / 512 (arvae_tick_free_run_wide;
+    the picks: include/arvae_hip.h).  weights / h0 / gib / ptab / mask as tick_free_run.  uniforms None: argmax; uniforms alone: the
+    multinomial draw; filter = (top_k, top_p, allow) as tick_free_run_filtered; plan (with filter = (top_k, top_p)) as
+    tick_free_run_planned.  return_logits: -> (tokens, logits (B, ticks, V)), the logits every pick was made from."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab, mask, uniforms)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    ticks, dev = beats * ticks_per_beat, gib.device
+    flt = npl = None
+    if filter is not None or plan is not None:
+        top_k, top_p, allow = (tuple(filter) + (None,) * 3)[:3] if filter is not None else (None, None, None)
+        flt, allow = sample_filter(vocab, top_k, top_p, allow)
+    if plan is not None:
+        npl, plan = note_plan(plan, batch, ticks, vocab)
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ticks, batch, hid)):
+        raise ValueError(f'the keep-mask must be uint8 of shape {(ticks, batch, hid)}, got {mask.dtype} {tuple(mask.shape)}')
+    u = None if uniforms is None else _sampling_uniforms(uniforms, (batch, ticks))
+    n_ws = lib.arvae_tick_free_run_wide_ws_floats(batch, hid, vocab)
+    if n_ws < 0:
+        raise RuntimeError(f'tick_free_run_wide: {batch} rows at hidden size {hid} and {vocab} notes')
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    tokens = torch.empty(batch, ticks, device=dev, dtype=torch.int64)
+    logits = torch.empty(batch, ticks, vocab, device=dev, dtype=torch.float32) if return_logits else None
+    ws = torch.empty(int(n_ws), device=dev, dtype=torch.float32)
+    with _timed('tick_free_run_wide', 2.0 * batch * ticks * (9 * hid * hid + vocab * hid), 0.0):
+        _lib.check(lib.arvae_tick_free_run_wide(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), _ptr(mask),
+                                                float(keep_scale), batch, beats, ticks_per_beat, hid, vocab, _ptr(u),
+                                                1.0 / float(temperature), None if flt is None else ctypes.byref(flt),
+                                                None if npl is None else ctypes.byref(npl), _ptr(tokens), _ptr(logits), _ptr(ws),
+                                                _stream()), 'tick_free_run_wide')
+    return (tokens, logits) if return_logits else tokens
 
 
 def tick_free_run_layers_supported(hidden, vocab, layers):
@@ -1933,8 +1991,7 @@ def resnet18_forward(prep, x):
 
 
 # ------------------------------------------------------------------------------------------------
-# scatter figures of the latent plane (csrc/scatter.hip); at the end of the file because tests/workspace_cases.py names an
-# allocation above by its line number
+# scatter figures of the latent plane (csrc/scatter.hip)
 # ------------------------------------------------------------------------------------------------
 SCATTER_FONT = '0123456789-.: dimenso'                 # the glyphs of csrc/scatter.hip's font, a glyph's number its place here
 SCATTER_TICK_X, SCATTER_TICK_Y = 21, 22                # the two tick marks (ARVAE_SCATTER_TICK_X / _Y)
@@ -2094,66 +2151,3 @@ def render_scatter(points, values, xlim, ylim, vmin=None, vmax=None, *, width=48
                                                 int(math.floor(alpha * 256 + 0.5)), marks, len(table), _ptr(out), _stream()),
                'render_scatter')
     return out.view(f, height, width, 3)
-
-
-# ------------------------------------------------------------------------------------------------
-# Hidden sizes 256 and 512: the whole-sequence GRU call on streamed weights (csrc/gru_wide.hip).  (At the end of the file: call
-# sites further up are named by line in tests/workspace_cases.py.)
-# ------------------------------------------------------------------------------------------------
-def gru_sequence_wide_supported(hidden):
-    """the streamed-weights recurrences (csrc/gru_wide.hip: one launch per time step): hidden sizes 256 and 512"""
-    return bool(_lib.load().arvae_gru_seq_wide_supported(int(hidden)))
-
-
-def _gru_seq_call(lib, which, descs, ndir, steps, rows, hid, dev):
-    """_GruSeqFn's library call: arvae_gru_seq_<which> (resident weights, one launch) or, at a wide hidden size,
-    arvae_gru_seq_wide_<which> (one launch per time step inside the call) with its scratch"""
-    if not lib.arvae_gru_seq_wide_supported(hid):
-        return getattr(lib, 'arvae_gru_seq_' + which)(descs, ndir, steps, rows, hid, _stream())
-    n_ws = lib.arvae_gru_seq_wide_ws_floats(ndir, rows, hid)
-    if n_ws < 0:
-        raise RuntimeError(f'gru_seq_wide_{which}: {ndir} sequences of {rows} rows at hidden size {hid}')
-    ws = torch.empty(max(int(n_ws), 4), device=dev, dtype=torch.float32)
-    return getattr(lib, 'arvae_gru_seq_wide_' + which)(descs, ndir, steps, rows, hid, _ptr(ws), _stream())
-
-
-# the free-running tick decoder at the same sizes (csrc/tick_wide.hip); here for the same reason
-def tick_free_run_wide_supported(hidden, vocab):
-    """True when the streamed-weights free-running tick decoder (csrc/tick_wide.hip: three launches per tick inside one call) is built
-    for (hidden, vocab): hidden 256 or 512, 2 to 128 notes"""
-    return bool(_lib.load().arvae_tick_free_run_wide_supported(int(hidden), int(vocab)))
-
-
-def tick_free_run_wide(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, mask=None, keep_scale=1.0, uniforms=None,
-                       temperature=1.0, filter=None, plan=None, return_logits=False):
-    """tokens (B, beats*ticks_per_beat) int64 of the free-running two-layer tick decoder at hidden 256 / 512 (arvae_tick_free_run_wide;
-    the picks: include/arvae_hip.h).  weights / h0 / gib / ptab / mask as tick_free_run.  uniforms None: argmax; uniforms alone: the
-    multinomial draw; filter = (top_k, top_p, allow) as tick_free_run_filtered; plan (with filter = (top_k, top_p)) as
-    tick_free_run_planned.  return_logits: -> (tokens, logits (B, ticks, V)), the logits every pick was made from."""
-    _dev(*weights, h0_l0, h0_l1, gib, ptab, mask, uniforms)
-    lib = _lib.load()
-    hid, vocab = weights[0].shape[1], weights[6].shape[0]
-    ticks, dev = beats * ticks_per_beat, gib.device
-    flt = npl = None
-    if filter is not None or plan is not None:
-        top_k, top_p, allow = (tuple(filter) + (None,) * 3)[:3] if filter is not None else (None, None, None)
-        flt, allow = sample_filter(vocab, top_k, top_p, allow)
-    if plan is not None:
-        npl, plan = note_plan(plan, batch, ticks, vocab)
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ticks, batch, hid)):
-        raise ValueError(f'the keep-mask must be uint8 of shape {(ticks, batch, hid)}, got {mask.dtype} {tuple(mask.shape)}')
-    u = None if uniforms is None else _sampling_uniforms(uniforms, (batch, ticks))
-    n_ws = lib.arvae_tick_free_run_wide_ws_floats(batch, hid, vocab)
-    if n_ws < 0:
-        raise RuntimeError(f'tick_free_run_wide: {batch} rows at hidden size {hid} and {vocab} notes')
-    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
-    tokens = torch.empty(batch, ticks, device=dev, dtype=torch.int64)
-    logits = torch.empty(batch, ticks, vocab, device=dev, dtype=torch.float32) if return_logits else None
-    ws = torch.empty(int(n_ws), device=dev, dtype=torch.float32)
-    with _timed('tick_free_run_wide', 2.0 * batch * ticks * (9 * hid * hid + vocab * hid), 0.0):
-        _lib.check(lib.arvae_tick_free_run_wide(ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), _ptr(mask),
-                                                float(keep_scale), batch, beats, ticks_per_beat, hid, vocab, _ptr(u),
-                                                1.0 / float(temperature), None if flt is None else ctypes.byref(flt),
-                                                None if npl is None else ctypes.byref(npl), _ptr(tokens), _ptr(logits), _ptr(ws),
-                                                _stream()), 'tick_free_run_wide')
-    return (tokens, logits) if return_logits else tokens

@@ -18,7 +18,7 @@ import torch
 import gru_cases as gc
 
 HIDDEN = (256, 512)
-ROW_TILES = (32,)                          # GW_RT of gru_wide.hip: every row-tile height a kernel is instantiated with
+ROW_TILES = (32,)                          # GWT_RT of gru_wide_tile.h: every row-tile height a kernel is instantiated with
 ROWS = (5, 37, 69)                         # 37 = 32 + 5, 69 = 2 * 32 + 5
 STEPS = (1, 6, 24)
 VARIANT_NAMES = ('plain', 'no_h0', 'finals_only', 'constant_gi', 'merged_gi')

@@ -1,5 +1,7 @@
 """tests/workspace_cases.py on the CPU: the table reaches scratch in every family (the size functions are host code), holds the
 shapes its docstrings promise, and its exceptions name single buffers of existing cases."""
+import importlib
+import inspect
 import re
 
 import pytest
@@ -101,6 +103,9 @@ def test_exceptions_name_one_buffer_of_one_case_each():
     for row in wc.EXCEPTIONS:
         case, key, site, why = row
         assert case in wc.BY_NAME and '*' not in case + key + site and key and re.fullmatch(r'[\w.]+\.py:\d+ \(\w+\)', site), row
+        module, line, function = re.fullmatch(r'([\w.]+)\.py:(\d+) \((\w+)\)', site).groups()
+        source, first = inspect.getsourcelines(getattr(importlib.import_module('arvae_amd.' + module), function))
+        assert first <= int(line) < first + len(source), f'{row}: line {line} is outside {function} ({module}.py:{first}-{first + len(source) - 1})'
         assert re.search(r'\w+\.(py|hip|h):\d+', why), f'{row}: the reason names the code line that makes it so'
         assert (case, key) not in seen
         seen.add((case, key))

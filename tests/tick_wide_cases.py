@@ -19,7 +19,7 @@ import functools
 import numpy as np
 
 HIDDEN = (256, 512)
-ROW_TILES = (16, 32)                       # TW_ORT and TW_RT of tick_wide.hip
+ROW_TILES = (16, 32)                       # TW_ORT of tick_wide.hip and GWT_RT of gru_wide_tile.h
 ROWS = (5, 37)                             # 37 = 2 * 16 + 5 = 32 + 5
 VOCABS = (35, 70)
 FORMS = ('argmax', 'multinomial', 'filtered', 'planned', 'planned_argmax')

@@ -539,7 +539,7 @@ def _tick_cases():
 # classifier, KSG
 # =====================================================================================================================
 RESNET_FC_BIAS_PAD = 2                                           # floats behind the 10 fc biases at the end of the prepared block
-EXCEPTIONS += [(f'classify-n{n}', 'prep', 'ops.py:1906 (resnet18_prepare)',
+EXCEPTIONS += [(f'classify-n{n}', 'prep', 'ops.py:1964 (resnet18_prepare)',
                 'resnet18.hip:326 sizes the fc bias as 12 floats (10, padded to a 16-byte multiple), resnet18.hip:459 copies the 10 biases and '
                 'resnet18.hip:294 reads fc_b[0..9] only: the last two floats of the prepared block are a pad nobody writes or reads')
                for n in (1, 3)]
