@@ -216,6 +216,15 @@ SIGNATURES = {
     'arvae_tick_beam_search_ws_floats': (c_i64, [c_i32]),
     'arvae_tick_beam_search': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32,
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_tick_beam_search_wide_supported': (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    'arvae_tick_beam_search_wide_ws_floats': (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    'arvae_tick_beam_search_wide': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                            c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_tick_beam_search_wide_planned': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                    c_i32, _P(NotePlan), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'arvae_tick_beam_search_wide_groups': (c_i32, [_P(TickWeights), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                   c_i32, c_i32, c_f32, _P(NotePlan), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                   c_vp]),
     'arvae_concat_cols': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     'arvae_split_cols': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     'arvae_scale_mask': (c_i32, [c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp]),

@@ -5,7 +5,8 @@
 //                             recurrence (tick_decoder.hip) over the W beams of every code as adjacent rows of a workgroup's tile, and
 //                             between a tick's logits and the next tick's input projection the selection and the row permutation;
 //   beam_select_kernel        the selection alone on given logits, any vocabulary: the tick-by-tick path (ARVAE_TICK_STEPWISE=1, other
-//                             layer counts and hidden sizes, more than 64 notes) and the on-device yardstick of the one-launch kernel;
+//                             layer counts and hidden sizes, more than 64 notes), the on-device yardstick of the one-launch kernel,
+//                             and through beam_select_launch (beam_select.h) every tick of beam_wide.hip's search at 256 / 512;
 //   sequence_log_prob_kernel  sum over t of the masked log-softmax of given logits at given tokens.
 // All three also serve a note plan (include/arvae_hip.h, "Note plans": the allowed notes per (code, tick)); the one-launch kernel has an
 // instantiation of its own for it, in which a code may hold fewer than W finite hypotheses (dead slots).  The one-launch kernel and
@@ -20,10 +21,10 @@
 #include "splitmath.h"
 #include "gru_common.h"
 #include "tick_common.h"
+#include "beam_select.h"
 
 namespace arvae {
 
-constexpr int BEAM_MAX_WIDTH = 16;
 typedef int beam_i32x4 __attribute__((ext_vector_type(4)));
 constexpr int BEAM_MAX_TICKS = 32;                             // the one-launch kernel keeps a measure's history in LDS
 
@@ -141,6 +142,13 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float *__restrict
             seen = made;
         }
     }
+}
+
+void beam_select_launch(const float *logits, const float *scores_in, int codes, int width, int vocab, int live, const uint8_t *allow,
+                        int64_t allow_stride, int *parents, int64_t *notes, float *scores_out, int groups, float penalty,
+                        const float *logp_in, float *logp_out, hipStream_t stream) {
+    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, stream, logits, scores_in, width, vocab, live, allow, allow_stride, parents,
+                 notes, scores_out, groups, penalty, logp_in, logp_out);
 }
 
 // One wave per row r: lane t (and t + 64, ...) takes tick t's masked log-softmax at the token -- the allowed maximum, the sum of
@@ -671,7 +679,7 @@ using namespace arvae;
 
 // what the three entry points check of a width and a mask: 1 <= width <= 16, the mask's count given by the host (the mask lives on the
 // device) and at least `width` notes allowed, so that `width` distinct hypotheses exist after the first tick
-static int beam_width_check(const char *who, int32_t width, int32_t vocab, const uint8_t *allow, int32_t allowed) {
+int arvae::beam_width_check(const char *who, int32_t width, int32_t vocab, const uint8_t *allow, int32_t allowed) {
     ARVAE_REQUIRE(width >= 1 && width <= BEAM_MAX_WIDTH, "%s: width %d is outside [1, %d]", who, width, BEAM_MAX_WIDTH);
     ARVAE_REQUIRE(vocab >= 1, "%s: vocab %d is not positive", who, vocab);
     ARVAE_REQUIRE(allowed >= 1 && allowed <= vocab, "%s: allowed %d is outside [1, vocab = %d]", who, allowed, vocab);
@@ -690,8 +698,8 @@ extern "C" int arvae_beam_select(const float *logits, const float *scores_in, in
     ARVAE_REQUIRE(live >= 1 && live <= width, "beam_select: live %d is outside [1, width = %d]", live, width);
     ARVAE_REQUIRE((int64_t)live * allowed >= width, "beam_select: %d live beams of %d allowed notes give fewer than width = %d candidates",
                   live, allowed, width);
-    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live, allow, (int64_t)0,
-                 parents, notes, scores_out, 1, 0.f, (const float *)nullptr, (float *)nullptr);
+    beam_select_launch(logits, scores_in, codes, width, vocab, live, allow, 0, parents, notes, scores_out, 1, 0.f, nullptr, nullptr,
+                       as_stream(stream));
     return check_launch("beam_select_kernel");
 }
 
@@ -705,14 +713,13 @@ extern "C" int arvae_beam_select_planned(const float *logits, const float *score
     ARVAE_REQUIRE(live >= 1 && live <= width, "beam_select_planned: live %d is outside [1, width = %d]", live, width);
     if (const int rc = note_plan_check("beam_select_planned", plan, ticks, vocab)) return rc;
     ARVAE_REQUIRE(tick >= 0 && tick < ticks, "beam_select_planned: tick %d is outside [0, %d)", tick, ticks);
-    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live,
-                 plan->allow + tick * plan->tick_stride, plan->row_stride, parents, notes, scores_out, 1, 0.f, (const float *)nullptr,
-                 (float *)nullptr);
+    beam_select_launch(logits, scores_in, codes, width, vocab, live, plan->allow + tick * plan->tick_stride, plan->row_stride, parents,
+                       notes, scores_out, 1, 0.f, nullptr, nullptr, as_stream(stream));
     return check_launch("beam_select_kernel");
 }
 
 // what the grouped entry points check of (width, groups, penalty)
-static int beam_groups_check(const char *who, int32_t width, int32_t groups, float penalty) {
+int arvae::beam_groups_check(const char *who, int32_t width, int32_t groups, float penalty) {
     ARVAE_REQUIRE(width >= 1 && width <= BEAM_MAX_WIDTH, "%s: width %d is outside [1, %d]", who, width, BEAM_MAX_WIDTH);
     ARVAE_REQUIRE(groups >= 1 && groups <= width, "%s: groups %d is outside [1, width = %d]", who, groups, width);
     ARVAE_REQUIRE(width % groups == 0, "%s: groups %d does not divide width %d", who, groups, width);
@@ -732,8 +739,8 @@ extern "C" int arvae_beam_select_groups(const float *logits, const float *scores
                   width / groups);
     if (const int rc = note_plan_check("beam_select_groups", plan, ticks, vocab)) return rc;
     ARVAE_REQUIRE(tick >= 0 && tick < ticks, "beam_select_groups: tick %d is outside [0, %d)", tick, ticks);
-    ARVAE_LAUNCH(beam_select_kernel, dim3(codes), dim3(64), 0, as_stream(stream), logits, scores_in, width, vocab, live,
-                 plan->allow + tick * plan->tick_stride, plan->row_stride, parents, notes, scores_out, groups, penalty, logp_in, logp_out);
+    beam_select_launch(logits, scores_in, codes, width, vocab, live, plan->allow + tick * plan->tick_stride, plan->row_stride, parents,
+                       notes, scores_out, groups, penalty, logp_in, logp_out, as_stream(stream));
     return check_launch("beam_select_kernel");
 }
 

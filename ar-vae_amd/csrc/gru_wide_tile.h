@@ -1,5 +1,5 @@
-// The streamed-weights GRU tile of hidden sizes 256 and 512: what the whole-sequence recurrences (gru_wide.hip) and the free-running
-// tick decoder (tick_wide.hip) share.  A workgroup of GWT_WAVES = 4 waves owns GWT_RT = 32 batch rows x 16 hidden units and ALL THREE
+// The streamed-weights GRU tile of hidden sizes 256 and 512: what the whole-sequence recurrences (gru_wide.hip), the free-running
+// tick decoder (tick_wide.hip) and the beam search (beam_wide.hip) share.  A workgroup of GWT_WAVES = 4 waves owns GWT_RT = 32 batch rows x 16 hidden units and ALL THREE
 // GATES of those units.  The waves split the K dimension of a GEMM, each on v_mfma_f32_16x16x32_bf16 with THREE-TERM bf16 operands
 // split in registers on the way from memory (splitmath.h), two 16-row blocks per wave against the same weight registers.  The partial
 // sums meet in LDS and are added in wave order 0, 1, 2, 3 (no float atomics: results are bit-identical from run to run); the
@@ -41,21 +41,21 @@ __device__ __forceinline__ void gwt_load_split(const float *p, bf16x8 &hi, bf16x
     gwt_load_split<false>(p, nullptr, 1.f, hi, mid, lo);
 }
 
-// a wave's quarter of K = H of  acc[rb][g] += a[rows of block rb][:] . wmat[g H + unit tile][:]^T:
-// A: lane (col, quad) holds row `col` of a 16-row block, k = 8 quad .. 8 quad + 7 of the k-step; rows past R repeat row R - 1.
+// a wave's quarter of K = H of  acc[rb][g] += a[src[rb]][:] . wmat[g H + unit tile][:]^T, the lane's operand row of either 16-row
+// block given by the caller (src[rb]: a row of `a` and of the keep-mask; beam_wide.hip reads a beam's parent's state this way):
+// A: lane (col, quad) holds row src[rb] as row `col` of block rb, k = 8 quad .. 8 quad + 7 of the k-step.
 // B: lane (col, quad) holds unit `col` of the tile, the same k; B[k][n] = wmat[g H + unit][k].
 template <int H, bool MASK>
-__device__ __forceinline__ void gwt_gemm3(f32x4 (&acc)[2][3], const float *a, int64_t a_stride, const uint8_t *m, float keep_scale,
-                                          const float *wmat, int row0, int unit0, int R, int w, int col, int quad) {
+__device__ __forceinline__ void gwt_gemm3_rows(f32x4 (&acc)[2][3], const float *a, int64_t a_stride, const uint8_t *m, float keep_scale,
+                                               const float *wmat, const int64_t (&src)[2], int unit0, int w, int col, int quad) {
     constexpr int KW = H / GWT_WAVES, KS = KW / 32;           // a wave's share of K, its MFMA k-steps
     static_assert(KS >= 1, "whole k-steps per wave");
     const float *a_src[2];
     const uint8_t *m_src[2] = {nullptr, nullptr};
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
-        const int64_t r = min(row0 + 16 * rb + col, R - 1);
-        a_src[rb] = a + r * a_stride + w * KW + 8 * quad;
-        if constexpr (MASK) m_src[rb] = m + r * H + w * KW + 8 * quad;
+        a_src[rb] = a + src[rb] * a_stride + w * KW + 8 * quad;
+        if constexpr (MASK) m_src[rb] = m + src[rb] * H + w * KW + 8 * quad;
     }
     const float *w_src = wmat + (int64_t)(unit0 + col) * H + w * KW + 8 * quad;
 #pragma unroll
@@ -71,6 +71,14 @@ __device__ __forceinline__ void gwt_gemm3(f32x4 (&acc)[2][3], const float *a, in
                         wh[0], wm[0], wl[0], wh[1], wm[1], wl[1], wh[2], wm[2], wl[2]);
         }
     }
+}
+
+// gwt_gemm3_rows on the tile's own rows: block rb's row `col` is row0 + 16 rb + col; rows past R repeat row R - 1.
+template <int H, bool MASK>
+__device__ __forceinline__ void gwt_gemm3(f32x4 (&acc)[2][3], const float *a, int64_t a_stride, const uint8_t *m, float keep_scale,
+                                          const float *wmat, int row0, int unit0, int R, int w, int col, int quad) {
+    const int64_t src[2] = {min(row0 + col, R - 1), min(row0 + 16 + col, R - 1)};
+    gwt_gemm3_rows<H, MASK>(acc, a, a_stride, m, keep_scale, wmat, src, unit0, w, col, quad);
 }
 
 // The epilogue's elements: wave w takes row block w & 1 and elements 2 (w >> 1), 2 (w >> 1) + 1 of every lane's 16 x 16 result

@@ -535,8 +535,10 @@ class HierarchicalDecoder(Decoder):
 
     def _beam_history(self, beat_out, width, mask, count, plan=None, groups=None):
         """-> (parents (B, 24, W) int32, tokens (B, 24, W) int64, scores (B, 24, W), sequences (B, W, 24) int64, scores (B, W)): one
-        launch (csrc/beam_decoder.hip, tick_beam_search_kernel) where it is offered, else tick by tick with the existing dense and
-        gate launches, ops.beam_select and a gather of the states (ARVAE_TICK_STEPWISE=1, other layer counts, hidden sizes, V > 64).
+        launch (csrc/beam_decoder.hip, tick_beam_search_kernel) where it is offered; at hidden 256 / 512 with two layers and up to 128
+        notes one call of four launches per tick (csrc/beam_wide.hip, ops.tick_beam_search_wide: plain, planned and grouped alike);
+        else tick by tick with the existing dense and gate launches, ops.beam_select and a gather of the states
+        (ARVAE_TICK_STEPWISE=1, other layer counts, other hidden sizes, V > 128, and V > 64 below hidden 256).
         plan (B, 24, V) uint8 on the device: the planned forms of both (mask and count are then not read).
         groups (G, penalty): the diverse search (include/arvae_hip.h, "Diverse beam search") -- ops.tick_beam_search_groups where
         offered, else ops.beam_select_groups per tick --, plan then always given (B, 24, V) or one mask (V,); a sixth tensor, the
@@ -547,8 +549,11 @@ class HierarchicalDecoder(Decoder):
         w_ih0, w_hh0, b_ih0, b_hh0 = self.rnn_tick.cell(0)
         out = self.tick_emb_to_note_emb[0]
         stepwise = os.environ.get('ARVAE_TICK_STEPWISE', '0') == '1'
-        if not stepwise and layers == 2 and (ops.tick_beam_search_supported(hid, vocab, width) if groups is None else
-                                            ops.tick_beam_search_groups_supported(hid, vocab, width, groups[0])):
+        one_launch = not stepwise and layers == 2 and (ops.tick_beam_search_supported(hid, vocab, width) if groups is None else
+                                                       ops.tick_beam_search_groups_supported(hid, vocab, width, groups[0]))
+        wide = not stepwise and layers == 2 and not one_launch and ops.tick_beam_search_wide_supported(
+            hid, vocab, width, 1 if groups is None else groups[0])
+        if one_launch or wide:
             emb_dim = self.note_embedding_dim
             w_note, w_beat = w_ih0[:, :emb_dim].contiguous(), w_ih0[:, emb_dim:].contiguous()
             gib = ops.dense(beat_emb, w_beat, b_ih0, Link.dense(hid, 3 * hid), ACT_NONE)
@@ -556,6 +561,9 @@ class HierarchicalDecoder(Decoder):
             ptab = ops.dense(table, w_note, None, Link.dense(emb_dim, 3 * hid), ACT_NONE)
             w_ih1, w_hh1, b_ih1, b_hh1 = self.rnn_tick.cell(1)
             weights = (w_hh0, b_hh0, w_ih1, b_ih1, w_hh1, b_hh1, out.weight, out.bias)
+            if wide:
+                return ops.tick_beam_search_wide(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, mask, count,
+                                                 plan, groups)
             if groups is not None:
                 return ops.tick_beam_search_groups(weights, h0[0].contiguous(), h0[1].contiguous(), gib, ptab, b, nb, 6, width, groups[0],
                                                    groups[1], plan)

@@ -2151,3 +2151,55 @@ def render_scatter(points, values, xlim, ylim, vmin=None, vmax=None, *, width=48
                                                 int(math.floor(alpha * 256 + 0.5)), marks, len(table), _ptr(out), _stream()),
                'render_scatter')
     return out.view(f, height, width, 3)
+
+
+def tick_beam_search_wide_supported(hidden, vocab, width, groups=1):
+    """True when the streamed-weights beam search (csrc/beam_wide.hip: four launches per tick inside one call) is built for (hidden,
+    vocab, width, groups): hidden 256 or 512, 2 to 128 notes, widths 1 to 16, groups dividing the width (1: not grouped)"""
+    return bool(_lib.load().arvae_tick_beam_search_wide_supported(int(hidden), int(vocab), int(width), int(groups)))
+
+
+def tick_beam_search_wide(weights, h0_l0, h0_l1, gib, ptab, batch, beats, ticks_per_beat, width, allow=None, allowed=None, plan=None,
+                          groups=None, return_logits=False):
+    """the beam search of the two-layer tick decoder at hidden 256 / 512 in one call (arvae_tick_beam_search_wide, _planned, _groups):
+    neither plan nor groups -> tick_beam_search's five tensors under the mask `allow`; plan -> tick_beam_search_planned's; groups =
+    (G, penalty) with plan (B, T, V), (T, V) or one mask (V,) -> tick_beam_search_groups' six.  return_logits: the logits (B, T, W, V)
+    every tick's selection was made from, appended."""
+    _dev(*weights, h0_l0, h0_l1, gib, ptab)
+    lib = _lib.load()
+    hid, vocab = weights[0].shape[1], weights[6].shape[0]
+    ticks, dev, width = beats * ticks_per_beat, gib.device, int(width)
+    if groups is not None:
+        if plan is None:
+            raise ValueError('tick_beam_search_wide: groups need a plan (every note: a mask of ones)')
+        npl, plan = _groups_plan(plan, batch, ticks, vocab)
+    elif plan is not None:
+        npl, plan = note_plan(plan, batch, ticks, vocab)
+    else:
+        allow, count = _beam_mask(vocab, allow) if allowed is None or allow is None else (allow.contiguous(), int(allowed))
+    n_ws = lib.arvae_tick_beam_search_wide_ws_floats(batch, ticks, hid, vocab, width)
+    if n_ws < 0:
+        raise RuntimeError(f'tick_beam_search_wide: {batch} codes of width {width} over {ticks} ticks at hidden size {hid} and {vocab} notes')
+    tw = _lib.TickWeights(*[_ptr(t) for t in weights])
+    parents = torch.empty(batch, ticks, width, device=dev, dtype=torch.int32)
+    tokens = torch.empty(batch, ticks, width, device=dev, dtype=torch.int64)
+    hist = torch.empty(batch, ticks, width, device=dev, dtype=torch.float32)
+    seqs = torch.empty(batch, width, ticks, device=dev, dtype=torch.int64)
+    scores = torch.empty(batch, width, device=dev, dtype=torch.float32)
+    logp = torch.empty(batch, width, device=dev, dtype=torch.float32) if groups is not None else None
+    logits = torch.empty(batch, ticks, width, vocab, device=dev, dtype=torch.float32) if return_logits else None
+    ws = torch.empty(int(n_ws), device=dev, dtype=torch.float32)
+    head = (ctypes.byref(tw), _ptr(h0_l0), _ptr(h0_l1), 0, _ptr(gib), _ptr(ptab), batch, beats, ticks_per_beat, hid, vocab, width)
+    outs = (_ptr(parents), _ptr(tokens), _ptr(hist), _ptr(seqs), _ptr(scores))
+    with _timed('tick_beam_search_wide', 2.0 * batch * width * ticks * (9 * hid * hid + vocab * hid), 0.0):
+        if groups is not None:
+            _lib.check(lib.arvae_tick_beam_search_wide_groups(*head, int(groups[0]), float(groups[1]), ctypes.byref(npl), *outs, _ptr(logp),
+                                                              _ptr(logits), _ptr(ws), _stream()), 'tick_beam_search_wide_groups')
+        elif plan is not None:
+            _lib.check(lib.arvae_tick_beam_search_wide_planned(*head, ctypes.byref(npl), *outs, _ptr(logits), _ptr(ws), _stream()),
+                       'tick_beam_search_wide_planned')
+        else:
+            _lib.check(lib.arvae_tick_beam_search_wide(*head, _ptr(allow), count, *outs, _ptr(logits), _ptr(ws), _stream()),
+                       'tick_beam_search_wide')
+    res = (parents, tokens, hist, seqs, scores) + (() if groups is None else (logp,))
+    return res + (logits,) if return_logits else res

@@ -599,6 +599,40 @@ int arvae_tick_beam_search_groups(const arvae_tick_weights_t *weights, const flo
                                   const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens, float *scores_hist,
                                   int64_t *sequences, float *scores, float *log_probs, float *ws, arvae_stream_t stream);
 
+/* Beam search at the hidden sizes of arvae_gru_seq_wide_supported (256, 512): the three searches above ("Beam search", "Note plans",
+ * "Diverse beam search": the same inputs, outputs and meanings) for the two-layer tick RNN with streamed weights, any vocab in
+ * [2, 128], every width in [1, 16], groups dividing the width (arvae_tick_beam_search_wide_supported; groups 0 or 1: not grouped),
+ * any number of ticks.  One call issues FOUR LAUNCHES PER TICK on `stream` (layer 0, layer 1, logits, selection), one before the first
+ * tick and one after the last: a tick needs every unit of the tick before it, and no kernel waits for another workgroup.  The call
+ * neither allocates nor synchronises nor reads back: a captured graph can hold it; results are bit-identical from run to run.
+ *   Rows are code * W + k.  A beam's previous states are read from its parent's row (an index in the loads: no gather, no copy); the
+ *   recurrence is arvae_tick_free_run_wide's, bit for bit (W = 1 is its argmax run), and the selection of tick t is
+ *   arvae_beam_select / _planned / _groups on that tick's logits, the scores (and log_probs) of the tick before (zeros at tick 0) and
+ *   live = 1 at tick 0, else W (grouped: at most W / G), bit for bit.
+ *   logits_out: NULL, or [batch][ticks][W][vocab] = the logits every tick's selection was made from.
+ *   ws: arvae_tick_beam_search_wide_ws_floats(batch, ticks, hidden, vocab, width) floats of caller scratch, 16-byte aligned, contents
+ *   irrelevant on entry (-1: bad arguments): the states of two ticks, a tick's logits and the history of the search, tick-major.
+ * ARVAE_E_INVALID with a message before any launch: w_hh0 / w_ih1 / w_hh1 / w_out / h0_l0 / h0_l1 / ws not 16-byte aligned, an
+ * h0_stride that is no multiple of 4 floats, and whatever the one-launch searches refuse of a width, a mask, a plan or groups. */
+int arvae_tick_beam_search_wide_supported(int32_t hidden, int32_t vocab, int32_t width, int32_t groups);
+int64_t arvae_tick_beam_search_wide_ws_floats(int32_t batch, int32_t ticks, int32_t hidden, int32_t vocab, int32_t width);
+int arvae_tick_beam_search_wide(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1, int64_t h0_stride /* 0 = hidden */,
+                                const float *gib, const float *ptab, int32_t batch, int32_t beats, int32_t ticks_per_beat, int32_t hidden,
+                                int32_t vocab, int32_t width, const uint8_t *allow, int32_t allowed, int32_t *parents, int64_t *tokens,
+                                float *scores_hist, int64_t *sequences, float *scores, float *logits_out, float *ws,
+                                arvae_stream_t stream);
+int arvae_tick_beam_search_wide_planned(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1,
+                                        int64_t h0_stride /* 0 = hidden */, const float *gib, const float *ptab, int32_t batch,
+                                        int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int32_t width,
+                                        const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens, float *scores_hist,
+                                        int64_t *sequences, float *scores, float *logits_out, float *ws, arvae_stream_t stream);
+int arvae_tick_beam_search_wide_groups(const arvae_tick_weights_t *weights, const float *h0_l0, const float *h0_l1,
+                                       int64_t h0_stride /* 0 = hidden */, const float *gib, const float *ptab, int32_t batch,
+                                       int32_t beats, int32_t ticks_per_beat, int32_t hidden, int32_t vocab, int32_t width, int32_t groups,
+                                       float penalty, const arvae_note_plan_t *plan, int32_t *parents, int64_t *tokens,
+                                       float *scores_hist, int64_t *sequences, float *scores, float *log_probs, float *logits_out,
+                                       float *ws, arvae_stream_t stream);
+
 /* out[r] = [a[r] | b[r]] (torch.cat along dim 1/2, decoder.py:503) and its adjoint (db optionally accumulated) */
 int arvae_concat_cols(const float *a, const float *b, int64_t rows, int32_t ca, int32_t cb, float *out,
                       arvae_stream_t stream);
