@@ -526,7 +526,7 @@ int conv_c1_wgrad_partial(const arvae_link_t *l, const Operand &lo, const Operan
 
 // the deferred finishing step by itself (a backward pass whose first launch is not the paired one above)
 __global__ __launch_bounds__(512) void vae_finish_deferred_kernel(const VaeFinishArgs *__restrict__ fin) {
-    __shared__ float4 red4[8];
+    __shared__ float4 red4[16];
     const VaeFinishArgs args = *fin;
     vae_finish_body<512>(args, red4);
 }

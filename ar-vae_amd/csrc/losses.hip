@@ -44,8 +44,8 @@ __global__ __launch_bounds__(256) void kld_fwd_kernel(const float *__restrict__ 
                                                        const float *__restrict__ pm, const float *__restrict__ ps,
                                                        int64_t count, float inv_batch, float beta,
                                                        const float *__restrict__ cap, float *__restrict__ out) {
-    __shared__ float red[4];
-    float s = 0.f;
+    __shared__ double red[4];
+    double s = 0.0;
     // one workgroup: eight elements per thread in flight (one element per iteration was a memory round trip each: 13 us for the
     // MeasureVAE's 8192 latent values)
     for (int64_t i0 = threadIdx.x; i0 < count; i0 += 256 * 8) {
@@ -60,9 +60,11 @@ __global__ __launch_bounds__(256) void kld_fwd_kernel(const float *__restrict__ 
         for (int u = 0; u < 8; ++u)
             if (i0 + 256 * u < count) s += kl_elem(m[u], g[u], qm[u], qs[u]);
     }
-    const float tot = block_sum_256(s, red);
+    s = wave_sum(s);                                      // (in double, as the elements: vae_finish.h kl_elem)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
     if (threadIdx.x == 0) {
-        const float kl = tot * inv_batch;
+        const float kl = kl_mean(red[0] + red[1] + red[2] + red[3], inv_batch);
         out[0] = beta * fabsf(kl - (cap ? cap[0] : 0.f));
         out[1] = kl;
     }
@@ -399,7 +401,7 @@ __device__ __forceinline__ float block_sum_1024(float v, float *red) {       // 
 
 // (VaeFinishArgs and the finishing body: vae_finish.h -- the last decoder layer's backward launch can carry it, conv_c1.hip)
 __global__ __launch_bounds__(1024) void vae_finish_kernel(VaeFinishArgs p) {
-    __shared__ float4 red4[16];
+    __shared__ float4 red4[32];
     vae_finish_body<1024>(p, red4);
 }
 

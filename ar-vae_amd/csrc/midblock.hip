@@ -642,6 +642,14 @@ static void mid_describe(const arvae_image_vae_t *m, const float *params, float 
         const bool shape_ok = !midc_topology(m, ne, nd);
         pl.wide_e = shape_ok && ne >= 1 && a.enc[0].k >= MID_WIDE_MIN && a.enc[0].k % 4 == 0 && a.enc[0].n % 4 == 0;
         pl.wide_d = shape_ok && nd >= 2 && a.dec[nd - 1].n >= MID_WIDE_MIN && a.dec[nd - 1].k % 4 == 0 && a.dec[nd - 1].n % 4 == 0;
+        // ... and only a layer whose four products fit them (dense.hip wide_gemm_fits), decided HERE: once to_planes() below has
+        // given the fp32 layouts' space to the planes the row kernels cannot take the layer back.  The narrow side is the
+        // reduction axis of the product that reads the small activation as planes (whole RG_R chunks) and the column axis of a
+        // "K x rows" product (8 columns per load); the encoder layer's data gradient has the wide side as that column axis.
+        // (A result of more tiles than AMAX entries is no reason to leave: mid_forward / mid_backward then take its maximum in
+        // a launch of its own.)
+        pl.wide_e = pl.wide_e && a.enc[0].n % RG_R == 0 && a.enc[0].k % 8 == 0;
+        pl.wide_d = pl.wide_d && a.dec[nd - 1].k % RG_R == 0;
         // their ONE prepared copy: the three bf16 terms of W'[n_mem][k_mem] as planes, in the space of the fp32 layouts they replace
         auto to_planes = [&](MidLayer &ml, MidPrepJob &j) {
             const int n_pad = (ml.n + 31) / 32 * 32, kb_pad = (ml.k + 31) / 32 * 32;

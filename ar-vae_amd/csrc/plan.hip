@@ -976,7 +976,14 @@ extern "C" int arvae_image_vae_backward(const arvae_image_vae_t *m, int32_t batc
             // `cur` is the gradient at the transposed conv layer's output, left by the layer behind it: the block takes it from
             // there (it must be w.r.t. the pre-activation: that layer's data-gradient kernel gates with the sign bits the
             // forward launch wrote) and hands the gradient at the conv layer's INPUT on
-            ARVAE_REQUIRE(pre, "image_vae_backward: the folded conv layer needs a gated upstream gradient");
+            if (!pre) {
+                // the layer behind it had no kernel with a gated epilogue (a layer without activation takes the per-layer link
+                // kernels): fold the folded layer's ReLU into the gradient in place, as layer_backward does for the wide layers
+                const arvae_layer_t &fd = m->dec[mid_nd];
+                const arvae_operand_t gop{cur, V.dec[mid_nd].out, nullptr, fd.act};
+                if (int rc = arvae_operand_apply(&gop, out_elems(fd, batch), cur, stream)) return rc;
+                pre = true;
+            }
             mf.hi_e = V.enc[e0 - 2].out;
             mf.g_hi_d = cur;
             mf.d_hi_e = V.enc[e0 - 2].keep;

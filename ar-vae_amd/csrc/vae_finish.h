@@ -9,11 +9,28 @@
 
 namespace arvae {
 
-__device__ __forceinline__ float kl_elem(float mu, float s, float m0, float s0) {
-    const float r = s / s0, d = (mu - m0) / s0;
-    const float var = r * r;
-    return 0.5f * (var + d * d - 1.f - logf(var));       // torch _kl_normal_normal
+// One element of KL(N(mu, s) || N(m0, s0)), torch _kl_normal_normal, in double.  Where s is near s0 the terms var - 1 - log(var)
+// cancel to a few ulp of 1: evaluated and summed in fp32, a handful of latent values left the KL mean 1 - 2 fp32 ulp from the mean
+// of its own inputs (tests/test_latent_block_float64.py holds the scalars to float64).  In double, elements and sums, the mean
+// is the correctly rounded one; the few thousand latent values of a batch make this no cost that shows.
+__device__ __forceinline__ double kl_elem(float mu, float s, float m0, float s0) {
+    const double r = (double)s / (double)s0, d = ((double)mu - (double)m0) / (double)s0;
+    const double var = r * r;
+    return 0.5 * (var + d * d - 1.0 - log(var));
 }
+// ... against N(0, 1), out of line: the finishing body below holds 16 elements of six arrays per thread and rides in the last decoder
+// layer's backward launch (conv_c1.hip pair_c1_kernel), whose occupancy its registers set -- 160 VGPRs this way, 174 inlined
+__device__ __noinline__ double kl_elem_std(float mu, float s) {
+    const double var = (double)s * (double)s;
+    return 0.5 * (var + (double)mu * (double)mu - 1.0 - log(var));
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// the mean of a KL sum over `batch` rows from the fp32 reciprocal the argument blocks carry: 1 / inv_batch is the batch to 2^-24
+__device__ __forceinline__ float kl_mean(double total, float inv_batch) { return (float)(total / rint(1.0 / (double)inv_batch)); }
 
 struct VaeFinishArgs {
     const float *rec_partial; int nb; float inv_batch, inv_count, inv_rec;     // reconstruction (inv_rec scales the summed term)
@@ -23,14 +40,15 @@ struct VaeFinishArgs {
     float *rec_out, *kld_out, *reg_out, *scalars;
 };
 
-// NT threads of ONE workgroup run it; red4: NT / 64 float4 of LDS scratch
+// NT threads of ONE workgroup run it; red4: NT / 32 float4 of LDS scratch (a float4 of sums per wave, behind them a double per wave)
 template <int NT>
 __device__ __forceinline__ void vae_finish_body(const VaeFinishArgs &p, float4 *red4) {
     // One workgroup, so the kernel is as long as its chain of dependent memory round trips: the first FU * NT (= 8192) elements of
     // every array (all of them at the sizes of this repo's models) are loaded before anything is summed -- one round trip --
     // and only what is left beyond that runs as plain loops.  Fixed summation order; 32-bit index math throughout.
     constexpr int FU = 8192 / NT;
-    float a = 0.f, b = 0.f, s = 0.f, t = 0.f;
+    float a = 0.f, b = 0.f, t = 0.f;
+    double s = 0.0;
     const int bz = (int)p.bz;
     const bool reg = p.row_loss != nullptr, want_dz = reg && p.dz != nullptr;
     const int n_rows = (int)p.n_rows, ldz = (int)p.ldz, nr = reg ? n_rows * p.r : 0, nz = want_dz ? n_rows * ldz : 0;
@@ -63,20 +81,23 @@ __device__ __forceinline__ void vae_finish_body(const VaeFinishArgs &p, float4 *
         for (int u = 0; u < FU; ++u) {
             const int i = base + threadIdx.x + u * NT;
             if (i < p.nb) { a += rp[u].x; b += rp[u].y; }
-            if (i < bz) s += kl_elem(mu[u], sg[u], 0.f, 1.f);
+            if (i < bz) s += kl_elem_std(mu[u], sg[u]);
             if (i < nr) t += rl[u];
             if (i < nz) p.dz[i] = dk[u] < 0 ? 0.f : p.grad_scale * rg[u];
         }
     }
-    float4 v = make_float4(wave_sum(a), wave_sum(b), wave_sum(s), wave_sum(t));
+    float4 v = make_float4(wave_sum(a), wave_sum(b), 0.f, wave_sum(t));
+    const double sw = wave_sum(s);
+    double *red_kl = reinterpret_cast<double *>(red4 + NT / 64);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red4[wave] = v;
+    if (lane == 0) { red4[wave] = v; red_kl[wave] = sw; }
     __syncthreads();
     if (threadIdx.x == 0) {
         float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+        double tot_kl = 0.0;
 #pragma unroll
-        for (int w = 0; w < NT / 64; ++w) { tot.x += red4[w].x; tot.y += red4[w].y; tot.z += red4[w].z; tot.w += red4[w].w; }
-        const float rec = tot.x * p.inv_rec, acc = tot.y * p.inv_count, kl = tot.z * p.inv_batch, reg = tot.w * p.loss_scale;
+        for (int w = 0; w < NT / 64; ++w) { tot.x += red4[w].x; tot.y += red4[w].y; tot_kl += red_kl[w]; tot.w += red4[w].w; }
+        const float rec = tot.x * p.inv_rec, acc = tot.y * p.inv_count, kl = kl_mean(tot_kl, p.inv_batch), reg = tot.w * p.loss_scale;
         const float dist = p.beta * fabsf(kl - (p.cap ? p.cap[0] : 0.f));
         p.rec_out[0] = rec; p.rec_out[1] = acc;
         p.kld_out[0] = dist; p.kld_out[1] = kl;
